@@ -16,7 +16,11 @@ N GPUs (one process per GPU, torch.distributed over RCCL):
       and reported as `weak_scaling` (the replica figure).
 One broadcast of the weights at start in both modes.
 
-Prints ONE JSON line on rank 0 (see the driver contract) with extra objects:
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 (see the driver contract).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see `dump_outputs`).
+--full adds everything beside the headline, each measured after it in the same process: the quality of what was
+coded, the weak-scaling figure (N > 1), `pipelined`, `high_rate`, `bitstream_only_encoder`, the other version of the
+fp32 contract, `precision_mode` and the two objects below (the --no-* options switch single ones off):
   roofline      dominant kernel (fp32 MFMA implicit-GEMM conv): algorithmic FLOPs per launch / average launch
                 duration, measured with HIP events on the launch stream during an extra, untimed, instrumented
                 step; `hbm_stages`: achieved GB/s of the memory-bound stages against the 8 TB/s HBM peak.
@@ -106,6 +110,43 @@ def gpu_synthetic_unit(width, height, n_frames, t0, device, seed):
             f[k] = a.round().clamp(0, 255).to(torch.uint8).unsqueeze(0).contiguous()
         out.append(f)
     return out
+
+
+def dump_outputs(out_dir, blobs, enc_recs, dec, seed=2718):
+    """--dump-outputs: what a caller of the timed path receives from one step, as float32 / float64 .npy files (about
+    40 MB at most, whatever the clip): the bitstream of every unit (its length in full and a fixed, seeded sample of its
+    bytes) and, per plane, a fixed, seeded sample of the pixels of all decoded frames and of all reconstructions of the
+    encoder, with each frame's exact plane sums over every pixel.  Frames are in unit order, display order inside a unit.
+    Sample positions depend only on `seed`, the name of the array and its size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    limits = {'y': 1 << 21, 'u': 1 << 19, 'v': 1 << 19}
+
+    def sample_index(name, n, k):
+        if n <= k:
+            return np.arange(n)
+        rng = np.random.default_rng([seed, sum(map(ord, name))])
+        return np.unique(rng.integers(0, n, k))
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+    stream = np.frombuffer(b''.join(blobs), dtype=np.uint8)
+    save('bitstream_lengths', np.array([len(b) for b in blobs], np.float64))
+    save('bitstream_sample', stream[sample_index('bitstream', stream.size, 1 << 22)].astype(np.float32))
+    for prefix, frames in (('decoded', [f for u in sorted(dec) for f in dec[u]]),
+                           ('encoder_recon', [f for u in (enc_recs or []) for f in u])):
+        if not frames:
+            continue
+        sums = np.zeros((len(frames), 3), np.float64)
+        for j, k in enumerate('yuv'):
+            sums[:, j] = torch.stack([f[k].double().sum() for f in frames]).cpu().numpy()  # integers: exact in any order
+            planes = torch.stack([f[k].reshape(-1) for f in frames])  # [frames, pixels] uint8, on the device
+            idx = sample_index(prefix + '_' + k, planes.numel(), limits[k])
+            vals = planes.reshape(-1)[torch.from_numpy(idx).to(planes.device)]
+            save('%s_%s_sample' % (prefix, k), vals.cpu().numpy().astype(np.float32))
+            del planes
+        save(prefix + '_plane_sums', sums)
 
 
 def cpu_baseline(width, height, model, fc, dev, gop_name='1_GOP_32', unit_frames=33):
@@ -283,6 +324,12 @@ def main():
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--active-y', type=str, default='6,12',
                     help='non-zero y feature maps MOFNet,CodecNet the synthetic model is calibrated to (64,64 = high rate)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline (quality, weak scaling, roofline, CPU baseline, pipelined, '
+                         'high rate, bitstream-only encoder, other contract version, precision mode); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (bitstream, decoded frames, encoder reconstructions; '
+                         'fixed seeded samples, float32 / float64) as DIR/<name>.npy')
     args = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -351,7 +398,7 @@ def main():
         fr = fr + [fr[-1]] * (coded - args.frames)
         return [fr[u * unit:(u + 1) * unit] for u in range(n_units)]
 
-    n_total = args.warmup + args.steps + 1
+    n_total = args.warmup + args.steps + (1 if args.full else 0)  # (--full: one more clip for the instrumented step)
     shard = parallel.ClipShard(n_units, dev) if sharded else None
     # strong: every rank holds the same clips; weak: rank r codes clips r, r + world, ...
     clips = [make_clip(i if strong else rank + i * world) for i in range(n_total)]
@@ -390,12 +437,17 @@ def main():
         if use_dist:
             dist.barrier()
 
-    def timed_run(sh, first):
+    def timed_run(sh, first, keep_last=False):
+        """-> wall seconds of args.steps steps; with keep_last, (seconds, what the last step returned)"""
         barrier()
         torch.cuda.synchronize()
         t0 = time.time()
+        last = None
         for i in range(first, first + args.steps):
-            step(clips[i], timed=True, sh=sh)
+            if keep_last and i == first + args.steps - 1:
+                last = step(clips[i], timed=True, sh=sh)
+            else:
+                step(clips[i], timed=True, sh=sh)
         torch.cuda.synchronize()
         barrier()
         el = time.time() - t0
@@ -407,7 +459,7 @@ def main():
             tt = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        return el
+        return (el, last) if keep_last else el
 
     # ---- warm-up; closed loop (decoder == encoder reconstruction) and, for the sharded path, bytes == single rank
     def warm_up():
@@ -445,7 +497,11 @@ def main():
         closed_loop, bytes_equal = warm_up()
     if bytes_equal is False:
         raise SystemExit('bench.py: sharded bitstream differs from the single-rank bitstream')
-    elapsed = timed_run(shard, args.warmup)
+    elapsed, last_step = timed_run(shard, args.warmup, keep_last=True)
+    if args.dump_outputs and rank == 0 and last_step is not None:
+        blobs, _, enc_recs, dec = last_step
+        dump_outputs(args.dump_outputs, blobs, enc_recs, dec)
+    del last_step
     main_stats = dict(stats)
     clips_done_for_hr = args.steps * args.frames
     # every range-decode launch of the run left its bit count behind (real_life/bitstream.py): judged now, outside the
@@ -454,7 +510,7 @@ def main():
 
     # ---- the other scaling mode, reported next to the headline (N > 1 only: at N = 1 they coincide)
     other = None
-    if world > 1 and args.scaling == 'auto':
+    if args.full and world > 1 and args.scaling == 'auto':
         weak_clips = [make_clip(rank + i * world) for i in range(args.steps)]
         clips_backup, clips = clips, weak_clips
         stats.update(enc_s=0.0, dec_s=0.0, bytes=0)
@@ -471,7 +527,7 @@ def main():
     # about the codec's rate-distortion -- they are the "PSNR/bpp" slots of the metric, filled by the same code
     # that would score real weights.
     quality = None
-    if rank == 0 and not os.environ.get('AIVC_NO_QUALITY'):
+    if args.full and rank == 0 and not os.environ.get('AIVC_NO_QUALITY'):
         from aivc_amd.clic21.metrics import evaluate
         src_unit = clips[args.warmup][0]
         with torch.no_grad():
@@ -488,7 +544,7 @@ def main():
                    'note': 'synthetic random-init weights: not a rate-distortion result'}
 
     roofline = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         ops.PROFILE = []
         ops.PROFILE_HBM = []
         ops.PROFILE_DIRECT_EQUIVALENT[:] = [0.0, 0.0]
@@ -586,7 +642,7 @@ def main():
                                         for name, d in sorted(hbm.items()) if name.startswith('cdf_points:')}}
 
     cpu = None
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.width, args.height, model, fc, dev, args.gop, unit)
 
     # ---- two clips in flight (never the headline): the decoder's entropy stage depends on the bitstream only, so the decode of
@@ -621,7 +677,7 @@ def main():
                 'vs_headline': round(n_steps * args.frames / el / (clips_done_for_hr / elapsed), 4)}
 
     pipelined = None
-    if rank == 0 and world == 1 and not args.no_pipelined:
+    if args.full and rank == 0 and world == 1 and not args.no_pipelined:
         pipelined = pipelined_run(fc, args.pipelined_steps)
         pipelined['note'] = ('decode of clip i split around the encode of clip i + 1 (decode_units_begin / _finish): the entropy stage of a clip runs '
                              'under the next clip\'s transforms; the serial step stays the headline')
@@ -630,7 +686,7 @@ def main():
     # networks non-zero, the serial range coder's streams at their longest), same clip, same run, outside `value`
     high_rate = None
     c_y = widths['c_y']
-    if rank == 0 and world == 1 and not args.no_high_rate and tuple(active_y) != (c_y, c_y):
+    if args.full and rank == 0 and world == 1 and not args.no_high_rate and tuple(active_y) != (c_y, c_y):
         model_hr = synth.make_model(widths, seed=seed, device=dev)
         synth.calibrate_operating_point(model_hr, dev, active_y=(c_y, c_y))
         fc_hr = FrameCodec(model_hr, max_batch=args.max_batch, entropy_streams=args.entropy_streams,
@@ -674,7 +730,7 @@ def main():
     # ---- bitstream-only encoder (FrameCodec.encode_units(recon='refs'); never the headline: `value` keeps the encoder that
     # reconstructs every frame, as the reference's does): frames no other frame references skip their CodecNet synthesis
     lean_encoder = None
-    if rank == 0 and world == 1 and not args.no_lean_encoder:
+    if args.full and rank == 0 and world == 1 and not args.no_lean_encoder:
         with torch.no_grad():
             ref_blobs, _, _ = fc.encode_units(clips[0], args.gop)
             blobs, lean_recs, dd = fc.encode_units(clips[0], args.gop, recon='refs')
@@ -716,7 +772,7 @@ def main():
     # (tests/test_gpu_winograd.py), other bits than version 1 (the 9-tap chains, 'fp32').
     contract_v2 = None
     other_contract = 'fp32' if args.contract == 'fp32w' else 'fp32w'
-    if rank == 0 and world == 1 and not args.no_contract_v2:
+    if args.full and rank == 0 and world == 1 and not args.no_contract_v2:
         prev_prec = ops.set_precision(other_contract)
         try:
             with torch.no_grad():
@@ -768,7 +824,7 @@ def main():
     # ---- the bf16x3 precision MODE (aivc_conv_params.precision; never the headline: `value` stays the fp32 contract):
     # same clip, same model, same code path with the wide convolutions on six bf16 MFMA products per fp32 product
     precision_mode = None
-    if rank == 0 and world == 1 and not args.no_precision_mode:
+    if args.full and rank == 0 and world == 1 and not args.no_precision_mode:
         prev_prec = ops.set_precision('bf16x3')
         try:
             with torch.no_grad():

@@ -35,7 +35,7 @@ def _run(n, extra=(), timeout=900):
 def test_bench_multi_rank_flow_end_to_end(n, cuda):
     """416x240, 64 frames under `1_GOP_16` = 4 intra-period units of 17 frames (the clip of configs[3] in small): on 2
     ranks two groups ... on 4 ranks four groups of one rank; strong scaling is the headline, weak beside it."""
-    out, err = _run(n)
+    out, err = _run(n, ['--full'])  # (the weak-scaling object is measured by --full runs only)
     assert out['n_gpus'] == n and out['steps'] == 1 and out['warmup'] == 1
     assert out['scaling'] == 'strong'
     assert out['bytes_equal_single_rank'] is True and out['closed_loop_ok'] is True

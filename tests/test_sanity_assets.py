@@ -14,7 +14,7 @@ import sys
 
 import pytest
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 MODEL = 'ms_ssim-2021cc-6'
 VIDEO = 'BlowingBubbles_416x240_50_420.yuv'
@@ -30,11 +30,10 @@ def _assets():
 
 
 def test_expected_numbers_are_the_readme_s():
-    """(runs everywhere) the constants above are the ones the reference documents"""
-    readme = '/root/reference/README.md'
-    if not os.path.isfile(readme):
-        pytest.skip('reference not mounted here')
-    text = open(readme).read()
+    """(runs everywhere) the constants above are the ones the reference documents: the output block of its README
+    (README.md:167-170), stored verbatim as tests/golden/sanity_expected_output.txt"""
+    with open(os.path.join(GOLDEN, 'sanity_expected_output.txt')) as f:
+        text = f.read()
     for k, v in EXPECT.items():
         assert re.search(re.escape(k) + r':\s*' + re.escape(('%.5f' % v) if isinstance(v, float) else str(v)), text), k
 

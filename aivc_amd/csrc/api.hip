@@ -1,5 +1,4 @@
 // api.hip -- library identity, error plumbing and the conv dispatcher.
-#include <stdlib.h>
 #include <string.h>
 
 #include "common.h"
@@ -22,12 +21,6 @@ int check_launch(const char *what) {
 
 AIVC_EXPORT int aivc_abi_version(void) { return AIVC_ABI_VERSION; }
 AIVC_EXPORT const char *aivc_last_error(void) { return aivc::g_err; }
-
-// tuning aid: AIVC_GDN_RESIDENT=0 sends stand-alone (I)GDN launches to the generic kernel again (bit identical)
-static bool gdn_resident_on() {
-  static const bool on = !(getenv("AIVC_GDN_RESIDENT") && atoi(getenv("AIVC_GDN_RESIDENT")) == 0);
-  return on;
-}
 
 static int validate_conv(const aivc_conv_params *p) {
   if (!p || !p->x || !p->w || !p->y) return AIVC_ERR_ARG;
@@ -63,26 +56,44 @@ static int validate_conv(const aivc_conv_params *p) {
   return AIVC_OK;
 }
 
-AIVC_EXPORT int aivc_conv2d_variant(const aivc_conv_params *p) {
-  int rc = validate_conv(p);
+// The kernel family a launch takes: the one dispatch rule of aivc_conv2d and aivc_conv2d_variant.
+enum ConvRoute { ROUTE_DIRECT, ROUTE_MFMA, ROUTE_GDN_RESIDENT, ROUTE_THIN, ROUTE_WINO, ROUTE_BF16X3 };
+
+// -> a ConvRoute, or the (negative) error code aivc_conv2d returns without a launch
+static int conv_route(const aivc_conv_params *p) {
+  const int rc = validate_conv(p);
   if (rc != AIVC_OK) return rc;
-  // version 2 of the contract: the layers it covers run the Winograd chain or nothing (a fused gdn is two launches there)
+  // version 2 of the fp32 contract: a covered layer is computed by the Winograd chain or not at all (never silently by
+  // the tap chain: the two differ in the last bits and an encoder / decoder pair must agree); a fused gdn is two launches there
   if (p->precision == AIVC_PREC_FP32_WINO && aivc_winograd_covers(p))
-    return aivc::conv2d_wino_supported(*p) ? aivc::conv2d_wino_variant(*p) : AIVC_ERR_UNSUPPORTED;
-  if (p->gdn && (p->algo == AIVC_ALGO_DIRECT || !aivc::conv2d_mfma_supported(*p))) return AIVC_ERR_UNSUPPORTED;
-  // 1000 + the fp32 code with the mode's tile: the precision mode takes this launch
-  if (p->precision == AIVC_PREC_BF16X3 && p->algo != AIVC_ALGO_DIRECT && aivc::conv2d_bf16x3_supported(*p) &&
-      aivc::conv2d_mfma_supported(*p) && (!p->tail_c_out || aivc::conv2d_mfma_tail_supported(*p)))
-    return p->tail_c_out ? 1190 : 1000 + 100 + 10 * (p->mode == AIVC_MODE_TCONV ? 1 : 0) + aivc::conv2d_bf16x3_tile(*p) + (p->gdn ? 50 : 0);
-  if (p->tail_c_out) {
-    if (p->algo == AIVC_ALGO_DIRECT || !aivc::conv2d_mfma_tail_supported(*p)) return AIVC_ERR_UNSUPPORTED;
-    return aivc::conv2d_mfma_variant(*p);
+    return aivc::conv2d_wino_supported(*p) ? ROUTE_WINO : AIVC_ERR_UNSUPPORTED;
+  const bool direct = p->algo == AIVC_ALGO_DIRECT, auto_ = p->algo == AIVC_ALGO_AUTO;
+  // precision mode (never the default): the shapes it covers; everything else runs the fp32 contract
+  if (p->precision == AIVC_PREC_BF16X3 && !direct && aivc::conv2d_bf16x3_supported(*p) && aivc::conv2d_mfma_supported(*p) &&
+      (!p->tail_c_out || aivc::conv2d_mfma_tail_supported(*p)))
+    return ROUTE_BF16X3;
+  // fused (I)GDN and fused 1x1 tail exist on the MFMA path only
+  if (p->gdn) return direct || !aivc::conv2d_mfma_supported(*p) ? AIVC_ERR_UNSUPPORTED : ROUTE_MFMA;
+  if (p->tail_c_out) return direct || !aivc::conv2d_mfma_tail_supported(*p) ? AIVC_ERR_UNSUPPORTED : ROUTE_MFMA;
+  if (direct) return ROUTE_DIRECT;
+  if (p->algo == AIVC_ALGO_MFMA) return ROUTE_MFMA;
+  if (auto_ && aivc::gdn_resident_supported(*p)) return ROUTE_GDN_RESIDENT;  // stand-alone (I)GDN: same bits as the MFMA GDN mode
+  if (auto_ && aivc::conv2d_thin_supported(*p)) return ROUTE_THIN;
+  return aivc::conv2d_mfma_supported(*p) ? ROUTE_MFMA : ROUTE_DIRECT;
+}
+
+AIVC_EXPORT int aivc_conv2d_variant(const aivc_conv_params *p) {
+  const int route = conv_route(p);
+  switch (route) {
+    case ROUTE_DIRECT: return 0;
+    case ROUTE_MFMA: return aivc::conv2d_mfma_variant(*p);
+    case ROUTE_GDN_RESIDENT: return 400;
+    case ROUTE_THIN: return aivc::conv2d_thin_variant(*p);
+    case ROUTE_WINO: return aivc::conv2d_wino_variant(*p);
+    case ROUTE_BF16X3:  // 1000 + the fp32 code with the mode's tile
+      return p->tail_c_out ? 1190 : 1000 + 100 + 10 * (p->mode == AIVC_MODE_TCONV ? 1 : 0) + aivc::conv2d_bf16x3_tile(*p) + (p->gdn ? 50 : 0);
+    default: return route;
   }
-  if (p->algo == AIVC_ALGO_DIRECT) return 0;
-  if (p->algo == AIVC_ALGO_AUTO && gdn_resident_on() && aivc::gdn_resident_supported(*p)) return 400;
-  if (p->algo == AIVC_ALGO_AUTO && aivc::conv2d_thin_supported(*p)) return aivc::conv2d_thin_variant(*p);
-  if (p->algo == AIVC_ALGO_MFMA || aivc::conv2d_mfma_supported(*p)) return aivc::conv2d_mfma_variant(*p);
-  return 0;
 }
 
 AIVC_EXPORT int aivc_split_weights_bf16x3(const float *w, int32_t c_out, int32_t k_total, void *out, aivc_stream_t stream) {
@@ -120,31 +131,17 @@ AIVC_EXPORT int aivc_conv_images(const aivc_image_src *src, int32_t n_img, const
 }
 
 AIVC_EXPORT int aivc_conv2d(const aivc_conv_params *p, aivc_stream_t stream) {
-  int rc = validate_conv(p);
-  if (rc != AIVC_OK) return rc;
+  const int route = conv_route(p);
   hipStream_t s = aivc::to_stream(stream);
-  // version 2 of the fp32 contract: a covered layer is computed by the Winograd chain or not at all (never silently by
-  // the tap chain: the two differ in the last bits and an encoder / decoder pair must agree)
-  if (p->precision == AIVC_PREC_FP32_WINO && aivc_winograd_covers(p)) {
-    if (!p->w_wino || ((uintptr_t)p->w_wino & 15u) || ((uintptr_t)p->x & 15u)) return AIVC_ERR_ARG;  // (16-byte LDS-DMA loads)
-    return aivc::conv2d_wino(*p, s);
+  switch (route) {
+    case ROUTE_DIRECT: return aivc::conv2d_direct(*p, s);
+    case ROUTE_MFMA: return aivc::conv2d_mfma(*p, s);
+    case ROUTE_GDN_RESIDENT: return aivc::gdn_resident(*p, s);
+    case ROUTE_THIN: return aivc::conv2d_thin(*p, s);
+    case ROUTE_WINO:
+      if (!p->w_wino || ((uintptr_t)p->w_wino & 15u) || ((uintptr_t)p->x & 15u)) return AIVC_ERR_ARG;  // (16-byte LDS-DMA loads)
+      return aivc::conv2d_wino(*p, s);
+    case ROUTE_BF16X3: return aivc::conv2d_bf16x3(*p, s);
+    default: return route;
   }
-  // precision mode (never the default): the shapes it covers; everything else runs the fp32 contract
-  if (p->precision == AIVC_PREC_BF16X3 && p->algo != AIVC_ALGO_DIRECT && aivc::conv2d_bf16x3_supported(*p) &&
-      aivc::conv2d_mfma_supported(*p) && (!p->tail_c_out || aivc::conv2d_mfma_tail_supported(*p)))
-    return aivc::conv2d_bf16x3(*p, s);
-  if (p->gdn) {  // fused (I)GDN exists on the MFMA path only
-    if (p->algo == AIVC_ALGO_DIRECT || !aivc::conv2d_mfma_supported(*p)) return AIVC_ERR_UNSUPPORTED;
-    return aivc::conv2d_mfma(*p, s);
-  }
-  if (p->tail_c_out) {  // fused 1x1 tail: MFMA path only
-    if (p->algo == AIVC_ALGO_DIRECT || !aivc::conv2d_mfma_tail_supported(*p)) return AIVC_ERR_UNSUPPORTED;
-    return aivc::conv2d_mfma(*p, s);
-  }
-  if (p->algo == AIVC_ALGO_DIRECT) return aivc::conv2d_direct(*p, s);
-  if (p->algo == AIVC_ALGO_MFMA) return aivc::conv2d_mfma(*p, s);
-  if (gdn_resident_on() && aivc::gdn_resident_supported(*p)) return aivc::gdn_resident(*p, s);  // stand-alone (I)GDN: same bits as the GDN-mode launch below
-  if (aivc::conv2d_thin_supported(*p)) return aivc::conv2d_thin(*p, s);
-  if (aivc::conv2d_mfma_supported(*p)) return aivc::conv2d_mfma(*p, s);
-  return aivc::conv2d_direct(*p, s);
 }

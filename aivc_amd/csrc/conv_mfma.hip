@@ -1309,9 +1309,8 @@ static int launch_cfg2(const aivc_conv_params &p, hipStream_t s) {
 #ifndef AIVC_CONV_BF16X3
 // LDS-DMA K loop: conv with c_in % 32 == 0 on the tiles it is instantiated for; per-lane BYTE offsets are 32 bits
 static bool use_glds(const aivc_conv_params &p) {
-  static const int off = getenv("AIVC_NO_GLDS") ? atoi(getenv("AIVC_NO_GLDS")) : 0;  // tuning aid: 1 = the register-staged loop everywhere, 2 = for transposed conv
-  if (off == 1 || (off == 2 && p.mode == AIVC_MODE_TCONV) || (p.mode != AIVC_MODE_CONV && p.mode != AIVC_MODE_TCONV)) return false;
-  if (p.c_in % BK != 0 && (p.mode != AIVC_MODE_CONV || off == 3)) return false;  // generic K: conv only (3 = tuning aid: off)
+  if (p.mode != AIVC_MODE_CONV && p.mode != AIVC_MODE_TCONV) return false;
+  if (p.c_in % BK != 0 && p.mode != AIVC_MODE_CONV) return false;  // generic K: conv only
   return (uint64_t)p.n * p.h_in * p.w_in * p.c_in * 4ull < 0xFFFFFFFFull && (uint64_t)p.c_out * p.ksize * p.ksize * p.c_in * 4ull < 0xFFFFFFFFull;
 }
 
@@ -1369,9 +1368,8 @@ static int pick_tile_auto(const aivc_conv_params &p) {
   // workgroups per CU: 48 KB of ring, <= 172 registers) beats 128x128 (two) wherever BN = 128 fits -- 5x5 s2 64->128
   // + GDN 135.3 -> 137.8, 3x3 128->128 138.4 -> 140.3 (+ GDN 131.9 -> 133.5), transposed 5x5 128->128 122.6 -> 132.9
   // (+ GDN 114.6 -> 127.4), transposed 3x3 115.0 -> 118.5 TFLOP/s; for c_out = 64 the transposed 5x5 + GDN runs
-  // 121.5 on 256x64, 125.1 on 128x64, 125.6 on 64x64.  AIVC_TILE_RULES_R2 restores the round-2 rules below.
-  static const bool r2_rules = getenv("AIVC_TILE_RULES_R2") != nullptr;
-  if (!r2_rules && p.c_in % BK == 0 && (p.mode == AIVC_MODE_CONV || t)) {
+  // 121.5 on 256x64, 125.1 on 128x64, 125.6 on 64x64.
+  if (p.c_in % BK == 0 && (p.mode == AIVC_MODE_CONV || t)) {
     // Round 4: few tiles (a single frame's 1/16-resolution layers: 8160 pixels = 128 tiles of 64x128 for 256 CUs): the 64x64
     // tile doubles the workgroup count -- 3x3 128->128 at 68x120, batch 1: 53 -> 90 TFLOP/s, transposed 5x5 94 -> 104, equal
     // from ~512 tiles on (tools/_ab_tiles_n4.sh at BATCH=1 / 4).  Not with a fused GDN (its tile must hold all channels).
@@ -1393,21 +1391,17 @@ static int pick_tile_auto(const aivc_conv_params &p) {
   };
   // stand-alone (I)GDN launch (K = C: bound by its memory traffic): with 128 channels the 128-column tile reads the input
   // once as the GEMM operand instead of once per 64-column tile (round 6: the second launch of a Winograd-covered layer,
-  // 4.0 -> see experiments/r06.md); AIVC_GDN_TILE overrides (tuning aid)
-  if (p.mode == AIVC_MODE_GDN || p.mode == AIVC_MODE_IGDN) {
-    static const int gdn_tile = getenv("AIVC_GDN_TILE") ? atoi(getenv("AIVC_GDN_TILE")) : -1;
-    if (gdn_tile >= 0) return gdn_tile;
-    return co == 128 ? 5 : 1;
-  }
+  // 4.0 -> see experiments/r06.md)
+  if (p.mode == AIVC_MODE_GDN || p.mode == AIVC_MODE_IGDN) return co == 128 ? 5 : 1;
   double best = score(128, 128, 512, 0.80);  // 176 registers: two workgroups per CU
   int tile = 0;
   const double s1 = score(64, 64, 1536, kred <= 256 ? 0.85 : 0.74);
   if (s1 > best) best = s1, tile = 1;
-  if ((t && p.ksize == 3) || (!r2_rules && p.c_in % BK == 0 && co % 128 != 0)) {
+  if ((t && p.ksize == 3) || (p.c_in % BK == 0 && co % 128 != 0)) {
     const double s5 = score(64, 128, 1024, t && p.ksize == 3 ? 0.75 : 0.80);
     if (s5 > best) best = s5, tile = 5;
   }
-  if (!r2_rules && co % 128 != 0) {
+  if (co % 128 != 0) {
     const double s6 = score(128, 64, 1024, 0.76);
     if (s6 > best) best = s6, tile = 6;
     if (p.c_in % BK == 0) {
@@ -1478,8 +1472,7 @@ static bool glds_sizes_ok(const aivc_conv_params &p) {
 int conv2d_mfma(const aivc_conv_params &p, hipStream_t s) {
   // a batch whose input exceeds the 4 GB the LDS-DMA loader can address goes out as several launches over
   // sub-batches (images are independent; same kernels, same results)
-  if ((p.mode == AIVC_MODE_CONV || (p.mode == AIVC_MODE_TCONV && p.c_in % BK == 0)) && p.n > 1 && !glds_sizes_ok(p) &&
-      !getenv("AIVC_NO_GLDS")) {
+  if ((p.mode == AIVC_MODE_CONV || (p.mode == AIVC_MODE_TCONV && p.c_in % BK == 0)) && p.n > 1 && !glds_sizes_ok(p)) {
     const uint64_t per_image = (uint64_t)p.h_in * p.w_in * p.c_in * 4ull;
     int chunk = (int)(0xFFFFFFF0ull / per_image);
     if (chunk >= 1) {
@@ -1499,11 +1492,7 @@ int conv2d_mfma(const aivc_conv_params &p, hipStream_t s) {
   }
   if (p.tail_c_out) {
     if (!conv2d_mfma_tail_supported(p)) return AIVC_ERR_UNSUPPORTED;
-    if (use_glds(p)) {
-      static const int tail_tile = getenv("AIVC_TAIL_TILE") ? atoi(getenv("AIVC_TAIL_TILE")) : 6;  // tuning aid: 1 = 64x64
-      if (tail_tile == 1) return launch_cfg2<AIVC_MODE_CONV, 2, 2, 1, 1, false, true, true, true>(p, s);
-      return launch_cfg2<AIVC_MODE_CONV, 2, 2, 2, 1, false, true, true, true>(p, s);
-    }
+    if (use_glds(p)) return launch_cfg2<AIVC_MODE_CONV, 2, 2, 2, 1, false, true, true, true>(p, s);
     return launch_cfg2<AIVC_MODE_CONV, 2, 2, 2, 1, false, true, true>(p, s);
   }
   switch (p.mode) {

@@ -432,12 +432,8 @@ static int launch_thin_mfma_l(const aivc_conv_params &p, hipStream_t s) {
     n_cu = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 ? cus : 256;
   }
   const int cus = n_cu.load(std::memory_order_relaxed);
-  // More workgroups than CUs (one fits per CU): a group that shares its CU with a range-coder wave of the entropy side
-  // streams runs slower, and with ONE group per CU walking a fixed share of the tiles the slowest CU set the launch
-  // time; with several rounds of groups the hardware dispatcher evens it out (the B operand is re-gathered per group:
-  // 25 x 64 x c_out floats out of L2).  AIVC_THIN_GRID_MULT: tuning aid.
-  static const int mult = getenv("AIVC_THIN_GRID_MULT") ? atoi(getenv("AIVC_THIN_GRID_MULT")) : 1;
-  int want = cus * (mult > 0 ? mult : 1);
+  // one persistent workgroup per CU (one fits per CU), each walking its share of the tiles
+  int want = cus;
   // AIVC_THIN_GRID_MAX (test aid): few persistent groups on a small input, so that the tile walk (several tiles per
   // group, origins advanced across rows and images) runs at sizes the CPU oracle checks in seconds
   if (const char *gm = getenv("AIVC_THIN_GRID_MAX")) want = atoi(gm) > 0 && atoi(gm) < want ? atoi(gm) : want;
@@ -479,11 +475,11 @@ static int launch_thin(const aivc_conv_params &p, hipStream_t s) {
   return check_launch("thin_tconv");
 }
 
-int conv2d_thin_variant(const aivc_conv_params &p) { return thin_mfma_ok(p) && !getenv("AIVC_THIN_VALU") ? 2 : 1; }
+int conv2d_thin_variant(const aivc_conv_params &p) { return thin_mfma_ok(p) ? 2 : 1; }
 
 int conv2d_thin(const aivc_conv_params &p, hipStream_t s) {
   if (!conv2d_thin_supported(p)) return AIVC_ERR_UNSUPPORTED;
-  if (thin_mfma_ok(p) && !getenv("AIVC_THIN_VALU")) {
+  if (thin_mfma_ok(p)) {
     if (p.ksize == 5) return p.c_out == 3 ? launch_thin_mfma<5, 3>(p, s) : launch_thin_mfma<5, 6>(p, s);
     return p.c_out == 3 ? launch_thin_mfma<3, 3>(p, s) : launch_thin_mfma<3, 6>(p, s);
   }

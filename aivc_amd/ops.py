@@ -128,70 +128,85 @@ def set_precision(mode):
     return prev
 
 
-_SPLIT_WEIGHTS = {}  # id(weight tensor) -> (weak reference, (data_ptr, version), its bf16x3 image); dies with the packed weight
+_DERIVED_WEIGHTS = {}  # (id(weight tensor), transform) -> (weak reference, (data_ptr, version), image); dies with the weight
 
 
-def split_weights_bf16x3(w_ohwi):
-    """aivc_split_weights_bf16x3 of an OHWI weight, once per tensor and version (aivc_conv_params.w_bf16x3).  The codec's
-    side streams launch convolutions too, so the (one-off) split is closed with a device-wide wait like every other
+def _derived_weights(w_ohwi, fn, numel, dtype, *dims):
+    """fn(w_ohwi, *dims, out) into a fresh tensor of numel elements, once per weight tensor and version.  The codec's side
+    streams launch convolutions too, so the (one-off) transform is closed with a device-wide wait like every other
     kernel-ready parameter (layers/_cache.py)."""
     import weakref
-    key = id(w_ohwi)
+    key = (id(w_ohwi), fn)
     stamp = (w_ohwi.data_ptr(), w_ohwi._version)
-    hit = _SPLIT_WEIGHTS.get(key)
+    hit = _DERIVED_WEIGHTS.get(key)
     if hit is not None and hit[0]() is w_ohwi and hit[1] == stamp:
         return hit[2]
-    co = w_ohwi.shape[0]
-    k_total = w_ohwi.numel() // co
-    out = torch.empty(co * k_total * 6, dtype=torch.uint8, device=w_ohwi.device)
+    out = torch.empty(numel, dtype=dtype, device=w_ohwi.device)
     torch.cuda.synchronize(w_ohwi.device)
-    call('aivc_split_weights_bf16x3', _p(w_ohwi), co, k_total, _p(out), _stream())
+    call(fn, _p(w_ohwi), *dims, _p(out), _stream())
     torch.cuda.synchronize(w_ohwi.device)
-    _SPLIT_WEIGHTS[key] = (weakref.ref(w_ohwi, lambda _r, k=key: _SPLIT_WEIGHTS.pop(k, None)), stamp, out)
+    _DERIVED_WEIGHTS[key] = (weakref.ref(w_ohwi, lambda _r, k=key: _DERIVED_WEIGHTS.pop(k, None)), stamp, out)
     return out
 
 
-_WINO_WEIGHTS = {}  # id(weight tensor) -> (weak reference, (data_ptr, version), U)
+def split_weights_bf16x3(w_ohwi):
+    """aivc_split_weights_bf16x3 of an OHWI weight, once per tensor and version (aivc_conv_params.w_bf16x3)"""
+    co = w_ohwi.shape[0]
+    k_total = w_ohwi.numel() // co
+    return _derived_weights(w_ohwi, 'aivc_split_weights_bf16x3', co * k_total * 6, torch.uint8, co, k_total)
 
 
 def winograd_weights(w_ohwi, transposed=False):
     """aivc_winograd_weights of an OHWI 3x3 weight ([co, 3, 3, ci] -> co * 16 * ci floats), aivc_winograd_weights_poly5 of a 5x5
     stride-2 one (4 ci virtual input channels) or, transposed, aivc_winograd_weights_tconv5 (4 co virtual output channels), once per
-    tensor and version (aivc_conv_params.w_wino); closed with a device-wide wait like every other kernel-ready parameter."""
-    import weakref
-    key = (id(w_ohwi), bool(transposed))
-    stamp = (w_ohwi.data_ptr(), w_ohwi._version)
-    hit = _WINO_WEIGHTS.get(key)
-    if hit is not None and hit[0]() is w_ohwi and hit[1] == stamp:
-        return hit[2]
+    tensor and version (aivc_conv_params.w_wino), in the kernels' staging order (AIVC_WINO_U_INDEX)"""
     co, k, _, ci = w_ohwi.shape
     fn = 'aivc_winograd_weights_tconv5' if transposed else ('aivc_winograd_weights_poly5' if k == 5 else 'aivc_winograd_weights')
-    out = torch.empty(co * 16 * ci * (4 if k == 5 else 1), dtype=torch.float32, device=w_ohwi.device)  # (the kernels' staging order, AIVC_WINO_U_INDEX)
-    torch.cuda.synchronize(w_ohwi.device)
-    call(fn, _p(w_ohwi), co, ci, _p(out), _stream())
-    torch.cuda.synchronize(w_ohwi.device)
-    _WINO_WEIGHTS[key] = (weakref.ref(w_ohwi, lambda _r, k_=key: _WINO_WEIGHTS.pop(k_, None)), stamp, out)
-    return out
-
-
-def _winograd_covers(mode, k, stride, pad, c, co, act1, act2, h, w, tail=False):
-    """include/aivc_hip.h: aivc_winograd_covers"""
-    if tail or act1 == 3 or act2 == 3:
-        return False
-    if mode == abi.MODE_TCONV:  # transposed 5x5 stride 2, class by class: the size rule counts INPUT pixels
-        return k == 5 and stride == 2 and c % 32 == 0 and co % 64 == 0 and (h * w >= abi.WINO_MIN_PIXELS_TCONV or WINO_ANY_SIZE)
-    if mode != abi.MODE_CONV or co % 128:
-        return False
-    if k == 3 and stride == 1 and pad == 1 and c % 32 == 0:
-        return h * w >= abi.WINO_MIN_PIXELS or WINO_ANY_SIZE
-    if k == 5 and stride == 2 and pad == 2 and c >= 32 and c & (c - 1) == 0:  # polyphase form: the size rule counts OUTPUT pixels
-        ho, wo = abi.conv_out_size(mode, h, w, k, stride, pad)
-        return ho * wo >= abi.WINO_MIN_PIXELS or WINO_ANY_SIZE
-    return False
+    return _derived_weights(w_ohwi, fn, co * 16 * ci * (4 if k == 5 else 1), torch.float32, co, ci)
 
 
 WINO_ANY_SIZE = False  # tests: fp32w on images below AIVC_WINO_MIN_PIXELS too (aivc_conv_params.flags, AIVC_CONV_WINO_ANY_SIZE)
 PRESPLIT_WEIGHTS = True  # bf16x3 mode: hand the kernels the split weights (False: they split in their K loop; same bits)
+# Winograd codes of aivc_conv2d_variant -> (multiplications per 2 x 2 tile and channel pair, whether the tiles cover the OUTPUT
+# pixel grid rather than the input's)
+_WINO_VARIANTS = {301: (16, False), 302: (49, True), 303: (49, False)}
+
+
+def _profiled(launch, variant, mode, k, stride, c_real, co, n, h, w, ho, wo, fused_gdn=False, co2=0):
+    """launch() of one conv kernel -> what it returned.  While PROFILE is on (bench.py), HIP events on the launch stream
+    bracket it and a launch that succeeded appends (variant, algorithmic FLOPs, e0, e1, shape) to PROFILE."""
+    if PROFILE is None:
+        return launch()
+    pix = n * h * w if mode == abi.MODE_TCONV else n * ho * wo
+    flops = 2.0 * k * k * c_real * co * pix + (2.0 * co * co * n * ho * wo if fused_gdn else 0.0) + 2.0 * co * co2 * n * ho * wo
+    if variant in _WINO_VARIANTS:
+        # version 2 of the contract: what the matrix pipe EXECUTES (3x3: 16 multiplications per tile of 2 x 2 outputs and
+        # channel pair instead of 36; 5x5 stride 2 in polyphase form / transposed by classes: 49 instead of 100, the
+        # transposed form on its grid of input pixels) -- a roofline fraction is priced on issued work; the tap chain's count
+        # is kept beside it
+        mults, on_output = _WINO_VARIANTS[variant]
+        gh, gw = (ho, wo) if on_output else (h, w)
+        PROFILE_DIRECT_EQUIVALENT[0] += flops
+        flops = 2.0 * mults * c_real * co * n * ((gh + 1) // 2) * ((gw + 1) // 2)
+        PROFILE_DIRECT_EQUIVALENT[1] += flops
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    rc = launch()
+    e1.record()
+    if not rc:
+        PROFILE.append((variant, flops, e0, e1, (mode, k, stride, c_real, co, n, h, w, fused_gdn)))
+    return rc
+
+
+def _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, g, tail):
+    """a fused (I)GDN or 1x1 tail the kernels cannot take for this shape: the same arithmetic in two launches"""
+    if tail is not None:
+        t = conv2d(x, w_ohwi, bias, stride=stride, pad=pad, act1=act1, algo=algo)
+        return conv2d(t, tail[0], tail[1], res=res, act2=act2, algo=algo)
+    if act1 or act2 or mul is not None:
+        raise AivcNativeError('conv2d: fused gdn with act/mul epilogue needs a fusable shape')
+    t = conv2d(x, w_ohwi, bias, mode=mode, stride=stride, pad=pad, algo=algo)
+    return gdn(t, g[0], g[1], inverse=g[2], res=res, algo=algo)
 
 
 def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, act2=0, mul=None,
@@ -214,122 +229,60 @@ def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, ac
         if y is not None:
             return y
         x = x.tensor()
-    if tail is not None:
-        return _conv2d_tail(x, w_ohwi, bias, stride, pad, act1, act2, res, algo, tail)
     x = _dev(x, torch.float32, 'x')
     n, h, w_, c = x.shape
-    cmap = getattr(x, '_aivc_cmap', None)
-    c_real = c if cmap is None else len(cmap)  # algorithmic FLOPs count real channels, not zero padding
-    if c % 4:
-        x = pad_channels(x, (c + 3) // 4 * 4)
-        c = x.shape[-1]
-    w_ohwi = _dev(w_ohwi, torch.float32, 'weight')
-    co, k, _, cw = w_ohwi.shape
-    if cw != c:
-        raise AivcNativeError('conv2d: weight packed for %d stored channels, input has %d' % (cw, c))
+    if tail is not None:
+        w_ohwi, w3 = _dev(w_ohwi, torch.float32, 'weight'), _dev(tail[0], torch.float32, 'tail weight')
+        co, k, _, cw = w_ohwi.shape
+        co2 = w3.shape[0]
+        if not (c % 4 == 0 and cw == c and tuple(w3.shape) == (co2, 1, 1, co) and bias is not None and tail[1] is not None):
+            return _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, gdn, tail)
+        c_real, flags = c, 0  # (a tail launch counts stored channels)
+    else:
+        cmap = getattr(x, '_aivc_cmap', None)
+        c_real = c if cmap is None else len(cmap)  # algorithmic FLOPs count real channels, not zero padding
+        if c % 4:
+            x = pad_channels(x, (c + 3) // 4 * 4)
+            c = x.shape[-1]
+        w_ohwi = _dev(w_ohwi, torch.float32, 'weight')
+        co, k, _, cw = w_ohwi.shape
+        co2 = 0
+        if cw != c:
+            raise AivcNativeError('conv2d: weight packed for %d stored channels, input has %d' % (cw, c))
+        # 3-channel images stored as 4: the zero pad channels are exact no-ops the MFMA kernels may skip
+        flags = abi.CONV_SPARSE4 if cmap is not None and all(ci % 4 != 3 for ci in cmap) else 0
+        if WINO_ANY_SIZE:
+            flags |= abi.CONV_WINO_ANY_SIZE
     ho, wo = abi.conv_out_size(mode, h, w_, k, stride, pad)
-    y = torch.empty((n, ho, wo, co), dtype=torch.float32, device=x.device)
+    y = torch.empty((n, ho, wo, co2 or co), dtype=torch.float32, device=x.device)
     bias = _dev(bias, torch.float32, 'bias')
     mul = _dev(mul, torch.float32, 'mul')
     res = _dev(res, torch.float32, 'res')
     for t, nm in ((mul, 'mul'), (res, 'res')):
         if t is not None and tuple(t.shape) != tuple(y.shape):
             raise AivcNativeError('conv2d: %s shape %s != output shape %s' % (nm, tuple(t.shape), tuple(y.shape)))
-    # 3-channel images stored as 4: the zero pad channels are exact no-ops the MFMA kernels may skip
-    flags = abi.CONV_SPARSE4 if cmap is not None and all(ci % 4 != 3 for ci in cmap) else 0
-    if WINO_ANY_SIZE:
-        flags |= abi.CONV_WINO_ANY_SIZE
-    if gdn is not None:
-        g_beta, g_gamma, g_inv = gdn
-        p = abi.ConvParams(mode, k, stride, pad, n, h, w_, c, ho, wo, co, act1, act2, algo, 2 if g_inv else 1, flags,
-                           _p(x), _p(w_ohwi), _p(bias), _p(mul), _p(res), _p(y), _p(g_beta), _p(g_gamma))
-        p.precision = PRECISION
-        from ._lib import load
-        if load()['aivc_conv2d_variant'](C.byref(p)) < 0:  # not fusable for this shape: two launches
-            t = conv2d(x, w_ohwi, bias, mode=mode, stride=stride, pad=pad, algo=algo)
-            return globals()['gdn'](t, g_beta, g_gamma, inverse=g_inv, res=res, algo=algo) if act1 == 0 and \
-                act2 == 0 and mul is None else _unsupported_gdn_epilogue()
-    else:
-        p = abi.ConvParams(mode, k, stride, pad, n, h, w_, c, ho, wo, co, act1, act2, algo, 0, flags,
-                           _p(x), _p(w_ohwi), _p(bias), _p(mul), _p(res), _p(y), None, None)
+    g_beta, g_gamma, gflag = (None, None, 0) if gdn is None else (gdn[0], gdn[1], 2 if gdn[2] else 1)
+    p = abi.ConvParams(mode, k, stride, pad, n, h, w_, c, ho, wo, co, act1, act2, algo, gflag, flags,
+                       _p(x), _p(w_ohwi), _p(bias), _p(mul), _p(res), _p(y), _p(g_beta), _p(g_gamma))
+    if co2:
+        b3 = _dev(tail[1], torch.float32, 'tail bias')
+        p.tail_w, p.tail_bias, p.tail_c_out = _p(w3), _p(b3), co2
     p.precision = PRECISION
-    if PRECISION == abi.PREC_BF16X3 and PRESPLIT_WEIGHTS and w_ohwi.is_contiguous() and (w_ohwi.numel() // co) % 32 == 0:
-        from ._lib import load
-        if load()['aivc_conv2d_variant'](C.byref(p)) >= 1000:  # a launch the mode covers
-            p.w_bf16x3 = _p(split_weights_bf16x3(w_ohwi))
-    if PRECISION == abi.PREC_FP32_WINO and _winograd_covers(mode, k, stride, pad, c, co, act1, act2, h, w_):
-        p.w_wino = _p(winograd_weights(w_ohwi if w_ohwi.is_contiguous() else w_ohwi.contiguous(), transposed=mode == abi.MODE_TCONV))
-    if PROFILE is None:
-        call('aivc_conv2d', C.byref(p), _stream())
-        return y
-    # bench.py instrumentation: HIP events on the launch stream around this one kernel
-    from ._lib import load
+    # which kernel the library will launch (aivc_conv2d_variant): the one place the dispatch rule lives
     variant = load()['aivc_conv2d_variant'](C.byref(p))
-    taps = k * k
-    pix = n * h * w_ if mode == abi.MODE_TCONV else n * ho * wo
-    flops = 2.0 * taps * c_real * co * pix + (2.0 * co * co * n * ho * wo if gdn is not None else 0.0)
-    if variant == 303:  # transposed 5x5 stride 2 by classes: 49 multiplications per 2 x 2 grid pixels (4 x 4 outputs) and channel pair instead of 100
-        PROFILE_DIRECT_EQUIVALENT[0] += flops
-        flops = 2.0 * 49 * c_real * co * n * ((h + 1) // 2) * ((w_ + 1) // 2)
-        PROFILE_DIRECT_EQUIVALENT[1] += flops
-    if variant == 302:  # 5x5 stride 2 in polyphase form: 49 multiplications per 2 x 2 outputs and channel pair instead of 100
-        PROFILE_DIRECT_EQUIVALENT[0] += flops
-        flops = 2.0 * 49 * c_real * co * n * ((ho + 1) // 2) * ((wo + 1) // 2)
-        PROFILE_DIRECT_EQUIVALENT[1] += flops
-    if variant == 301:
-        # version 2 of the contract: what the matrix pipe EXECUTES (16 multiplications per tile of 2 x 2 outputs and channel
-        # pair instead of 36) -- a roofline fraction is priced on issued work; the tap chain's count is kept beside it
-        PROFILE_DIRECT_EQUIVALENT[0] += flops
-        flops = 2.0 * 16 * c_real * co * n * ((h + 1) // 2) * ((w_ + 1) // 2)
-        PROFILE_DIRECT_EQUIVALENT[1] += flops
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    call('aivc_conv2d', C.byref(p), _stream())
-    e1.record()
-    PROFILE.append((variant, flops, e0, e1, (mode, k, stride, c_real, co, n, h, w_, gdn is not None)))
+    if variant < 0 and (gdn is not None or co2):  # no fused kernel for this shape
+        return _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, gdn, tail)
+    w_derived = None  # (referenced until the launch has been issued)
+    if variant in _WINO_VARIANTS:  # version 2 of the contract: the kernel reads the transformed weights
+        w_derived = winograd_weights(w_ohwi, transposed=mode == abi.MODE_TCONV)
+        p.w_wino = _p(w_derived)
+    elif variant >= 1000 and PRESPLIT_WEIGHTS:  # a launch the precision mode covers
+        w_derived = split_weights_bf16x3(w_ohwi)
+        p.w_bf16x3 = _p(w_derived)
+        variant = load()['aivc_conv2d_variant'](C.byref(p))  # (the mode's tile depends on the split weights)
+    _profiled(lambda: call('aivc_conv2d', C.byref(p), _stream()), variant, mode, k, stride, c_real, co, n, h, w_, ho, wo,
+              gdn is not None, co2)
     return y
-
-
-def _conv2d_tail(x, w_ohwi, bias, stride, pad, act1, act2, res, algo, tail):
-    from ._lib import load
-    w3, b3 = tail
-    x = _dev(x, torch.float32, 'x')
-    w_ohwi = _dev(w_ohwi, torch.float32, 'weight')
-    w3 = _dev(w3, torch.float32, 'tail weight')
-    n, h, w_, c = x.shape
-    co, k, _, cw = w_ohwi.shape
-    co2 = w3.shape[0]
-    fused = c % 4 == 0 and cw == c and tuple(w3.shape) == (co2, 1, 1, co) and bias is not None and b3 is not None
-    if fused:
-        ho, wo = abi.conv_out_size(abi.MODE_CONV, h, w_, k, stride, pad)
-        y = torch.empty((n, ho, wo, co2), dtype=torch.float32, device=x.device)
-        bias, b3, res = _dev(bias, torch.float32, 'bias'), _dev(b3, torch.float32, 'tail bias'), _dev(res, torch.float32, 'res')
-        if res is not None and tuple(res.shape) != tuple(y.shape):
-            raise AivcNativeError('conv2d: res shape %s != output shape %s' % (tuple(res.shape), tuple(y.shape)))
-        p = abi.ConvParams(abi.MODE_CONV, k, stride, pad, n, h, w_, c, ho, wo, co, act1, act2, algo, 0, 0,
-                           _p(x), _p(w_ohwi), _p(bias), None, _p(res), _p(y), None, None, _p(w3), _p(b3), co2, 0)
-        p.precision = PRECISION
-        variant = load()['aivc_conv2d_variant'](C.byref(p))
-        fused = variant >= 0
-        if variant >= 1000 and PRESPLIT_WEIGHTS and w_ohwi.is_contiguous():
-            p.w_bf16x3 = _p(split_weights_bf16x3(w_ohwi))
-    if not fused:  # two launches, same arithmetic
-        t = conv2d(x, w_ohwi, bias, stride=stride, pad=pad, act1=act1, algo=algo)
-        return conv2d(t, w3, b3, res=res, act2=act2, algo=algo)
-    if PROFILE is None:
-        call('aivc_conv2d', C.byref(p), _stream())
-        return y
-    flops = 2.0 * (k * k * c * co + co * co2) * n * ho * wo
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    call('aivc_conv2d', C.byref(p), _stream())
-    e1.record()
-    PROFILE.append((variant, flops, e0, e1, (abi.MODE_CONV, k, stride, c, co, n, h, w_, False)))
-    return y
-
-
-def _unsupported_gdn_epilogue():
-    raise AivcNativeError('conv2d: fused gdn with act/mul epilogue needs a fusable shape')
 
 
 def gdn_reparam(beta, gamma, beta_bound, gamma_bound, pedestal):
@@ -386,8 +339,9 @@ def yuv420_to_444(y, u, v, c_store=4, c_off=0, out=None):
     return out
 
 
-_CONV_IMAGES_MAX = int(os.environ.get('AIVC_CONV_IMAGES_MAX', '2'))  # tuning aid: 0 disables aivc_conv_images
-_IMAGES_UNFUSED_GDN = bool(os.environ.get('AIVC_IMAGES_UNFUSED_GDN'))  # tuning aid: the first layer's GDN as a launch of its own
+# three images (K = 300, 113 KB of LDS: one workgroup per CU) measured slower than pack + generic conv (5.2 vs ~4.3 ms at
+# 16 x 1080p), one and two images at par with the conv alone and without the packed tensor
+_CONV_IMAGES_MAX = 2
 
 
 class ImageStack:
@@ -427,16 +381,8 @@ class ImageStack:
 
 def _conv_images(x, w_ohwi, bias, stride, pad, act1, act2, mul, res, algo, gdn):
     """aivc_conv_images on an ImageStack; None when the library declines the layer (caller packs and convolves)"""
-    from ._lib import load
-    if mul is not None or res is not None or act2 or algo != abi.ALGO_AUTO:
+    if mul is not None or res is not None or act2 or algo != abi.ALGO_AUTO or len(x.parts) > _CONV_IMAGES_MAX:
         return None
-    # three images (K = 300, 113 KB of LDS: one workgroup per CU) measured slower than pack + generic conv
-    # (5.2 vs ~4.3 ms at 16 x 1080p), one and two images at par with the conv alone and without the packed tensor
-    if len(x.parts) > _CONV_IMAGES_MAX:
-        return None
-    if gdn is not None and _IMAGES_UNFUSED_GDN:  # tuning aid: first layer without its fused GDN + a GDN-mode launch (bit identical)
-        t = _conv_images(x, w_ohwi, bias, stride, pad, act1, act2, mul, res, algo, None)
-        return None if t is None else globals()['gdn'](t, gdn[0], gdn[1], inverse=gdn[2])
     w_ohwi = _dev(w_ohwi, torch.float32, 'weight')
     co, k, _, cw = w_ohwi.shape
     n, h, w_, c = x.shape
@@ -445,27 +391,16 @@ def _conv_images(x, w_ohwi, bias, stride, pad, act1, act2, mul, res, algo, gdn):
     ho, wo = abi.conv_out_size(abi.MODE_CONV, h, w_, k, stride, pad)
     y = torch.empty((n, ho, wo, co), dtype=torch.float32, device=x.device)
     bias = _dev(bias, torch.float32, 'bias')
-    g_beta = g_gamma = None
-    gflag = 0
-    if gdn is not None:
-        g_beta, g_gamma, gflag = gdn[0], gdn[1], (2 if gdn[2] else 1)
+    g_beta, g_gamma, gflag = (None, None, 0) if gdn is None else (gdn[0], gdn[1], 2 if gdn[2] else 1)
     p = abi.ConvParams(abi.MODE_CONV, k, stride, pad, n, h, w_, c, ho, wo, co, act1, 0, algo, gflag, abi.CONV_SPARSE4,
                        None, _p(w_ohwi), _p(bias), None, None, _p(y), _p(g_beta), _p(g_gamma))
     arr, keep = x.sources()
-    e0 = e1 = None
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = load()['aivc_conv_images'](arr, len(x.parts), C.byref(p), _stream())
+    rc = _profiled(lambda: load()['aivc_conv_images'](arr, len(x.parts), C.byref(p), _stream()), 191, abi.MODE_CONV, k, stride,
+                   len(x._aivc_cmap), co, n, h, w_, ho, wo, gdn is not None)
     if rc == abi.ERR_UNSUPPORTED:
         return None
     if rc != 0:
         raise AivcNativeError('aivc_conv_images failed (%d)' % rc)
-    if PROFILE is not None:
-        e1.record()
-        c_real = len(x._aivc_cmap)
-        flops = 2.0 * k * k * c_real * co * n * ho * wo + (2.0 * co * co * n * ho * wo if gdn is not None else 0.0)
-        PROFILE.append((191, flops, e0, e1, (abi.MODE_CONV, k, stride, c_real, co, n, h, w_, gdn is not None)))
     del keep
     return y
 

@@ -58,6 +58,34 @@ def test_argument_validation_without_gpu():
         abi.MODE_CONV, 3, 1, 1, 1, 270, 480, 128, 270, 480, 128, 0, 0, 0, 0, 0, 1, 1, None, None, None, 1, None, None))) == 105  # 64x128 (round-3 tile rules)
 
 
+def test_conv_dispatch_of_the_default_model_at_1080p():
+    """aivc_conv2d_variant on every conv parameter set of a `bench.py --full` run (default widths, 1920x1080: every
+    dependency level's batch, the fused and the unfused GDN / tail requests, the side measurements' shapes) under fp32,
+    fp32w and bf16x3 (weights split in the K loop, and split ahead): the kernel each launch takes, checked without a GPU.
+    The expected codes are what the library answered before its dispatch became one routing function
+    (tests/golden/conv_variants_1080p.npz; x / w 16-byte aligned, bias always given, as the codec launches them)."""
+    import numpy as np
+    from aivc_amd import _lib, abi
+    fns = _lib.load()
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'conv_variants_1080p.npz'))
+    assert list(g['columns'][16:]) == ['fp32', 'fp32w', 'bf16x3', 'bf16x3_split']
+    rows = g['rows']
+    assert len(rows) == 247
+    a = 1 << 20
+    for r in rows.tolist():
+        mode, k, s, pad, n, h, w, ci, co, act1, act2, gdn, flags, mul, res, tail = r[:16]
+        ho, wo = abi.conv_out_size(mode, h, w, k, s, pad)
+        p = abi.ConvParams(mode, k, s, pad, n, h, w, ci, ho, wo, co, act1, act2, abi.ALGO_AUTO, gdn, flags, a, 2 * a, 3 * a,
+                           4 * a if mul else None, 5 * a if res else None, 6 * a, 7 * a if gdn else None, 8 * a if gdn else None)
+        if tail:
+            p.tail_w, p.tail_bias, p.tail_c_out = 9 * a, 10 * a, tail
+        got = []
+        for prec, split in ((abi.PREC_FP32, False), (abi.PREC_FP32_WINO, False), (abi.PREC_BF16X3, False), (abi.PREC_BF16X3, True)):
+            p.precision, p.w_bf16x3 = prec, 11 * a if split else None
+            got.append(fns['aivc_conv2d_variant'](ctypes.byref(p)))
+        assert got == r[16:], (r[:16], got, r[16:])
+
+
 def test_product_path_refuses_cpu_tensors():
     from aivc_amd import ops
     from aivc_amd._lib import AivcNativeError

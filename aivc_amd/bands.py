@@ -6,14 +6,24 @@ ranks idle under frame sharding (parallel.ClipShard).  Here every rank computes 
 of such a frame and the ranks exchange the few boundary rows the next layer's kernel window reaches into -- layer by
 layer (recomputing halos instead would cost ~5x: the receptive field of one conditional coder is ~550 rows).
 
-Bit-exactness is by construction: every output element of a conv is one fixed-order fmaf chain over its own window
-(include/aivc_hip.h), whatever tensor the window is cut from.  A rank runs the UNCHANGED kernels on a slab = its band
-plus halo rows:
+Bit-exactness is by construction.  In version 1 of the arithmetic contract (include/aivc_hip.h) every output element of a
+conv is one fixed-order fmaf chain over its own window, whatever tensor the window is cut from.  Version 2 (the default,
+Winograd F(2x2, 3x3) chains) computes an output inside a 2 x 2 tile of the tensor it is given, and decides by that
+tensor's size whether a layer takes the Winograd chain at all.  Three things make a slab compute the frame's bits there:
+  * tile grid: a slab starts on the frame's grid (an even row; a multiple of 4 for a stride-2 conv, whose polyphase
+    tiles sit on the output grid), so every valid output of the slab lies in the same tile as in the frame;
+  * zero-coefficient skip: an output row of a tile reads only its own 3-row window of the tile's 4 input rows (terms with
+    a zero coefficient are skipped), so the rows a slab lacks or clamps differently reach discarded outputs only;
+  * routing by frame size: every launch on a slab is told the row count of the map it was cut from, and the library's
+    routing rule is asked on the map's shape (ops.slab_contract): the slab computes in version 2 whatever its size when
+    the map would, in version 1 (what version 2 is outside the layers it covers) when it would not.
+A rank runs the UNCHANGED kernels on a slab = its band plus halo rows:
 
   * replicate padding (src/layers/misc/custom_conv_layers.py:145-153) is the kernel's clamp at the edge of the tensor
     it is given: a slab starts / ends at a true image edge exactly where the band does, and inside the image every row
     a valid output needs is present, so the clamp is only ever hit where the reference pads;
-  * stride-2 convs need the slab's first row on an even frame row (local output j = frame output j + a / 2);
+  * stride-2 convs need the slab's first row on an even frame row (local output j = frame output j + a / 2; the tile
+    grid asks for a multiple of 4);
     transposed convs (:206-223) zero-extend beyond the tensor, which is what the format does at the true edges only --
     inside the image the rows a valid output needs are, again, present;
   * rows of the slab's output that were computed from missing / clamped-too-early rows are NOT valid: a Band records
@@ -223,7 +233,7 @@ class BandCtx:
 
     def slab(self, x, a, b, needs):
         """tensor of rows [a, b) of x: own valid rows copied, the others' fetched (needs: every rank's (lo, hi) --
-        the rows that MUST be right; a .. lo may be unfilled: only discarded outputs read them)"""
+        the rows that MUST be right; a .. lo only reach discarded outputs: held rows or zeros)"""
         sends, recv_rows = self._plan(x, needs, self.bounds(x.k, x.H))
         out = None
         if b > a:
@@ -233,6 +243,8 @@ class BandCtx:
                 out = x.rows(a, b)  # everything this rank reads is held and valid: a view, no copy
             else:
                 out = torch.empty((1, b - a) + tuple(x.t.shape[2:]), dtype=x.t.dtype, device=x.t.device)
+                if lo > a:  # rows above the needed ones (the tile-grid alignment): zeros, never exchanged
+                    out[:, :lo - a].zero_()
                 c0, c1 = max(a, x.v0), min(b, x.v1)
                 if c1 > c0:
                     out[:, c0 - a:c1 - a].copy_(x.rows(c0, c1))
@@ -267,8 +279,11 @@ class BandCtx:
         needs = [need_rows(mode, k, stride, pad, ob[q], ob[q + 1], h_in) for q in range(self.R)]
         o0, o1 = ob[self.r], ob[self.r + 1]
         lo, hi = needs[self.r]
-        # first slab row: on a multiple of the stride (conv), so that local output j is frame output j + a / stride
-        a = (lo // stride) * stride if mode == abi.MODE_CONV else lo
+        # first slab row: on the frame's 2 x 2 tile grid of version 2 of the contract, so that every valid output of the slab
+        # is computed by the frame's own tile -- an even row (3x3 stride 1: output tiles; transposed: tiles of input pixels),
+        # a multiple of 4 for a stride-2 conv (polyphase 5x5: its output origin a / 2 is even; local output j is frame
+        # output j + a / 2).  The same rows serve version 1, whose outputs do not depend on the slab.
+        a = lo - lo % (4 if mode == abi.MODE_CONV and stride == 2 else 2)
         if isinstance(x, BandImages):
             a = (lo // 2) * 2  # 4:2:0 planes: chroma row = luma row / 2
             parts = []

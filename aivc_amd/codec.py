@@ -204,24 +204,28 @@ class FrameCodec:
         band's kernels plus ~70 halo exchanges per frame beat one rank doing the frame alone
         (profiles/r04_band_stats_*.json: per-rank kernel time 8.0 vs 29.0 ms for a 4K B frame on 8 ranks, 5.8 vs 9.0 ms at
         1080p on 4, but 7.7 vs 9.1 ms at 1080p on 2): by default from 4 ranks per group on, or from 2 for frames of >= 6 Mpixel.
-        AIVC_BAND_LEVELS=1 / 0 forces it on / off (every rank must see the same value)."""
+        AIVC_BAND_LEVELS=1 / 0 forces it on / off (every rank must see the same value).  Under version 2 of the contract
+        (the default) bands are opt-in: AIVC_BAND_LEVELS=1 or shard.band_levels = True."""
         if shard is None or shard.R <= 1 or n_frames >= shard.R:
             return False
         # Row bands are bit exact because every output element of version 1 of the contract is one chain over its own window
-        # whatever tensor the window is cut from.  Version 2 (Winograd chains, ops.set_precision('fp32w')) ties an output's
-        # chain to the 2 x 2 tile grid of the tensor it is computed in and to that tensor's size (aivc_winograd_covers): a
-        # slab is another tensor -- never banded there.
-        if ops.PRECISION == abi.PREC_FP32_WINO:
-            return False
+        # whatever tensor the window is cut from.  Version 2 (Winograd chains, ops.set_precision('fp32w')) computes an output
+        # in the 2 x 2 tile of the tensor it is given and decides by that tensor's size (aivc_winograd_covers); bands keep its
+        # bits too (aivc_amd/bands.py): every slab starts on the frame's tile grid, an output row of a tile reads only its own
+        # 3-row window (zero-coefficient terms are skipped), and a slab launch is routed by the size of the map it was cut
+        # from (ops.slab_contract).  Whether bands pay there is unmeasured (Winograd launches on slabs of ~17 latent rows),
+        # so the automatic rule below stays off in that version.
         force = _os.environ.get('AIVC_BAND_LEVELS')
         if force is not None:
             return force not in ('0', '')
+        mode = getattr(shard, 'band_levels', None)
+        if ops.PRECISION == abi.PREC_FP32_WINO:
+            return mode is True
         # shard.band_levels: True / False set by the caller (bench.py turns it on once its warm-up clip came out
         # byte-identical to a single-process encode over the same transport), None = automatic.  The automatic rule
         # applies over gloo / threads, where the byte identity is tested; over RCCL the point-to-point halo exchange on
         # a split sub-group has never run on hardware available to the build (one GPU per lease), so there it stays
         # opt-in until a caller has verified it (tools/rccl_preflight.py --codec, bench.py).
-        mode = getattr(shard, 'band_levels', None)
         if mode is not None:
             return bool(mode)
         if getattr(shard, 'backend', None) == 'nccl':

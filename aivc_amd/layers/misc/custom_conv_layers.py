@@ -53,18 +53,19 @@ def packed_conv(conv, c_store, device, cmap=None):
     return cached(conv, ('w', c_store, str(device), None if cmap is None else tuple(cmap)), params, build)
 
 
-def run_conv(conv, x, pad, act1=abi.ACT_NONE, act2=abi.ACT_NONE, res=None, mul=None, gdn=None, tail=None):
+def run_conv(conv, x, pad, act1=abi.ACT_NONE, act2=abi.ACT_NONE, res=None, mul=None, gdn=None, tail=None, frame_h=None):
     """x NHWC -> NHWC through one aivc_conv2d launch for a torch Conv2d / ConvTranspose2d.
     gdn: optional GDN module applied to the conv output (fused into the epilogue when possible).
     tail: optional 1x1 Conv2d applied to act1(conv(x)) in the same launch when possible; res / act2 then
     belong to the tail.
     x may be a row band of the map (aivc_amd/bands.py: one frame over the ranks of a unit group): the same launch then
-    runs on this rank's slab (band + halo rows fetched from the neighbours) and a band comes back."""
+    runs on this rank's slab (band + halo rows fetched from the neighbours) and a band comes back; every launch on the
+    slab is told the map's row count (frame_h), so that it computes in the contract version the whole map's launch would."""
     if isinstance(x, (bands.Band, bands.BandImages)):
         transposed = isinstance(conv, ConvTranspose2d)
 
         def launch(xs, rs, ms):
-            return run_conv(conv, xs, pad, act1=act1, act2=act2, res=rs, mul=ms, gdn=gdn, tail=tail)
+            return run_conv(conv, xs, pad, act1=act1, act2=act2, res=rs, mul=ms, gdn=gdn, tail=tail, frame_h=x.H)
         return x.ctx.conv(launch, x, abi.MODE_TCONV if transposed else abi.MODE_CONV, _sq(conv.kernel_size),
                           _sq(conv.stride), 0 if transposed else pad,
                           (tail if tail is not None else conv).out_channels, res=res, mul=mul)
@@ -74,21 +75,23 @@ def run_conv(conv, x, pad, act1=abi.ACT_NONE, act2=abi.ACT_NONE, res=None, mul=N
         if gdn is not None or mul is not None or isinstance(conv, ConvTranspose2d) or _sq(tail.kernel_size) != 1:
             raise NotImplementedError('fused tail: a plain Conv2d followed by a 1x1 Conv2d')
         w3, b3 = packed_conv(tail, (conv.out_channels + 3) // 4 * 4, x.device, None)
-        return ops.conv2d(x, w, b, stride=_sq(conv.stride), pad=pad, act1=act1, act2=act2, res=res, tail=(w3, b3))
+        return ops.conv2d(x, w, b, stride=_sq(conv.stride), pad=pad, act1=act1, act2=act2, res=res, tail=(w3, b3), frame_h=frame_h)
     g = None
     if gdn is not None:
         if gdn.beta.shape[0] % 4:  # exotic channel count: padded stand-alone path
-            return gdn.forward_nhwc(run_conv(conv, x, pad), res=res)
+            h = None if frame_h is None else abi.conv_out_size(abi.MODE_TCONV if isinstance(conv, ConvTranspose2d) else abi.MODE_CONV,
+                                                                frame_h, 1, _sq(conv.kernel_size), _sq(conv.stride), pad)[0]
+            return gdn.forward_nhwc(run_conv(conv, x, pad, frame_h=frame_h), res=res, frame_h=h)
         be, ge = gdn.effective_params(x.device)
         g = (be, ge, bool(gdn.inverse))
     if isinstance(conv, ConvTranspose2d):
         k = _sq(conv.kernel_size)
         if _sq(conv.stride) != 2 or _sq(conv.output_padding) != 1 or _sq(conv.padding) != (k + 1) // 2 - 1:
             raise NotImplementedError('only the reference UpscalingLayer geometry is implemented')
-        return ops.conv2d(x, w, b, mode=abi.MODE_TCONV, stride=2, act1=act1, act2=act2, res=res, mul=mul, gdn=g)
+        return ops.conv2d(x, w, b, mode=abi.MODE_TCONV, stride=2, act1=act1, act2=act2, res=res, mul=mul, gdn=g, frame_h=frame_h)
     if _sq(conv.padding) != 0 or _sq(conv.dilation) != 1 or conv.groups != 1:
         raise NotImplementedError('Conv2d with built-in padding/dilation/groups is not used by the codec')
-    return ops.conv2d(x, w, b, stride=_sq(conv.stride), pad=pad, act1=act1, act2=act2, res=res, mul=mul, gdn=g)
+    return ops.conv2d(x, w, b, stride=_sq(conv.stride), pad=pad, act1=act1, act2=act2, res=res, mul=mul, gdn=g, frame_h=frame_h)
 
 
 def _split_nl(seq):

@@ -62,9 +62,9 @@ class GDN(nn.Module):
                                    float(self.pedestal))
         return cached(self, ('gdn', str(device)), (self.beta, self.gamma), build)
 
-    def forward_nhwc(self, x, res=None):
+    def forward_nhwc(self, x, res=None, frame_h=None):
         be, ge = self.effective_params(x.device)
-        return ops.gdn(x, be, ge, inverse=self.inverse, res=res)
+        return ops.gdn(x, be, ge, inverse=self.inverse, res=res, frame_h=frame_h)
 
     def forward(self, inputs):
         if inputs.dim() == 5:  # the reference folds a 5-D tensor to 4-D and back

@@ -198,25 +198,48 @@ def _profiled(launch, variant, mode, k, stride, c_real, co, n, h, w, ho, wo, fus
     return rc
 
 
-def _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, g, tail):
+def _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, g, tail, frame_h):
     """a fused (I)GDN or 1x1 tail the kernels cannot take for this shape: the same arithmetic in two launches"""
     if tail is not None:
-        t = conv2d(x, w_ohwi, bias, stride=stride, pad=pad, act1=act1, algo=algo)
-        return conv2d(t, tail[0], tail[1], res=res, act2=act2, algo=algo)
+        t = conv2d(x, w_ohwi, bias, stride=stride, pad=pad, act1=act1, algo=algo, frame_h=frame_h)
+        return conv2d(t, tail[0], tail[1], res=res, act2=act2, algo=algo,
+                      frame_h=None if frame_h is None else abi.conv_out_size(abi.MODE_CONV, frame_h, 1, w_ohwi.shape[1], stride, pad)[0])
     if act1 or act2 or mul is not None:
         raise AivcNativeError('conv2d: fused gdn with act/mul epilogue needs a fusable shape')
-    t = conv2d(x, w_ohwi, bias, mode=mode, stride=stride, pad=pad, algo=algo)
-    return gdn(t, g[0], g[1], inverse=g[2], res=res, algo=algo)
+    t = conv2d(x, w_ohwi, bias, mode=mode, stride=stride, pad=pad, algo=algo, frame_h=frame_h)
+    return gdn(t, g[0], g[1], inverse=g[2], res=res, algo=algo,
+               frame_h=None if frame_h is None else abi.conv_out_size(mode, frame_h, 1, w_ohwi.shape[1], stride, pad)[0])
+
+
+def slab_contract(p, frame_h):
+    """-> (precision, flags) for the launch p on a row slab (aivc_amd/bands.py) cut from a map of frame_h rows, under
+    version 2 of the contract.  Version 2 decides on the size of the tensor a launch is given (aivc_winograd_covers) and a slab
+    is much smaller than its map, so the library is asked which family the WHOLE map's launch takes (aivc_conv2d_variant on p
+    with the map's rows: the rule still lives in one place) and the slab follows it:
+      * a Winograd code -> version 2 whatever the slab's size (AIVC_CONV_WINO_ANY_SIZE);
+      * no code (a covered layer with a fused gdn, which the map splits into two launches) -> the same, so the slab's
+        launch is split too, and each half decides again;
+      * any other code -> version 1, which is what version 2 computes outside the covered set.
+    Only p's copy is changed; p itself is the caller's to update."""
+    f = abi.ConvParams.from_buffer_copy(p)
+    f.h_in, f.h_out = frame_h, abi.conv_out_size(p.mode, frame_h, p.w_in, p.ksize, p.stride, p.pad)[0]
+    f.precision = abi.PREC_FP32_WINO
+    variant = load()['aivc_conv2d_variant'](C.byref(f))
+    if variant in _WINO_VARIANTS or variant < 0:
+        return abi.PREC_FP32_WINO, p.flags | abi.CONV_WINO_ANY_SIZE
+    return abi.PREC_FP32, p.flags
 
 
 def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, act2=0, mul=None,
-           res=None, algo=abi.ALGO_AUTO, gdn=None, tail=None):
+           res=None, algo=abi.ALGO_AUTO, gdn=None, tail=None, frame_h=None):
     """x [n,h,w,c] -> y [n,ho,wo,co]; semantics of aivc_conv2d (include/aivc_hip.h).
     gdn = (beta_eff, gamma_eff, inverse) fuses the (inverse) GDN into the conv epilogue when the
     kernels can (all channels of a pixel in one tile), else it is issued as a second launch --
     bit-identical either way.
     tail = (w3 [co2,1,1,co], b3): a 1x1 conv applied to act1(conv + bias) in the same launch when the kernels
-    can, else as a second launch (bit-identical); res / act2 then belong to the tail and y is [n,ho,wo,co2]."""
+    can, else as a second launch (bit-identical); res / act2 then belong to the tail and y is [n,ho,wo,co2].
+    frame_h: x is a row slab (n = 1) of a map of frame_h rows (aivc_amd/bands.py); the launch then computes in the
+    version of the contract the whole map's would (slab_contract)."""
     if not isinstance(x, ImageStack) and getattr(x, '_aivc_cmap', None) == (0, 1, 2) and x.dim() == 4 and x.shape[-1] == 4 \
             and mode == abi.MODE_CONV and tail is None:
         st = ImageStack([x], x.shape[1], x.shape[2], x.device)  # a single float image (the prediction fed to g_a_ref)
@@ -236,7 +259,7 @@ def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, ac
         co, k, _, cw = w_ohwi.shape
         co2 = w3.shape[0]
         if not (c % 4 == 0 and cw == c and tuple(w3.shape) == (co2, 1, 1, co) and bias is not None and tail[1] is not None):
-            return _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, gdn, tail)
+            return _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, gdn, tail, frame_h)
         c_real, flags = c, 0  # (a tail launch counts stored channels)
     else:
         cmap = getattr(x, '_aivc_cmap', None)
@@ -268,10 +291,12 @@ def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, ac
         b3 = _dev(tail[1], torch.float32, 'tail bias')
         p.tail_w, p.tail_bias, p.tail_c_out = _p(w3), _p(b3), co2
     p.precision = PRECISION
+    if frame_h is not None and PRECISION == abi.PREC_FP32_WINO:
+        p.precision, p.flags = slab_contract(p, frame_h)
     # which kernel the library will launch (aivc_conv2d_variant): the one place the dispatch rule lives
     variant = load()['aivc_conv2d_variant'](C.byref(p))
     if variant < 0 and (gdn is not None or co2):  # no fused kernel for this shape
-        return _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, gdn, tail)
+        return _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, gdn, tail, frame_h)
     w_derived = None  # (referenced until the launch has been issued)
     if variant in _WINO_VARIANTS:  # version 2 of the contract: the kernel reads the transformed weights
         w_derived = winograd_weights(w_ohwi, transposed=mode == abi.MODE_TCONV)
@@ -304,11 +329,11 @@ def selfcheck_gdn_math(n_div_pairs=1 << 34, seed=1, device=None):
     return tuple(int(v) for v in out.cpu())
 
 
-def gdn(x, beta_eff, gamma_eff, inverse=False, res=None, algo=abi.ALGO_AUTO):
+def gdn(x, beta_eff, gamma_eff, inverse=False, res=None, algo=abi.ALGO_AUTO, frame_h=None):
     c = x.shape[-1]
     mode = abi.MODE_IGDN if inverse else abi.MODE_GDN
     if c % 4 == 0:
-        return conv2d(x, gamma_eff.reshape(c, 1, 1, c), beta_eff, mode=mode, res=res, algo=algo)
+        return conv2d(x, gamma_eff.reshape(c, 1, 1, c), beta_eff, mode=mode, res=res, algo=algo, frame_h=frame_h)
     # channel counts that are not a multiple of 4 (never the case in a real model): run on a zero
     # padded copy (extra channels: x = 0, gamma = 0, beta = 1) and drop the padding
     c4 = (c + 3) // 4 * 4
@@ -317,7 +342,7 @@ def gdn(x, beta_eff, gamma_eff, inverse=False, res=None, algo=abi.ALGO_AUTO):
     b = torch.ones(c4, dtype=torch.float32, device=x.device)
     b[:c] = beta_eff
     y = conv2d(pad_channels(x, c4), g.reshape(c4, 1, 1, c4), b, mode=mode,
-               res=None if res is None else pad_channels(res, c4), algo=algo)
+               res=None if res is None else pad_channels(res, c4), algo=algo, frame_h=frame_h)
     return y[..., :c].contiguous()
 
 

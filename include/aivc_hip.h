@@ -133,9 +133,11 @@ typedef struct aivc_conv_params {
 #define AIVC_PREC_FP32 0
 #define AIVC_PREC_BF16X3 1
 /* AIVC_PREC_FP32_WINO (ABI 16): the fp32 arithmetic contract, version 2.  Identical to AIVC_PREC_FP32 everywhere except
- * for the stride-1 3x3 convolutions with replicate padding 1, c_in % 32 == 0, c_out % 128 == 0 (not the 64-channel 3x3 of the
- * bottleneck blocks, which the kernels fuse with its 1x1 tail: fused or in two launches, it stays version 1), no fused 1x1 tail and at
- * least AIVC_WINO_MIN_PIXELS input pixels per image (aivc_winograd_covers: a function of the layer and its input size only;
+ * for the stride-1 3x3 convolutions with replicate padding 1, c_in % 32 == 0, c_out % 128 == 0 (so not the 64-channel 3x3 of the
+ * default bottleneck blocks, which the kernels fuse with its 1x1 tail) and at least AIVC_WINO_MIN_PIXELS input pixels per image
+ * (aivc_winograd_covers: a function of the layer and its input size only; a fused 1x1 tail does not change the version of its conv,
+ * which is decided on the conv launch without the tail -- the kernels have no fused tail for a covered conv, the library declines
+ * such a request and the caller issues the two launches, the first of them on the chain below;
  * src/layers/misc/custom_conv_layers.py:21-180, src/layers/misc/attention.py:22-97 build their residual blocks from
  * them), whose accumulator is the Winograd F(2x2, 3x3) chain below instead of the 9-tap chain: 16 multiplications per
  * 2x2 output pixels, input channel and output channel instead of 36 (the fp32 matrix pipe is the scarce unit of the
@@ -158,8 +160,8 @@ typedef struct aivc_conv_params {
 #define AIVC_WINO_MIN_PIXELS_TCONV 32768 /* ... of the transposed form (INPUT pixels): a class pass is 16 chunks of 6 positions per wave on
                                          * average, so a block's fixed costs weigh more (68 x 120: x0.93, 272 x 480: x1.2) */
 #define AIVC_CONV_WINO_ANY_SIZE 2 /* aivc_conv_params.flags: version 2 whatever the image size (the tests drive the kernel on shapes the oracle checks in seconds) */
-/* ... and (ABI 17) for the 5x5 STRIDE-2 convolutions with replicate padding 2, c_in = 32 * 2^k, c_out % 128 == 0, no fused 1x1 tail and
- * at least AIVC_WINO_MIN_PIXELS OUTPUT pixels (the second analysis layer of both networks, src/layers/misc/custom_conv_layers.py:129-180:
+/* ... and (ABI 17) for the 5x5 STRIDE-2 convolutions with replicate padding 2, c_in = 32 * 2^k, c_out % 128 == 0 (a fused 1x1 tail: as
+ * above) and at least AIVC_WINO_MIN_PIXELS OUTPUT pixels (the second analysis layer of both networks, src/layers/misc/custom_conv_layers.py:129-180:
  * a quarter of the codec's multiplications), in POLYPHASE form: output pixel (oy, ox) sums, over the four phases (py, px) of the input,
  * a stride-1 3x3 convolution of the phase image  X_ph[y][x] = x[clamp(2 y + py)][clamp(2 x + px)]  (the replicate padding of the ORIGINAL
  * image) with the phase kernel  g_ph[r][l] = w[2 r + py][2 l + px]  (zero where that index would be 5).  Exactly the chain above on a
@@ -174,6 +176,8 @@ typedef struct aivc_conv_params {
  * above with  d[r][c] = x[2 tv - 1 + r][2 tu - 1 + c]  (0 outside the image)  for the tile of grid pixels (2 tv + a, 2 tu + b),
  * U_p[co][ci] = (G g_c G^T)[i][j],  and the positions whose U is zero by construction -- i == 0 for pyc = 1, j == 0 for pxc = 1 -- taking
  * no part in M_p (49 instead of 100 multiplications per 4x4 outputs ...).  U = aivc_winograd_weights_tconv5(w). */
+/* (tail_c_out != 0 -> 0: no Winograd kernel takes a tail, so the router declines the fused request; the version of a tail launch's
+ * conv is that of the same launch without its tail, above) */
 static inline int aivc_winograd_covers(const aivc_conv_params *p) {
   if (p->tail_c_out != 0 || p->act1 == AIVC_ACT_SIGMOID || p->act2 == AIVC_ACT_SIGMOID) return 0;
   if (p->mode == AIVC_MODE_TCONV)

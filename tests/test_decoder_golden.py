@@ -23,10 +23,18 @@ from oracle import spec as ospec
 # LDP_8 from frame 3 on an odd-sized frame, and 1_GOP_8 at 128 x 96 decoded FREE-RUNNING (the second seed tried: the first
 # desynchronised, which the fixture's search log records)
 CASES = ['decoder_ra', 'decoder_ra_chained', 'decoder_ldp_odd', 'decoder_big_gop8', 'decoder_noref_empty_y',
-         'decoder_gain_i', 'decoder_b_gop4', 'decoder_b_ldp8', 'decoder_b_mid_gop8', 'decoder_mid_gop8']
+         'decoder_gain_i', 'decoder_b_gop4', 'decoder_b_ldp8', 'decoder_b_mid_gop8', 'decoder_mid_gop8',
+         'decoder_default_gop2', 'decoder_default_i']
 # decoder_mid_gop8: MID widths (n2 32, n 64, c_y = c_short = c_z = 32, n_h 64: c_in % 32 == 0 on every layer behind the
 # image layers, i.e. the LDS-DMA K loop, fused-GDN / fused-tail tiles and the thin MFMA kernel carry the decode), 1_GOP_8 at
 # 128 x 96, 20 + 6 coded maps, writer's sigma; its 3.2 M parameters are seeded (decoder_variants.seeded_init), not stored
+# decoder_default_*: the DEFAULT widths (aivc_amd.models.arch.DEFAULT_WIDTHS, seeded, 2 + 3 coded maps) at sizes where version 2 of
+# the contract (fp32w) routes launches to the Winograd chains with its size rule in force: 1_GOP_2 at 448 x 320 (I, P, B: 301 on the
+# 3x3 128 -> 128 convs at 1/4 resolution, 302 on g_a_ref's 5x5 stride-2 64 -> 128 layer) and one intra frame at 1024 x 576 (303 on
+# the UpscalingLayer(5, 128 -> 64) at 1/4 resolution, and 301).  Writer's sigma (both desynchronise free-running); q and sigma are
+# stored on the coded maps only (lat_*_maps)
+WINO_LIVE = {'decoder_default_gop2': {301, 302}, 'decoder_default_i': {301, 303}}
+TEACHER_CASES = ['decoder_big_gop8', 'decoder_mid_gop8', 'decoder_default_gop2', 'decoder_default_i']
 NAMES = ('mofnet', 'codecnet')
 
 
@@ -58,9 +66,32 @@ def _model(golden, case='decoder_ra', device=None):
     return model
 
 
-def _ref_sigma(g, idx, name):
-    """sigma the reference wrote frame idx's y section of `name` with, NHWC"""
-    return np.ascontiguousarray(np.transpose(np.asarray(g['lat_%d_%s_sigma' % (idx, name)]), (0, 2, 3, 1)))
+def _lat(g, idx, name, what, fill=1.0):
+    """latent `what` (z, q, sigma) of frame idx's `name`, NCHW as the reference computed it.  Fixtures written with
+    lat_*_maps store q and sigma only on the maps the y section codes: q is 0 on the others, sigma (which the stream does not
+    use there) is set to `fill` (a scalar, or an NCHW array of the full shape to take those maps from)"""
+    a = np.asarray(g['lat_%d_%s_%s' % (idx, name, what)])
+    key = 'lat_%d_%s_maps' % (idx, name)
+    if what == 'z' or key not in g.files:
+        return a
+    maps = np.asarray(g[key])
+    shape = (a.shape[0], _meta(g)['coded_maps_of'], a.shape[2], a.shape[3])  # (coded_maps_of: the model's c_y)
+    full = np.zeros(shape, a.dtype) if what == 'q' else np.broadcast_to(np.asarray(fill, a.dtype), shape).copy()
+    full[:, maps] = a
+    return full
+
+
+def _coded(g, idx, name):
+    """indices of the y maps frame idx's section of `name` codes, or None where the fixture stores every map"""
+    key = 'lat_%d_%s_maps' % (idx, name)
+    return np.asarray(g[key]) if key in g.files else None
+
+
+def _ref_sigma(g, idx, name, own=None):
+    """sigma the reference wrote frame idx's y section of `name` with, NHWC; on maps the fixture does not store (not coded),
+    the decoder's own sigma `own` (NHWC)"""
+    fill = 1.0 if own is None else np.transpose(own, (0, 3, 1, 2))
+    return np.ascontiguousarray(np.transpose(_lat(g, idx, name, 'sigma', fill), (0, 2, 3, 1)))
 
 
 def _pixel_budget(m, frames):
@@ -79,9 +110,7 @@ def _frames(g, m, prefix):
 def _sections_from_latents(g, idx, net_spec, name, md5=False):
     """restated framing of one conditional coder's two sections from the reference's own latents"""
     from oracle import oracle as O
-    z = np.asarray(g['lat_%d_%s_z' % (idx, name)])
-    q = np.asarray(g['lat_%d_%s_q' % (idx, name)])
-    sigma = np.asarray(g['lat_%d_%s_sigma' % (idx, name)])
+    z, q, sigma = (_lat(g, idx, name, what) for what in ('z', 'q', 'sigma'))
     nhwc = lambda a: np.ascontiguousarray(np.transpose(a, (0, 2, 3, 1)))
     table, _ = O.balle_cdf_table(net_spec['balle'])
     sz = ocodec._z_section(table, nhwc(z).astype(np.int16))
@@ -158,7 +187,7 @@ def test_oracle_decode_equals_reference_decoder(case, oracle, golden):
         # streams of this size written on torch's conv arithmetic: the CDFs are built from the writer's sigma, the
         # oracle's own sigma is held against it (oracle/codec.py cond_decode)
         def hook(idx, name, sigma):
-            ref = _ref_sigma(g, idx, name)
+            ref = _ref_sigma(g, idx, name, sigma)
             worst[0] = max(worst[0], float(np.abs(sigma / ref - 1).max()))
             return ref
     dec = ocodec.decode_video(spec, np.asarray(g['video_file']).tobytes(), hook)
@@ -174,7 +203,7 @@ def test_oracle_decode_equals_reference_decoder(case, oracle, golden):
     assert n_off <= _pixel_budget(m, want)
 
 
-@pytest.mark.parametrize('case', [c for c in CASES if c in ('decoder_big_gop8', 'decoder_mid_gop8')])
+@pytest.mark.parametrize('case', TEACHER_CASES)
 def test_free_running_statistic_of_teacher_sigma_cases(case, oracle, golden):
     """The writer's-sigma cases, decoded WITHOUT the writer's sigma: the outcome (desynchronised: how many pixels
     differ, by how much) was recorded by the generator in the model fixture's search log; the deterministic oracle must
@@ -227,18 +256,87 @@ def test_oracle_latents_equal_reference(case, oracle, golden):
             q_z = O.scatter_symbols(sym, npz, net['c_z'], list(range(net['c_z']))).reshape(1, dz[0], dz[1], -1)
             np.testing.assert_array_equal(np.transpose(q_z, (0, 3, 1, 2)), g['lat_%d_%s_z' % (idx, name)])
             mu, sigma = O.hyper_params(O.run_layer(net['h_s'], O.dequantize(q_z)), net['c_y'], dy[0], dy[1])
-            np.testing.assert_allclose(np.transpose(sigma, (0, 3, 1, 2)), g['lat_%d_%s_sigma' % (idx, name)], rtol=2e-6)
+            coded = _coded(g, idx, name)
+            own = np.transpose(sigma, (0, 3, 1, 2))
+            np.testing.assert_allclose(own if coded is None else own[:, coded], g['lat_%d_%s_sigma' % (idx, name)], rtol=2e-6)
             if m.get('teacher_sigma'):
-                sigma = _ref_sigma(g, idx, name)
+                sigma = _ref_sigma(g, idx, name, sigma)
             sy = sec[2 * k + 1]
             maps = list(sy[1:1 + sy[0]])
             q_y = np.zeros((npy, net['c_y']), np.int16)
             if maps:
                 sym = O.range_decode(sy[1 + sy[0]:], O.laplace_cdf_rows(sigma, maps), len(maps) * npy)
                 q_y = O.scatter_symbols(sym, npy, net['c_y'], maps)
+            if coded is not None:
+                assert list(coded) == maps  # the fixture's coded maps are the ones the section lists
             np.testing.assert_array_equal(np.transpose(q_y.reshape(1, dy[0], dy[1], -1), (0, 3, 1, 2)),
-                                          g['lat_%d_%s_q' % (idx, name)])
+                                          _lat(g, idx, name, 'q'))
 
+
+
+def _oracle_conv_launches(monkeypatch):
+    """record the parameters of every oracle.conv2d call (the whole conv family of a decode: oracle.run_layer) as a
+    list of abi.ConvParams with stand-in pointers, shaped as aivc_amd.ops.conv2d issues the same layer (stored channel
+    counts; x, w 16-byte aligned, bias given)"""
+    from aivc_amd import abi
+    from oracle import oracle as O
+    seen, orig = [], O.conv2d
+
+    def rec(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, act2=0, mul=None, res=None, gdn=None,
+            cmap=None, tail=None):
+        n, h, w, c = x.shape
+        c = (max(cmap) + 4) // 4 * 4 if cmap is not None else (c + 3) // 4 * 4
+        co, k = w_ohwi.shape[0], w_ohwi.shape[1]
+        ho, wo = abi.conv_out_size(mode, h, w, k, stride, pad)
+        a = 1 << 20
+        p = abi.ConvParams(mode, k, stride, pad, n, h, w, c, ho, wo, co, act1, act2, abi.ALGO_AUTO,
+                           0 if gdn is None else (2 if gdn[2] else 1), 0, a, 2 * a, 3 * a, 4 * a if mul is not None else None,
+                           5 * a if res is not None else None, 6 * a, 7 * a if gdn is not None else None,
+                           8 * a if gdn is not None else None)
+        if tail is not None:
+            p.tail_w, p.tail_bias, p.tail_c_out = 9 * a, 10 * a, tail[0].shape[0]
+        p.precision = abi.PREC_FP32_WINO
+        seen.append(p)
+        return orig(x, w_ohwi, bias, mode=mode, stride=stride, pad=pad, act1=act1, act2=act2, mul=mul, res=res, gdn=gdn,
+                    cmap=cmap, tail=tail)
+    monkeypatch.setattr(O, 'conv2d', rec)
+    return seen
+
+
+def _variant_codes(launches):
+    """the aivc_conv2d_variant code of each launch; a fused gdn / tail the kernels decline is asked again as the first of
+    the two launches the product issues instead (aivc_amd/ops.py _two_launches)"""
+    import ctypes
+    from aivc_amd import _lib, abi
+    variant = _lib.load()['aivc_conv2d_variant']
+    codes = []
+    for p in launches:
+        v = variant(ctypes.byref(p))
+        if v < 0 and (p.gdn or p.tail_c_out):
+            h = abi.ConvParams.from_buffer_copy(p)
+            h.gdn, h.gdn_beta, h.gdn_gamma = 0, None, None
+            if p.tail_c_out:
+                h.tail_w, h.tail_bias, h.tail_c_out, h.res, h.act2 = None, None, 0, None, 0
+            v = variant(ctypes.byref(h))
+        codes.append(v)
+    return codes
+
+
+@pytest.mark.parametrize('case', sorted(WINO_LIVE))
+def test_winograd_variants_are_live_in_the_default_cases(case, oracle, golden, monkeypatch):
+    """The default-width cases exist to run the decode through version 2's Winograd chains with the size rule in force: the
+    conv launches of the oracle's decode, asked of the library's own routing (aivc_conv2d_variant, no WINO_ANY_SIZE), take
+    exactly the expected Winograd codes.  Raising AIVC_WINO_MIN_PIXELS*, or shrinking a case, fails here, not silently."""
+    g = golden(case)
+    m = _meta(g)
+    assert m['teacher_sigma'] and not oracle.WINO_ANY_SIZE
+    spec = ospec.export_model(_model(golden, case))
+    launches = _oracle_conv_launches(monkeypatch)
+    dec = ocodec.decode_video(spec, np.asarray(g['video_file']).tobytes(), lambda idx, name, sigma: _ref_sigma(g, idx, name, sigma))
+    assert len(dec) == m['n'] and launches
+    codes = _variant_codes(launches)
+    assert all(c >= 0 for c in codes), codes
+    assert set(codes) & {301, 302, 303} == WINO_LIVE[case], sorted(set(codes))
 
 def test_md5_text_format(golden):
     """the product's latent_md5 == the 32 bytes the reference's compute_md5sum put in front of the sections"""
@@ -268,19 +366,21 @@ def _teach_sigma(model, g, m, monkeypatch):
         for i in range(m['n']):
             idx = m['first'] + i
             sy = ocodec.split_lp(np.asarray(g['frame_%d' % idx]).tobytes(), 0, 4)[2 * k + 1]
-            if len(sy) > 1:
-                table[bytes(sy)] = _ref_sigma(g, idx, name)
+            if len(sy) > 1:  # (the writer's sigma, NHWC, on the maps the fixture stores: all, or the coded ones)
+                table[bytes(sy)] = (np.transpose(np.asarray(g['lat_%d_%s_sigma' % (idx, name)]), (0, 2, 3, 1)),
+                                    _coded(g, idx, name))
         assert len(table) == m['n'] - (m['n'] // gop_len if name == 'mofnet' else 0)
         orig = net.ac.decode_y
 
         def patched(payloads, sigma, _orig=orig, _table=table):
             sigma = sigma.clone()
             for j, p in enumerate(payloads):
-                ref = _table.get(bytes(p))
-                if ref is not None:
-                    ref = torch.from_numpy(ref).to(sigma.device)
-                    assert float((sigma[j:j + 1] / ref - 1).abs().max()) < 2e-6
-                    sigma[j:j + 1] = ref
+                entry = _table.get(bytes(p))
+                if entry is not None:
+                    ref = torch.from_numpy(np.ascontiguousarray(entry[0])).to(sigma.device)
+                    maps = slice(None) if entry[1] is None else torch.from_numpy(entry[1].astype(np.int64)).to(sigma.device)
+                    assert float((sigma[j:j + 1, :, :, maps] / ref - 1).abs().max()) < 2e-6
+                    sigma[j:j + 1, :, :, maps] = ref
             return _orig(payloads, sigma)
         monkeypatch.setattr(net.ac, 'decode_y', patched)
 
@@ -308,7 +408,46 @@ def test_hip_decode_video_equals_reference_decoder(case, cuda, golden, monkeypat
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('case', ['decoder_big_gop8', 'decoder_mid_gop8'])
+@pytest.mark.parametrize('case', sorted(WINO_LIVE))
+def test_hip_decode_in_version_2_where_it_is_live(case, cuda, golden, monkeypatch):
+    """The shipped decode path in the default contract (fp32w, size rule in force) on the reference-written default-width
+    streams: the launches take the Winograd kernels the case is sized for (301 / 302 / 303; union over the cases: all three),
+    and the planes still meet the reference within 1 LSB inside the pixel budget, on the writer's track."""
+    from aivc_amd import abi, ops
+    assert ops.PRECISION == abi.PREC_FP32_WINO and not ops.WINO_ANY_SIZE
+    g = golden(case)
+    m = _meta(g)
+    model = _model(golden, case, cuda)
+    _teach_sigma(model, g, m, monkeypatch)
+    fc = model.frame_codec()
+    ops.PROFILE = []
+    try:
+        with torch.no_grad():
+            dec, _, first, last = fc.decode_video(np.asarray(g['video_file']).tobytes(), cuda)
+        torch.cuda.synchronize()
+        codes = [rec[0] for rec in ops.PROFILE]
+    finally:
+        ops.PROFILE = None
+    wino = {c: codes.count(c) for c in sorted(set(codes) & set(ops._WINO_VARIANTS))}
+    print('\n%s: Winograd launches %s of %d conv launches' % (case, wino, len(codes)))
+    assert set(wino) == WINO_LIVE[case]
+    assert (first, last) == (m['first'], m['first'] + m['n'] - 1)
+    want = _frames(g, m, 'dec')
+    n_off = 0
+    for d, w in zip(dec, want):
+        for k in 'yuv':
+            diff = np.abs(d[k][0].cpu().numpy().astype(np.int32) - w[k].astype(np.int32))
+            assert diff.max() <= 1, (case, k)
+            n_off += int((diff != 0).sum())
+    assert n_off <= _pixel_budget(m, want)
+    assert fc.stream_errors() == []
+
+
+def test_default_cases_make_every_winograd_variant_live():
+    assert set().union(*WINO_LIVE.values()) == {301, 302, 303}
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', TEACHER_CASES)
 def test_hip_free_running_desync_is_reported(case, cuda, golden):
     """The reference-written streams of the writer's-sigma cases decoded WITHOUT the writer's sigma: this build's h_s
     differs from torch's in the last bits of sigma, some coded symbol meets a flipped CDF bound and the range decoder
@@ -364,7 +503,7 @@ def test_hip_arithmetic_coder_path_api(case, md5, cuda, golden, tmp_path, capsys
     for i in range(m['n']):
         idx = m['first'] + i
         path = str(tmp_path / str(idx))
-        lat = lambda name, what: torch.from_numpy(np.asarray(g['lat_%d_%s_%s' % (idx, name, what)])).to(cuda)
+        lat = lambda name, what: torch.from_numpy(np.ascontiguousarray(_lat(g, idx, name, what))).to(cuda)
         names = NAMES if gop['frame_%d' % (i % len(gop))]['type'] != 0 else NAMES[1:]
         for name in names:
             common = {'bitstream_path': path, 'flag_debug': True, 'flag_md5sum': md5}

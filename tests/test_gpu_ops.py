@@ -569,9 +569,13 @@ def test_fused_gdn_operand_range_fallback(scale, zero_bias, inv, oracle, cuda):
     (3, 1, 64, 64, 64, 2, 9, 9, abi.ACT_LEAKY, abi.ACT_LEAKY, True),      # not fusable (tail width): two launches
     (3, 1, 8, 12, 24, 2, 9, 9, abi.ACT_LEAKY, abi.ACT_LEAKY, True),       # not fusable (narrow): two launches
     (3, 1, 12, 6, 12, 1, 7, 9, abi.ACT_LEAKY, abi.ACT_LEAKY, True),       # intermediate width not a multiple of 4
+    # an attention block 128 wide (bench.py --widths n=256) at 96 x 96 >= AIVC_WINO_MIN_PIXELS, size rule in force: under fp32w the
+    # 3x3 is covered, the library declines the fused request, the two launches take 301 then the 1x1
+    (3, 1, 128, 128, 256, 1, 96, 96, abi.ACT_LEAKY, abi.ACT_LEAKY, True),
 ])
 def test_fused_tail_bit_exact(case, oracle, cuda):
-    """conv + activation + 1x1 conv (+ residual, activation) in one launch == the oracle's two convolutions"""
+    """conv + activation + 1x1 conv (+ residual, activation) in one launch == the oracle's two convolutions; a tail leaves the
+    contract version of its conv unchanged (the Winograd chain where version 2 covers the conv, else none)"""
     from aivc_amd import ops
     k, s, ci, cm, ct, n, h, w, a1, a2, use_res = case
     rng = np.random.default_rng(abs(hash(case)) % (2 ** 31))
@@ -590,8 +594,49 @@ def test_fused_tail_bit_exact(case, oracle, cuda):
     want = oracle.conv2d(t, w3, b3, res=res, act2=a2)
     if cm4 == cm:  # the oracle's own fused twin
         np.testing.assert_array_equal(oracle.conv2d(x, wt, b1, stride=s, pad=k // 2, act1=a1, act2=a2, res=res, tail=(w3, b3)), want)
-    got = ops.conv2d(T(x, cuda), T(wt, cuda), T(b1, cuda), stride=s, pad=k // 2, act1=a1, act2=a2,
-                     res=None if res is None else T(res, cuda), tail=(T(w3, cuda), T(b3, cuda)))
+    assert not ops.WINO_ANY_SIZE and not oracle.WINO_ANY_SIZE
+    ops.PROFILE = []
+    try:
+        got = ops.conv2d(T(x, cuda), T(wt, cuda), T(b1, cuda), stride=s, pad=k // 2, act1=a1, act2=a2,
+                         res=None if res is None else T(res, cuda), tail=(T(w3, cuda), T(b3, cuda)))
+        torch.cuda.synchronize()
+        codes = [rec[0] for rec in ops.PROFILE]
+    finally:
+        ops.PROFILE = None
+    eq(got, want)
+    covered = ops.PRECISION == abi.PREC_FP32_WINO and k == 3 and s == 1 and ci % 32 == 0 and cm % 128 == 0 and h * w >= 8000
+    if covered:
+        assert len(codes) == 2 and codes[0] == 301 and codes[1] not in ops._WINO_VARIANTS, codes
+    else:
+        assert not set(codes) & set(ops._WINO_VARIANTS), codes
+
+
+def test_attention_res_block_256_bit_exact_in_version_2(oracle, cuda):
+    """AttentionResBlock(256) (what bench.py --widths n=256 builds: a 128-wide bottleneck) at a 1/4-resolution size past
+    AIVC_WINO_MIN_PIXELS, default contract, size rule in force: its 3x3 128 -> 128 with the fused-tail request runs 301 in two
+    launches, and forward_nhwc == the oracle's run_layer on the exported spec, bit for bit"""
+    from aivc_amd import ops
+    from aivc_amd.layers.misc.attention import AttentionResBlock
+    from oracle import spec as ospec
+    assert ops.PRECISION == abi.PREC_FP32_WINO and not ops.WINO_ANY_SIZE and not oracle.WINO_ANY_SIZE
+    torch.manual_seed(256)
+    m = AttentionResBlock(256).eval()
+    with torch.no_grad():
+        for p in m.parameters():
+            p.copy_(torch.randn(p.shape) / (p[0].numel() ** 0.5 if p.dim() > 1 else 10.0))
+    rng = np.random.default_rng(256)
+    x = rng.standard_normal((1, 90, 100, 256), dtype=np.float32)  # 9000 pixels
+    want = oracle.run_layer(ospec.export_spec(m), x)
+    m = m.to(cuda)
+    ops.PROFILE = []
+    try:
+        with torch.no_grad():
+            got = m.forward_nhwc(T(x, cuda))
+        torch.cuda.synchronize()
+        codes = [rec[0] for rec in ops.PROFILE]
+    finally:
+        ops.PROFILE = None
+    assert codes.count(301) == 1 and len(codes) == 3, codes  # 1x1, the 3x3 on the chain, the 1x1 tail
     eq(got, want)
 
 

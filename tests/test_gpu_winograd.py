@@ -223,8 +223,9 @@ def test_wide_reference_fixtures_in_version_2(cuda, golden):
     ChengResBlocks, the attention modules ...) with the covered layers on Winograd chains (size rule lifted: the fixtures are
     small): version 2 meets the bound the version 1 kernels are held to (2e-5 relative to max(1, |y|)); printed side by side"""
     from test_wide_golden import NAMES, _build, _run_gpu
+    from wide_cases import WINO_VARIANTS
     from aivc_amd import ops
-    worst, took = {}, 0
+    worst, took = {}, {}
     for name in NAMES:
         g = golden('wide_' + name)
         m, x, _ = _build(name)
@@ -239,12 +240,12 @@ def test_wide_reference_fixtures_in_version_2(cuda, golden):
                 ops.set_precision(prev)
             errs.append(float((np.abs(y - g['y']) / np.maximum(1.0, np.abs(g['y']))).max()))
             if mode == 'fp32w':
-                took += 1 if 301 in variants else 0
+                took[name] = variants & set(ops._WINO_VARIANTS)
         worst[name] = errs
     print('\nmax relative error vs the reference outputs, version 1 | version 2 (Winograd where covered):')
     for k, (e0, e1) in worst.items():
         print('  %-22s %.2e | %.2e' % (k, e0, e1))
-    assert took >= 3, 'only %d of the wide fixtures took a Winograd launch' % took
+    assert took == {name: WINO_VARIANTS[name] for name in NAMES}, took  # (302 / 303 not reached would fall back silently)
     assert max(e[1] for e in worst.values()) <= 2e-5, worst
 
 

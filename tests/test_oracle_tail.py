@@ -30,6 +30,34 @@ def test_fused_tail_equals_two_convs(case, oracle):
     np.testing.assert_array_equal(fused, two)
 
 
+@pytest.mark.parametrize('mode', ['fp32', 'fp32w'])
+def test_fused_tail_keeps_the_version_of_its_conv(mode, oracle):
+    """A 3x3 128 -> 128 conv at 96 x 96 (>= AIVC_WINO_MIN_PIXELS: version 2 covers it) with a 1x1 tail to 256, size rule
+    in force: the fused launch computes what the two launches compute, in either contract (an attention block 128 wide,
+    bench.py --widths n=256, issues it as two launches on the GPU, the first one on the Winograd chain)."""
+    rng = np.random.default_rng(96)
+    n, h, w, ci, cm, ct = 1, 96, 96, 128, 128, 256
+    x = rng.standard_normal((n, h, w, ci), dtype=np.float32)
+    wt = (rng.standard_normal((cm, 3, 3, ci), dtype=np.float32) / np.sqrt(9 * ci)).astype(np.float32)
+    b1 = rng.standard_normal(cm, dtype=np.float32)
+    w3 = (rng.standard_normal((ct, 1, 1, cm), dtype=np.float32) / np.sqrt(cm)).astype(np.float32)
+    b3 = rng.standard_normal(ct, dtype=np.float32)
+    res = rng.standard_normal((n, h, w, ct), dtype=np.float32)
+    assert h * w >= 8000 and not oracle.WINO_ANY_SIZE
+    prev = oracle.set_precision(mode)
+    try:
+        t = oracle.conv2d(x, wt, b1, pad=1, act1=abi.ACT_LEAKY)
+        two = oracle.conv2d(t, w3, b3, res=res, act2=abi.ACT_LEAKY)
+        fused = oracle.conv2d(x, wt, b1, pad=1, act1=abi.ACT_LEAKY, act2=abi.ACT_LEAKY, res=res, tail=(w3, b3))
+        oracle.set_precision('fp32')
+        t1 = oracle.conv2d(x, wt, b1, pad=1, act1=abi.ACT_LEAKY)
+    finally:
+        oracle.set_precision(prev)
+    np.testing.assert_array_equal(fused, two)
+    # the 3x3 itself is covered under fp32w: its bits differ from version 1's there, and only there
+    assert (mode == 'fp32w') == (not np.array_equal(t, t1))
+
+
 def test_tail_argument_checks(oracle):
     x = np.zeros((1, 4, 4, 4), np.float32)
     w = np.zeros((4, 1, 1, 4), np.float32)

@@ -50,7 +50,18 @@ CASES = [
     ('first_layer_3', 'first_layer', dict(n_img=3), (34, 52), 116, {151}, (6,)),  # (the bench's batches take 156 = tile 6)
 ]
 
+# the Winograd codes (301: 3x3 stride 1, 302: 5x5 stride 2 in polyphase form, 303: transposed 5x5 stride 2) each case's launches take
+# in version 2 of the contract with the size rule lifted (AIVC_CONV_WINO_ANY_SIZE): exactly these, beside `variants` above
+WINO_VARIANTS = {
+    'conv5_64_128_s2_gdn': {302}, 'conv5_128_64_s2_no': set(), 'conv3_64_128_leaky': {301}, 'conv3_128_128_gdn': {301},
+    'up5_128_64_igdn': {303}, 'up5_128_128_igdn': {303}, 'up5_32_128_leaky': {303}, 'up5_64_3_no': set(), 'up5_64_6_no': set(),
+    'cheng128_down': {301}, 'cheng128_up': {301},  # (the 3x3 128 -> 128 behind the strided / transposed 3x3)
+    'attention128_light': set(),  # (the bottleneck's 3x3 is 64 wide)
+    'attention128_full': {301}, 'first_layer_1': set(), 'first_layer_2': set(), 'first_layer_3': set(),
+}
+
 CASE = {c[0]: c for c in CASES}
+assert set(WINO_VARIANTS) == set(CASE)
 
 
 def seeded_arrays(state_dict_shapes, in_shape, seed, build):

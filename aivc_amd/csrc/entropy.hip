@@ -2,9 +2,15 @@
 //
 // CDF build (massively parallel, fp64 transcendentals from aivc_detmath.h):
 //   balle_cdf_table      one thread per (channel, k)          once per model load
-//   laplace_cdf_rows     one thread per 8 CDF points (16 B)   decoder: a 1040-byte uint16 row per
-//                        symbol position, so the serial decoder only does lookups
+//   laplace_cdf_rows     one thread per 8 CDF points (16 B)   a 1040-byte uint16 row per symbol position (tests,
+//                        tools; the decoder reads windows)
+//   laplace_cdf_windows  one wavefront per (64 positions,     decoder: the 64 entries around the centre of every row,
+//                        8 entries)                           so the serial decoder only does lookups
 //   laplace_bounds       one thread per symbol                encoder: the 2 CDF values it needs
+//   table_bounds         one thread per symbol                the same from the z table (pmf mode)
+//   scatter_symbols      one thread per (pixel, 8 channels)   decoder: symbols back into the latent
+//   The last four run per frame BATCH (blockIdx.y = frame) and exist once: a single-frame entry point launches the
+//   same kernel as the one-frame batch, with the map list passed by value instead of read from the device table.
 // Range coder (format-mandated: ONE serial stream per latent section):
 //   one 64-lane wavefront per stream, streams of a batch run concurrently on different CUs.
 //   All coder state is wave-uniform, so it lives in SGPRs / the scalar ALU; the vector lanes are
@@ -107,6 +113,16 @@ __global__ __launch_bounds__(256) void laplace_cdf_rows_kernel(const float *__re
   *reinterpret_cast<uint4 *>(rows + pos * AIVC_CDF_ROW + chunk * 8) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// ---- one kernel per step of the entropy model, launched per frame BATCH -------------------------------------------
+// blockIdx.y = frame f; sigma / q are the batch tensors [n][npix][c]; f's aivc_frame_maps holds its coded map list and
+// the position where its results start in the concatenated stream-order arrays.  FRAMES says where that struct comes
+// from: FrameTable, a device table indexed by blockIdx.y (272 bytes per frame: beyond kernel-argument space for a
+// 64-frame level), or ONE aivc_frame_maps by value, the one-frame batch of the single-frame entry points (which
+// thereby stay stateless: no allocation, no copy, no synchronisation).
+using FrameTable = const aivc_frame_maps *__restrict__;
+__device__ __forceinline__ const aivc_frame_maps &frame_of(FrameTable frames) { return frames[blockIdx.y]; }
+__device__ __forceinline__ const aivc_frame_maps &frame_of(const aivc_frame_maps &fm) { return fm; }
+
 // The decoder's fast path only ever looks at the 64 entries DEC_WIN0 .. DEC_WIN0 + 63 of a row (symbols -32 .. +31);
 // this kernel produces just those (128 B per coded position instead of 1040) plus sigma of the position, from which
 // the decoder's slow path rebuilds the rest of a row on demand with the same function.
@@ -115,22 +131,26 @@ constexpr int CDF_WIN0 = 224, CDF_WIN = 64;
 // is wave-uniform: for the small sigmas of P / B latents the outer chunks of a window lie where the function returns
 // expm1 = -1 exactly (|t| / b > 17.5: cdf 0 or 1, entry k or 65023 + k) for every position of the wavefront, and
 // the fp64 evaluation is skipped for the whole wavefront (one diverging lane used to keep all 64 on the long path).
-__global__ __launch_bounds__(256) void laplace_cdf_windows_kernel(const float *__restrict__ sigma, size_t npix, int c,
-                                                                  aivc_map_list maps, uint16_t *__restrict__ win,
-                                                                  float *__restrict__ sigma_pos) {
+template <class FRAMES>
+__global__ __launch_bounds__(256) void laplace_cdf_windows_batch_kernel(const float *__restrict__ sigma, size_t npix, int c,
+                                                                        const FRAMES frames, uint16_t *__restrict__ win,
+                                                                        float *__restrict__ sigma_pos) {
   constexpr int CHUNKS = CDF_WIN / 8;  // 8 x 16 B per position
+  const aivc_frame_maps &fm = frame_of(frames);
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)maps.n_maps * npix;
+  const size_t total = (size_t)fm.n_maps * npix;
   const size_t wv = gid >> 6;
+  if ((wv / CHUNKS) * 64 >= total) return;  // wave-uniform: the grid is sized for the batch's longest map list
   const int lane = (int)(gid & 63), chunk = (int)(wv % CHUNKS);
   const size_t pos = (wv / CHUNKS) * 64 + (size_t)lane;
   const bool valid = pos < total;
+  const float *sg = sigma + (size_t)blockIdx.y * npix * c;
   float s = 1.0f;
   if (valid) {
     const int m = (int)(pos / npix);
     const size_t pix = pos % npix;
-    s = sigma[pix * c + maps.idx[m]];
-    if (chunk == 0) sigma_pos[pos] = s;
+    s = sg[pix * c + fm.idx[m]];
+    if (chunk == 0) sigma_pos[fm.pos_off + pos] = s;
   }
   const int k0 = CDF_WIN0 + chunk * 8;
   uint32_t w[4];
@@ -139,7 +159,7 @@ __global__ __launch_bounds__(256) void laplace_cdf_windows_kernel(const float *_
   if (chunk != CHUNKS / 2) {  // (the chunk around t = 0 holds both signs)
     const float tmin = chunk < CHUNKS / 2 ? 256.5f - (float)(k0 + 7) : (float)k0 - 256.5f;
     const float b = s / 1.41421354f;  // as in aivc_laplace_cdf
-    sat = tmin / b > 17.5f;           // aivc_expm1f_det(-a) returns -1.0f for -a < -17.5f
+    sat = tmin / b > 17.5f;           // aivc_expm1f_det(-a) returns -1.0f beyond that
   }
   if (__all(sat || !valid)) {
     const uint32_t base = chunk < CHUNKS / 2 ? 0u : 65023u;  // rint(0 * 65023), rint(1 * 65023)
@@ -155,149 +175,36 @@ __global__ __launch_bounds__(256) void laplace_cdf_windows_kernel(const float *_
       w[j] = (uint32_t)aivc_laplace_cdf_u16(k, s) | ((uint32_t)aivc_laplace_cdf_u16(k + 1, s) << 16);
     }
   }
-  if (valid) *reinterpret_cast<uint4 *>(win + pos * CDF_WIN + chunk * 8) = make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-__global__ __launch_bounds__(256) void laplace_bounds_kernel(const float *__restrict__ sigma,
-                                                             const int16_t *__restrict__ q, size_t npix, int c,
-                                                             aivc_map_list maps, uint32_t *__restrict__ bounds) {
-  const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pos >= (size_t)maps.n_maps * npix) return;
-  const int ch = maps.idx[pos / npix];
-  const size_t pix = pos % npix;
-  const float s = sigma[pix * c + ch];
-  // symbols outside the alphabet [0, 512] never reach this kernel through the codec (quantize_center clamps,
-  // the path API raises like torchac's check_input_bounds); the clamp keeps a misuse memory-safe.
-  // Symbol 512 (torchac's max_symbol): upper bound 2^16, packed as 0 (include/aivc_hip.h)
-  const int sym = min(max((int)q[pix * c + ch] + AIVC_AC_MAX_VAL, 0), AIVC_MAX_SYMBOL);
-  const uint32_t lo = aivc_laplace_cdf_u16(sym, s), hi = sym == AIVC_MAX_SYMBOL ? 0u : aivc_laplace_cdf_u16(sym + 1, s);
-  bounds[pos] = lo | (hi << 16);
-}
-
-__global__ __launch_bounds__(256) void table_bounds_kernel(const uint16_t *__restrict__ table,
-                                                           const int16_t *__restrict__ q, size_t npix, int c,
-                                                           uint32_t *__restrict__ bounds) {
-  const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pos >= (size_t)c * npix) return;
-  const int ch = (int)(pos / npix);
-  const size_t pix = pos % npix;
-  const int sym = min(max((int)q[pix * c + ch] + AIVC_AC_MAX_VAL, 0), AIVC_MAX_SYMBOL);
-  const uint16_t *row = table + (size_t)ch * AIVC_CDF_ROW;
-  bounds[pos] = (uint32_t)row[sym] | (sym == AIVC_MAX_SYMBOL ? 0u : (uint32_t)row[sym + 1] << 16);
-}
-
-__global__ __launch_bounds__(256) void table_bounds_batch_kernel(const uint16_t *__restrict__ table, const int16_t *__restrict__ q,
-                                                                 size_t npix, int c, uint32_t *__restrict__ bounds) {
-  const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pos >= (size_t)c * npix) return;
-  const int ch = (int)(pos / npix);
-  const size_t pix = pos % npix;
-  const int sym = min(max((int)q[((size_t)blockIdx.y * npix + pix) * c + ch] + AIVC_AC_MAX_VAL, 0), AIVC_MAX_SYMBOL);
-  const uint16_t *row = table + (size_t)ch * AIVC_CDF_ROW;
-  bounds[(size_t)blockIdx.y * c * npix + pos] = (uint32_t)row[sym] | (sym == AIVC_MAX_SYMBOL ? 0u : (uint32_t)row[sym + 1] << 16);
-}
-
-struct InvMap {
-  int16_t slot[AIVC_MAX_MAPS];  // channel -> position in the coded list, or -1
-};
-// A thread writes 8 consecutive channels (16 bytes) of one pixel; consecutive lanes take consecutive pixels, so every
-// read of a coded map is 128 contiguous bytes per wavefront (one thread per (pixel, channel) with the channel
-// fastest read 64 different maps per load: 36 us for a 1080p latent).
-__global__ __launch_bounds__(256) void scatter_symbols_kernel(const uint16_t *__restrict__ sym, size_t npix, int c,
-                                                              InvMap inv, int16_t *__restrict__ q, int vec) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int groups = (c + 7) / 8;
-  if (gid >= npix * groups) return;
-  const size_t pix = gid % npix;
-  const int ch0 = (int)(gid / npix) * 8;
-  int16_t v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int ch = ch0 + e;
-    const int m = ch < c ? inv.slot[ch] : -1;
-    v[e] = m < 0 ? (int16_t)0 : (int16_t)((int)sym[(size_t)m * npix + pix] - AIVC_AC_MAX_VAL);
-  }
-  int16_t *dst = q + pix * c + ch0;
-  if (vec) {  // c % 8 == 0 and q 16-byte aligned
-    uint4 o;
-    o.x = (uint32_t)(uint16_t)v[0] | ((uint32_t)(uint16_t)v[1] << 16);
-    o.y = (uint32_t)(uint16_t)v[2] | ((uint32_t)(uint16_t)v[3] << 16);
-    o.z = (uint32_t)(uint16_t)v[4] | ((uint32_t)(uint16_t)v[5] << 16);
-    o.w = (uint32_t)(uint16_t)v[6] | ((uint32_t)(uint16_t)v[7] << 16);
-    *reinterpret_cast<uint4 *>(dst) = o;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (ch0 + e < c) dst[e] = v[e];
-  }
-}
-
-// ---- frame-batch variants: blockIdx.y = frame, its map list and stream offset read from a device table ------------
-__global__ __launch_bounds__(256) void laplace_cdf_windows_batch_kernel(const float *__restrict__ sigma, size_t npix, int c,
-                                                                        const aivc_frame_maps *__restrict__ frames,
-                                                                        uint16_t *__restrict__ win, float *__restrict__ sigma_pos) {
-  constexpr int CHUNKS = CDF_WIN / 8;
-  const aivc_frame_maps &fm = frames[blockIdx.y];
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)fm.n_maps * npix;
-  const size_t wv = gid >> 6;
-  if ((wv / CHUNKS) * 64 >= total) return;  // wave-uniform
-  const int lane = (int)(gid & 63), chunk = (int)(wv % CHUNKS);
-  const size_t pos = (wv / CHUNKS) * 64 + (size_t)lane;
-  const bool valid = pos < total;
-  const float *sg = sigma + (size_t)blockIdx.y * npix * c;
-  float s = 1.0f;
-  if (valid) {
-    const int m = (int)(pos / npix);
-    const size_t pix = pos % npix;
-    s = sg[pix * c + fm.idx[m]];
-    if (chunk == 0) sigma_pos[fm.pos_off + pos] = s;
-  }
-  const int k0 = CDF_WIN0 + chunk * 8;
-  uint32_t w[4];
-  bool sat = false;
-  if (chunk != CHUNKS / 2) {
-    const float tmin = chunk < CHUNKS / 2 ? 256.5f - (float)(k0 + 7) : (float)k0 - 256.5f;
-    const float b = s / 1.41421354f;
-    sat = tmin / b > 17.5f;
-  }
-  if (__all(sat || !valid)) {
-    const uint32_t base = chunk < CHUNKS / 2 ? 0u : 65023u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t k = (uint32_t)(k0 + 2 * j);
-      w[j] = ((base + k) & 0xFFFFu) | (((base + k + 1u) & 0xFFFFu) << 16);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = k0 + 2 * j;
-      w[j] = (uint32_t)aivc_laplace_cdf_u16(k, s) | ((uint32_t)aivc_laplace_cdf_u16(k + 1, s) << 16);
-    }
-  }
   if (valid) *reinterpret_cast<uint4 *>(win + (fm.pos_off + pos) * CDF_WIN + chunk * 8) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+template <class FRAMES>
 __global__ __launch_bounds__(256) void laplace_bounds_batch_kernel(const float *__restrict__ sigma, const int16_t *__restrict__ q,
-                                                                   size_t npix, int c, const aivc_frame_maps *__restrict__ frames,
+                                                                   size_t npix, int c, const FRAMES frames,
                                                                    uint32_t *__restrict__ bounds) {
-  const aivc_frame_maps &fm = frames[blockIdx.y];
+  const aivc_frame_maps &fm = frame_of(frames);
   const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pos >= (size_t)fm.n_maps * npix) return;
   const int ch = fm.idx[pos / npix];
   const size_t pix = pos % npix;
   const size_t o = ((size_t)blockIdx.y * npix + pix) * c + ch;
   const float s = sigma[o];
+  // symbols outside the alphabet [0, 512] never reach this kernel through the codec (quantize_center clamps,
+  // the path API raises like torchac's check_input_bounds); the clamp keeps a misuse memory-safe.
+  // Symbol 512 (torchac's max_symbol): upper bound 2^16, packed as 0 (include/aivc_hip.h)
   const int sym = min(max((int)q[o] + AIVC_AC_MAX_VAL, 0), AIVC_MAX_SYMBOL);
   const uint32_t lo = aivc_laplace_cdf_u16(sym, s), hi = sym == AIVC_MAX_SYMBOL ? 0u : aivc_laplace_cdf_u16(sym + 1, s);
   bounds[fm.pos_off + pos] = lo | (hi << 16);
 }
 
+// A thread writes 8 consecutive channels (16 bytes) of one pixel; consecutive lanes take consecutive pixels, so every
+// read of a coded map is 128 contiguous bytes per wavefront (one thread per (pixel, channel) with the channel
+// fastest read 64 different maps per load: 36 us for a 1080p latent).
+template <class FRAMES>
 __global__ __launch_bounds__(256) void scatter_symbols_batch_kernel(const uint16_t *__restrict__ sym, size_t npix, int c,
-                                                                    const aivc_frame_maps *__restrict__ frames,
-                                                                    int16_t *__restrict__ q, int vec) {
+                                                                    const FRAMES frames, int16_t *__restrict__ q, int vec) {
   __shared__ int16_t slot[AIVC_MAX_MAPS];  // channel -> position in the frame's coded list, or -1
-  const aivc_frame_maps &fm = frames[blockIdx.y];
+  const aivc_frame_maps &fm = frame_of(frames);
   for (int i = threadIdx.x; i < AIVC_MAX_MAPS; i += blockDim.x) slot[i] = -1;
   __syncthreads();
   for (int i = threadIdx.x; i < fm.n_maps; i += blockDim.x) slot[fm.idx[i]] = (int16_t)i;
@@ -316,7 +223,7 @@ __global__ __launch_bounds__(256) void scatter_symbols_batch_kernel(const uint16
     v[e] = m < 0 ? (int16_t)0 : (int16_t)((int)fs[(size_t)m * npix + pix] - AIVC_AC_MAX_VAL);
   }
   int16_t *dst = q + ((size_t)blockIdx.y * npix + pix) * c + ch0;
-  if (vec) {
+  if (vec) {  // c % 8 == 0 and q 16-byte aligned
     uint4 o;
     o.x = (uint32_t)(uint16_t)v[0] | ((uint32_t)(uint16_t)v[1] << 16);
     o.y = (uint32_t)(uint16_t)v[2] | ((uint32_t)(uint16_t)v[3] << 16);
@@ -328,6 +235,18 @@ __global__ __launch_bounds__(256) void scatter_symbols_batch_kernel(const uint16
     for (int e = 0; e < 8; ++e)
       if (ch0 + e < c) dst[e] = v[e];
   }
+}
+
+// pmf mode codes every channel of every frame: no map list, so the single-frame entry point is this kernel with n = 1
+__global__ __launch_bounds__(256) void table_bounds_batch_kernel(const uint16_t *__restrict__ table, const int16_t *__restrict__ q,
+                                                                 size_t npix, int c, uint32_t *__restrict__ bounds) {
+  const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pos >= (size_t)c * npix) return;
+  const int ch = (int)(pos / npix);
+  const size_t pix = pos % npix;
+  const int sym = min(max((int)q[((size_t)blockIdx.y * npix + pix) * c + ch] + AIVC_AC_MAX_VAL, 0), AIVC_MAX_SYMBOL);
+  const uint16_t *row = table + (size_t)ch * AIVC_CDF_ROW;
+  bounds[(size_t)blockIdx.y * c * npix + pos] = (uint32_t)row[sym] | (sym == AIVC_MAX_SYMBOL ? 0u : (uint32_t)row[sym + 1] << 16);
 }
 
 // ------------------------------------------------------------------ range encoder
@@ -712,7 +631,7 @@ __device__ __forceinline__ void window_dma(const uint16_t *base, uint32_t voff, 
 // subtractions, one mad + shift, compare + popcount, two readlanes, the interval update, ONE renormalisation test and,
 // when it fires, one merged shift; the loop is unrolled by hand, the window's answer is taken unconditionally and
 // replaced on the rare symbol outside the window.
-// WINDOWED: `rows` holds only the 64-entry window of every position (laplace_cdf_windows_kernel); the slow path evaluates
+// WINDOWED: `rows` holds only the 64-entry window of every position (laplace_cdf_windows_batch_kernel); the slow path evaluates
 // the entries it needs itself from the position's Laplace scale, which the prefetching wave has put beside the windows
 // (`sigma_ring`, LDS).  At high rate a quarter of an I frame's symbols take that path and it is a serial chain of
 // ~100 fp64 / fp32 instructions: aivc_laplace_cdf_u16_scale is the row function laid out without divergent branches.
@@ -1007,6 +926,14 @@ static int check_maps(const aivc_map_list *maps, int c) {
   return AIVC_OK;
 }
 
+// a single frame as the one-frame batch: its (checked) map list, results from element 0 on
+static aivc_frame_maps one_frame(const aivc_map_list *maps) {
+  aivc_frame_maps fm = {};
+  fm.n_maps = maps->n_maps;
+  memcpy(fm.idx, maps->idx, sizeof fm.idx);
+  return fm;
+}
+
 AIVC_EXPORT int aivc_laplace_cdf_rows(const float *sigma, size_t npix, int32_t c, const aivc_map_list *maps,
                                       uint16_t *rows, aivc_stream_t stream) {
   if (!sigma || !rows || c <= 0) return AIVC_ERR_ARG;
@@ -1024,18 +951,14 @@ AIVC_EXPORT int aivc_laplace_bounds(const float *sigma, const int16_t *q, size_t
   if (int rc = check_maps(maps, c)) return rc;
   const size_t total = (size_t)maps->n_maps * npix;
   if (total == 0) return AIVC_OK;
-  hipLaunchKernelGGL(laplace_bounds_kernel, dim3(cdiv(total, 256)), dim3(256), 0, to_stream(stream), sigma, q, npix,
-                     c, *maps, bounds);
+  hipLaunchKernelGGL(laplace_bounds_batch_kernel<aivc_frame_maps>, dim3(cdiv(total, 256)), dim3(256), 0, to_stream(stream),
+                     sigma, q, npix, c, one_frame(maps), bounds);
   return check_launch("laplace_bounds");
 }
 
 AIVC_EXPORT int aivc_table_bounds(const uint16_t *table, const int16_t *q, size_t npix, int32_t c, uint32_t *bounds,
                                   aivc_stream_t stream) {
-  if (!table || !q || !bounds || c <= 0) return AIVC_ERR_ARG;
-  if (npix == 0) return AIVC_OK;
-  hipLaunchKernelGGL(table_bounds_kernel, dim3(cdiv((size_t)c * npix, 256)), dim3(256), 0, to_stream(stream), table,
-                     q, npix, c, bounds);
-  return check_launch("table_bounds");
+  return aivc_table_bounds_batch(table, q, 1, npix, c, bounds, stream);
 }
 
 AIVC_EXPORT int aivc_scatter_symbols(const uint16_t *sym, size_t npix, int32_t c, const aivc_map_list *maps,
@@ -1044,12 +967,9 @@ AIVC_EXPORT int aivc_scatter_symbols(const uint16_t *sym, size_t npix, int32_t c
   if (int rc = check_maps(maps, c)) return rc;
   if (maps->n_maps > 0 && !sym) return AIVC_ERR_ARG;
   if (npix == 0) return AIVC_OK;
-  InvMap inv;
-  for (int i = 0; i < AIVC_MAX_MAPS; ++i) inv.slot[i] = -1;
-  for (int i = 0; i < maps->n_maps; ++i) inv.slot[maps->idx[i]] = (int16_t)i;
   const int vec = (c & 7) == 0 && ((uintptr_t)q & 15) == 0;
-  hipLaunchKernelGGL(scatter_symbols_kernel, dim3(cdiv(npix * ((c + 7) / 8), 256)), dim3(256), 0, to_stream(stream), sym, npix,
-                     c, inv, q, vec);
+  hipLaunchKernelGGL(scatter_symbols_batch_kernel<aivc_frame_maps>, dim3(cdiv(npix * ((c + 7) / 8), 256)), dim3(256), 0,
+                     to_stream(stream), sym, npix, c, one_frame(maps), q, vec);
   return check_launch("scatter_symbols");
 }
 
@@ -1061,7 +981,7 @@ AIVC_EXPORT int aivc_laplace_cdf_windows_batch(const float *sigma, int32_t n, si
   const size_t n_pos = (size_t)max_maps * npix;
   if (n_pos == 0) return AIVC_OK;
   const size_t total = ((n_pos + 63) / 64) * (CDF_WIN / 8) * 64;
-  hipLaunchKernelGGL(laplace_cdf_windows_batch_kernel, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream),
+  hipLaunchKernelGGL(laplace_cdf_windows_batch_kernel<FrameTable>, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream),
                      sigma, npix, c, frames, win, sigma_pos);
   return check_launch("laplace_cdf_windows_batch");
 }
@@ -1073,7 +993,7 @@ AIVC_EXPORT int aivc_laplace_bounds_batch(const float *sigma, const int16_t *q, 
     return AIVC_ERR_ARG;
   const size_t total = (size_t)max_maps * npix;
   if (total == 0) return AIVC_OK;
-  hipLaunchKernelGGL(laplace_bounds_batch_kernel, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream), sigma, q,
+  hipLaunchKernelGGL(laplace_bounds_batch_kernel<FrameTable>, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream), sigma, q,
                      npix, c, frames, bounds);
   return check_launch("laplace_bounds_batch");
 }
@@ -1092,7 +1012,7 @@ AIVC_EXPORT int aivc_scatter_symbols_batch(const uint16_t *sym, int32_t n, size_
   if (!q || !frames || !sym || c <= 0 || c > AIVC_MAX_MAPS || n <= 0 || n > 65535) return AIVC_ERR_ARG;
   if (npix == 0) return AIVC_OK;
   const int vec = (c & 7) == 0 && ((uintptr_t)q & 15) == 0;
-  hipLaunchKernelGGL(scatter_symbols_batch_kernel, dim3(cdiv(npix * ((c + 7) / 8), 256), (unsigned)n), dim3(256), 0,
+  hipLaunchKernelGGL(scatter_symbols_batch_kernel<FrameTable>, dim3(cdiv(npix * ((c + 7) / 8), 256), (unsigned)n), dim3(256), 0,
                      to_stream(stream), sym, npix, c, frames, q, vec);
   return check_launch("scatter_symbols_batch");
 }
@@ -1145,8 +1065,8 @@ AIVC_EXPORT int aivc_laplace_cdf_windows(const float *sigma, size_t npix, int32_
   const size_t n_pos = (size_t)maps->n_maps * npix;
   if (n_pos == 0) return AIVC_OK;
   const size_t total = ((n_pos + 63) / 64) * (CDF_WIN / 8) * 64;  // a wavefront per (64 positions, chunk)
-  hipLaunchKernelGGL(laplace_cdf_windows_kernel, dim3(cdiv(total, 256)), dim3(256), 0, to_stream(stream), sigma, npix, c,
-                     *maps, win, sigma_pos);
+  hipLaunchKernelGGL(laplace_cdf_windows_batch_kernel<aivc_frame_maps>, dim3(cdiv(total, 256)), dim3(256), 0, to_stream(stream),
+                     sigma, npix, c, one_frame(maps), win, sigma_pos);
   return check_launch("laplace_cdf_windows");
 }
 

@@ -685,6 +685,9 @@ def scatter_symbols_batch(sym, maps_list, n, npix, c, table=None):
 
 
 def laplace_bounds(sigma, q, maps):
+    """sigma / q [1,h,w,c] (one image) -> bounds int32 [len(maps) * npix]: aivc_laplace_bounds, the one-frame case of the
+    batch kernel with the map list passed by value.  Nothing under aivc_amd/ calls it (the codec goes through
+    laplace_bounds_batch); the tests, the oracle comparisons and tools/bench_rangecoder.py do."""
     sigma, q = _dev(sigma, torch.float32, 'sigma'), _dev(q, torch.int16, 'q')
     c = sigma.shape[-1]
     npix = sigma.numel() // c
@@ -695,6 +698,9 @@ def laplace_bounds(sigma, q, maps):
 
 
 def table_bounds(table, q):
+    """q [1,h,w,c] (one image) -> bounds int32 [c * npix]: aivc_table_bounds = aivc_table_bounds_batch with n = 1.
+    Nothing under aivc_amd/ calls it (the codec goes through table_bounds_batch); the tests, the oracle comparisons and
+    tools/bench_rangecoder.py do."""
     q = _dev(q, torch.int16, 'q')
     c = q.shape[-1]
     npix = q.numel() // c

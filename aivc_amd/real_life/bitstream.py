@@ -11,6 +11,7 @@ never materialised -- the encoder evaluates the 2 CDF points a symbol needs, the
 the rare symbol outside), z uses a [C_z,514] table built once; there is no device->host copy of CDFs and no
 temp file.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -24,14 +25,12 @@ SECTION_NAMES = ('mofnet_z', 'mofnet_y', 'codecnet_z', 'codecnet_y')
 
 
 class PendingSection:
-    """A latent of ONE frame whose symbols are known on the device but not yet range-coded.
-    q / sigma are [1,h,w,c] views; `flags` is that frame's row of a batched non-zero-map tensor."""
+    """A latent of ONE frame whose symbols are known on the device but not yet range-coded.  `batch` = (q [n,h,w,c] of the
+    frame batch it was cut from, its sigma or None, the frame's index in it): the sections of one batch get their CDF bounds
+    from ONE launch (aivc_laplace_bounds_batch / aivc_table_bounds_batch); `flags` is the frame's row of its flag tensor."""
 
-    def __init__(self, mode, q, sigma=None, table=None, flags=None, md5=b'', batch=None):
-        self.mode, self.q, self.sigma, self.table, self.flags, self.md5 = mode, q, sigma, table, flags, md5
-        # (q of the whole frame batch, its sigma or None, this frame's index in it): sections of one batch get their CDF
-        # bounds from ONE launch (aivc_laplace_bounds_batch / aivc_table_bounds_batch) instead of one per frame
-        self.batch = batch
+    def __init__(self, mode, batch, table=None, flags=None, md5=b''):
+        self.mode, self.batch, self.table, self.flags, self.md5 = mode, batch, table, flags, md5
 
 
 _MD5_LINES = None
@@ -111,6 +110,17 @@ def _unpin(t):
 ESTIMATE_RATE = False
 
 
+@contextlib.contextmanager
+def estimating_rate(on=True):
+    """ESTIMATE_RATE = `on` inside the block, its previous value after it, also when the block raises"""
+    global ESTIMATE_RATE
+    keep, ESTIMATE_RATE = ESTIMATE_RATE, on
+    try:
+        yield
+    finally:
+        ESTIMATE_RATE = keep
+
+
 class EntropyJob:
     """Range-encode launches of a set of frames, possibly still running on a side stream."""
 
@@ -178,6 +188,15 @@ def prepare_finalize(frames_sections):
     return PreparedFlags(lap, flags_h, event)
 
 
+def _by_batch(sections):
+    """[(frame, section index, PendingSection, ...)] -> grouped by the frame batch the sections were cut from (a dependency
+    level's latents): batches in order of first appearance, the members of a batch by frame index in it"""
+    groups = {}
+    for member in sections:
+        groups.setdefault(id(member[2].batch[0]), []).append(member)
+    return [sorted(members, key=lambda m: m[2].batch[2]) for members in groups.values()]
+
+
 def launch_finalize(frames_sections, side_stream=None, prepared=None, fork_streams=None):
     """frames_sections: list (one entry per frame) of 4-lists of PendingSection / None.
     One host wait for all non-zero-map flags (C bytes per latent), then the CDF-bound kernels and ONE
@@ -200,49 +219,29 @@ def launch_finalize(frames_sections, side_stream=None, prepared=None, fork_strea
         side_stream.wait_event(prepared.event)  # the latents of THESE frames, not whatever was issued since
         ctx.__enter__()
     try:
-        jobs, bounds = [], []
-        # y sections: one bounds launch per frame BATCH the sections were cut from (a dependency level's latents)
-        groups = {}
+        # jobs / bounds in ops.range_encode's stream order, the byte layout collect() reads back: the y batches, then the z
+        # batches.  y sections: one bounds launch per frame batch; a frame with no coded map has a head but no stream
+        jobs, bounds, y = [], [], []
         for j, (fi, si, s) in enumerate(lap):
             maps = [int(c) for c in np.nonzero(flags_h[j])[0]]
             heads[fi][si] = s.md5 + bytes([len(maps)]) + bytes(maps)
-            key = id(s.batch[0]) if s.batch is not None else ('single', j)
-            groups.setdefault(key, []).append((fi, si, s, maps))
-        for members in groups.values():
-            s0 = members[0][2]
-            if s0.batch is None:
-                fi, si, s, maps = members[0]
-                if maps:
-                    jobs.append((fi, si))
-                    bounds.append(ops.laplace_bounds(s.sigma, s.q, maps))
-                continue
-            q_b, sigma_b, _ = s0.batch
-            per_frame = [[] for _ in range(q_b.shape[0])]
-            for fi, si, s, maps in members:
-                per_frame[s.batch[2]] = maps
+            y.append((fi, si, s, maps))
+        for members in _by_batch(y):
+            q_b, sigma_b, _ = members[0][2].batch
+            coded = {s.batch[2]: maps for _, _, s, maps in members}  # (frames of the batch that are not in this set: none)
             npix = q_b.shape[1] * q_b.shape[2]
-            allb, offs = ops.laplace_bounds_batch(sigma_b, q_b, per_frame)
-            for fi, si, s, maps in sorted(members, key=lambda m: m[2].batch[2]):
+            allb, offs = ops.laplace_bounds_batch(sigma_b, q_b, [coded.get(f, []) for f in range(q_b.shape[0])])
+            for fi, si, s, maps in members:
                 if maps:
                     jobs.append((fi, si))
                     bounds.append(allb[offs[s.batch[2]]:offs[s.batch[2]] + len(maps) * npix])
         # z sections likewise (every channel of every frame)
-        zgroups = {}
-        for fi, secs in enumerate(frames_sections):
-            for si, s in enumerate(secs):
-                if s is not None and s.mode == 'pmf':
-                    heads[fi][si] = s.md5
-                    key = id(s.batch[0]) if s.batch is not None else ('single', fi, si)
-                    zgroups.setdefault(key, []).append((fi, si, s))
-        for members in zgroups.values():
-            s0 = members[0][2]
-            if s0.batch is None:
-                for fi, si, s in members:
-                    jobs.append((fi, si))
-                    bounds.append(ops.table_bounds(s.table, s.q))
-                continue
-            zb = ops.table_bounds_batch(s0.table, s0.batch[0])
-            for fi, si, s in sorted(members, key=lambda m: m[2].batch[2]):
+        pmf = [(fi, si, s) for fi, secs in enumerate(frames_sections) for si, s in enumerate(secs)
+               if s is not None and s.mode == 'pmf']
+        for members in _by_batch(pmf):
+            zb = ops.table_bounds_batch(members[0][2].table, members[0][2].batch[0])
+            for fi, si, s in members:
+                heads[fi][si] = s.md5
                 jobs.append((fi, si))
                 bounds.append(zb[s.batch[2]])
         out_h = lens_h = offs = event = est_h = None
@@ -309,13 +308,12 @@ class ArithmeticCoder():
     def pend_z(self, q_z):
         """q_z [n,h,w,c] -> list of n PendingSection"""
         table = self.z_table(q_z.device)
-        return [PendingSection('pmf', q_z[i:i + 1], table=table, md5=self._md5(q_z[i:i + 1]), batch=(q_z, None, i))
+        return [PendingSection('pmf', (q_z, None, i), table=table, md5=self._md5(q_z[i:i + 1]))
                 for i in range(q_z.shape[0])]
 
     def pend_y(self, q_y, sigma):
         flags = ops.nonzero_flags(q_y)  # async, no sync here
-        return [PendingSection('laplace', q_y[i:i + 1], sigma=sigma[i:i + 1], flags=flags[i], md5=self._md5(q_y[i:i + 1]),
-                               batch=(q_y, sigma, i))
+        return [PendingSection('laplace', (q_y, sigma, i), flags=flags[i], md5=self._md5(q_y[i:i + 1]))
                 for i in range(q_y.shape[0])]
 
     def _md5(self, q):

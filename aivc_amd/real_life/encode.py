@@ -57,10 +57,9 @@ def encode(param):
     fc = FrameCodec(model)
     from . import bitstream
     from .. import parallel
-    keep_flag, bitstream.ESTIMATE_RATE = bitstream.ESTIMATE_RATE, True  # the reference's in-band rate check (RESULT lines)
     fc.estimated_bits, fc.coded_payload_bytes = 0.0, 0
     rank, world = parallel.rank_world()
-    with torch.no_grad():
+    with torch.no_grad(), bitstream.estimating_rate():  # the reference's in-band rate check (RESULT lines)
         if world > 1:  # one process per GPU: intra-period units over the ranks, the container on rank 0
             blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=get_value('idx_rate', param, default),
                                                       return_enc=True)
@@ -68,8 +67,7 @@ def encode(param):
             enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last,
                                   idx_rate=get_value('idx_rate', param, default))
             blob = fc.assemble_video(enc)
-    torch.cuda.synchronize()
-    bitstream.ESTIMATE_RATE = keep_flag
+        torch.cuda.synchronize()
     dt = time.time() - t0
     n = last - first + 1
     est_bits, payload = fc.estimated_bits, float(fc.coded_payload_bytes)

@@ -476,8 +476,10 @@ int aivc_scatter_symbols(const uint16_t *sym, size_t npix, int32_t c, const aivc
 /* ---- one launch per frame BATCH for the CDF-bound / scatter kernels (the frames of a dependency level) ----------
  * Per frame f of the batch: which y maps are coded (as aivc_map_list) and where its coded positions start in the
  * concatenated stream-order arrays.  The table lives in DEVICE memory (272 bytes per frame: beyond kernel-argument
- * space for a 64-frame level); sigma / q are the batch tensors [n][npix][c].  Frame f's results are bit-identical to
- * the single-frame call with its map list, written / read at element offset pos_off. */
+ * space for a 64-frame level); sigma / q are the batch tensors [n][npix][c]; frame f's results are written / read at
+ * element offset pos_off.  The single-frame calls above (aivc_laplace_cdf_windows, aivc_laplace_bounds, aivc_table_bounds,
+ * aivc_scatter_symbols) are by construction the one-frame case of these kernels: the same code, launched with n = 1,
+ * pos_off = 0 and the frame's aivc_frame_maps passed as a kernel argument instead of read from the table. */
 typedef struct aivc_frame_maps {
   uint64_t pos_off; /* first coded position (symbol) of frame f in bounds / win / sigma_pos / sym */
   int32_t n_maps;

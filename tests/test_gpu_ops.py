@@ -767,43 +767,54 @@ def test_pack_images_bit_exact(h, w, cuda, oracle):
 
 def test_frame_batch_entropy_kernels_equal_per_frame_calls(oracle, cuda):
     """aivc_laplace_cdf_windows_batch / laplace_bounds_batch / table_bounds_batch / scatter_symbols_batch (one launch per
-    frame batch, per-frame map lists in a device table) == the single-frame entry points frame by frame, incl. frames
-    with no coded map, and == the oracle's twins"""
+    frame batch, per-frame map lists in a device table) == the oracle's own implementation of every step, frame by frame
+    (the independent check: the single-frame entry points are the one-frame case of the same kernels), and == the
+    single-frame entry points (the map list passed by value against the one read from the table), incl. frames with no
+    coded map.  Second shape: c % 8 != 0 (the scatter's scalar tail), a frame with every map coded next to frames with
+    fewer (grid sized for the longest list) and one with none.  Exact equality throughout."""
     from aivc_amd import ops
     rng = np.random.default_rng(21)
-    n, h, w, c = 5, 7, 9, 16
-    npix = h * w
-    sig = (np.abs(rng.standard_normal((n, h, w, c))) * 2 + 0.05).astype(np.float32)
-    q = np.clip(np.rint(rng.standard_normal((n, h, w, c)) * sig), -256, 256).astype(np.int16)
-    maps = [[0, 3, 15], [], [1], list(range(c)), [2, 14]]
-    sd, qd = T(sig, cuda), T(q, cuda)
-    # bounds
-    allb, offs = ops.laplace_bounds_batch(sd, qd, maps)
-    for f, m in enumerate(maps):
-        if m:
-            eq(allb[offs[f]:offs[f] + len(m) * npix], ops.laplace_bounds(sd[f:f + 1], qd[f:f + 1], m))
-            np.testing.assert_array_equal(allb[offs[f]:offs[f] + len(m) * npix].cpu().numpy().view(np.uint32),
-                                          oracle.laplace_bounds(sig[f:f + 1], q[f:f + 1], m))
-    # windows + sigma per position
-    total = sum(len(m) for m in maps) * npix
-    win = torch.zeros((total, abi.CDF_WIN), dtype=torch.int16, device=cuda)
-    sp = torch.zeros(total, dtype=torch.float32, device=cuda)
-    offs2, tab = ops.laplace_cdf_windows_batch(sd, maps, (win, sp))
-    assert offs2 == offs
-    for f, m in enumerate(maps):
-        if m:
-            w1, s1 = ops.laplace_cdf_windows(sd[f:f + 1], m)
-            eq(win[offs[f]:offs[f] + len(m) * npix], w1)
-            eq(sp[offs[f]:offs[f] + len(m) * npix], s1)
-    # pmf bounds of every channel
-    table = T(rng.integers(0, 65535, (c, abi.CDF_ROW)).astype(np.uint16).view(np.int16), cuda)
-    zb = ops.table_bounds_batch(table, qd)
-    for f in range(n):
-        eq(zb[f], ops.table_bounds(table, qd[f:f + 1]))
-    # scatter: symbols in stream order -> [n, npix, c]
-    sym = torch.cat([(qd[f].reshape(npix, c)[:, m].T.reshape(-1).to(torch.int32) + 256).to(torch.int16) for f, m in enumerate(maps) if m])
-    back = ops.scatter_symbols_batch(sym, maps, n, npix, c, table=tab).view(n, h, w, c)
-    want = np.zeros_like(q)
-    for f, m in enumerate(maps):
-        want[f][..., m] = q[f][..., m]
-    eq(back, want)
+    for (n, h, w, c), maps in (((5, 7, 9, 16), [[0, 3, 15], [], [1], list(range(16)), [2, 14]]),
+                               ((4, 5, 6, 12), [list(range(12)), [], [0, 11], [5]])):
+        npix = h * w
+        sig = (np.abs(rng.standard_normal((n, h, w, c))) * 2 + 0.05).astype(np.float32)
+        q = np.clip(np.rint(rng.standard_normal((n, h, w, c)) * sig), -256, 256).astype(np.int16)
+        sd, qd = T(sig, cuda), T(q, cuda)
+        # bounds
+        allb, offs = ops.laplace_bounds_batch(sd, qd, maps)
+        for f, m in enumerate(maps):
+            if m:
+                eq(allb[offs[f]:offs[f] + len(m) * npix], ops.laplace_bounds(sd[f:f + 1], qd[f:f + 1], m))
+                np.testing.assert_array_equal(allb[offs[f]:offs[f] + len(m) * npix].cpu().numpy().view(np.uint32),
+                                              oracle.laplace_bounds(sig[f:f + 1], q[f:f + 1], m))
+        # windows + sigma per position
+        total = sum(len(m) for m in maps) * npix
+        win = torch.zeros((total, abi.CDF_WIN), dtype=torch.int16, device=cuda)
+        sp = torch.zeros(total, dtype=torch.float32, device=cuda)
+        offs2, tab = ops.laplace_cdf_windows_batch(sd, maps, (win, sp))
+        assert offs2 == offs
+        for f, m in enumerate(maps):
+            if m:
+                w1, s1 = ops.laplace_cdf_windows(sd[f:f + 1], m)
+                eq(win[offs[f]:offs[f] + len(m) * npix], w1)
+                eq(sp[offs[f]:offs[f] + len(m) * npix], s1)
+                w_o, s_o = oracle.laplace_cdf_windows(sig[f:f + 1], m)
+                eq(win[offs[f]:offs[f] + len(m) * npix], w_o)
+                eq(sp[offs[f]:offs[f] + len(m) * npix], s_o)
+        # pmf bounds of every channel
+        table = rng.integers(0, 65535, (c, abi.CDF_ROW)).astype(np.uint16)
+        table_d = T(table.view(np.int16), cuda)
+        zb = ops.table_bounds_batch(table_d, qd)
+        for f in range(n):
+            eq(zb[f], ops.table_bounds(table_d, qd[f:f + 1]))
+            eq(zb[f], oracle.table_bounds(table, q[f:f + 1]))
+        # scatter: symbols in stream order -> [n, npix, c]
+        per_frame = [(qd[f].reshape(npix, c)[:, m].T.reshape(-1).to(torch.int32) + 256).to(torch.int16) if m else None
+                     for f, m in enumerate(maps)]
+        sym = torch.cat([s for s in per_frame if s is not None])
+        back = ops.scatter_symbols_batch(sym, maps, n, npix, c, table=tab).view(n, h, w, c)
+        want = np.zeros_like(q)
+        for f, m in enumerate(maps):
+            want[f][..., m] = q[f][..., m]
+            eq(ops.scatter_symbols(per_frame[f], npix, c, m).view(h, w, c), want[f])
+        eq(back, want)

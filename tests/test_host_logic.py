@@ -430,3 +430,24 @@ def test_entropy_memory_estimate_reads_the_map_count_behind_the_md5_text():
     a = FrameCodec._entropy_bytes(_fake_codec(), plain, [0], dd)
     b = FrameCodec._entropy_bytes(_fake_codec(md5=True), tagged, [0], dd)
     assert a == b == 3 * 16 * 134 + 16 * 4 * 640
+
+
+def test_estimating_rate_restores_the_flag_when_the_body_raises():
+    """encode() switches bitstream.ESTIMATE_RATE on through estimating_rate(): a body that raises leaves the flag at its
+    previous value (for both previous values), so a failed encode does not leave every later launch_finalize of the
+    process paying the rate kernels"""
+    from aivc_amd.real_life import bitstream
+    before = bitstream.ESTIMATE_RATE
+    try:
+        for previous in (False, True):
+            bitstream.ESTIMATE_RATE = previous
+            with pytest.raises(ZeroDivisionError):
+                with bitstream.estimating_rate():
+                    assert bitstream.ESTIMATE_RATE is True
+                    1 / 0
+            assert bitstream.ESTIMATE_RATE is previous
+            with bitstream.estimating_rate():  # and on the success path
+                assert bitstream.ESTIMATE_RATE is True
+            assert bitstream.ESTIMATE_RATE is previous
+    finally:
+        bitstream.ESTIMATE_RATE = before

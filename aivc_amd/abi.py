@@ -1,4 +1,4 @@
-"""ctypes mirror of include/aivc_hip.h (struct layouts, constants, prototypes).
+"""ctypes mirror of include/aivc_hip.h and include/aivc_hip_warp.h (struct layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -6,7 +6,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -30,6 +30,10 @@ WINO_MIN_PIXELS = 8000  # include/aivc_hip.h: AIVC_WINO_MIN_PIXELS
 WINO_MIN_PIXELS_TCONV = 32768  # ... AIVC_WINO_MIN_PIXELS_TCONV
 
 FRAME_I, FRAME_P, FRAME_B = 0, 1, 2
+
+# include/aivc_hip_warp.h: aivc_warp_modes
+WARP_BILINEAR, WARP_NEAREST, WARP_BICUBIC = 0, 1, 2
+WARP_BORDER, WARP_ZEROS, WARP_REFLECTION = 0, 1, 2
 
 _f = C.c_void_p  # every buffer pointer travels as an integer address
 
@@ -165,6 +169,10 @@ def declare(lib, suffix=''):
         chk.argtypes = [C.c_uint64, C.c_uint32, _f, C.c_void_p]
         chk.restype = C.c_int
         fns['aivc_selfcheck_gdn_math'] = chk
+        wm = lib.aivc_warp_modes  # include/aivc_hip_warp.h: the warp in every sampling mode, no host twin either
+        wm.argtypes = [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, C.c_void_p]
+        wm.restype = C.c_int
+        fns['aivc_warp_modes'] = wm
     mws = getattr(lib, 'aivc_metrics_workspace' + suffix)
     mws.argtypes = [_i32, _i32, _i32]
     mws.restype = C.c_size_t

@@ -3,6 +3,7 @@
 // One thread per pixel (channels are innermost, so a pixel's channels sit in one or two
 // cache lines); grids are sized >> 256 CUs for every frame size the codec handles.
 #include "common.h"
+#include "warp_taps.h"
 
 namespace aivc {
 
@@ -262,6 +263,48 @@ __global__ __launch_bounds__(256) void warp_kernel(const float *__restrict__ x, 
   const float *img = x + (size_t)b * h * w * c;
   const WarpTap t = warp_taps(h, w, flow[pix * 2], flow[pix * 2 + 1], r, q);
   for (int ch = 0; ch < c; ++ch) out[pix * c + ch] = warp_apply(img, c, ch, t);
+}
+
+// ---------------------------------------------------------------- warp in every sampling mode (include/aivc_hip_warp.h)
+// One thread per output pixel and group of 4 channels: position, tap indices, weights and mask once (warp_taps.h), then
+// every tap is one 16-byte gather and the result one 16-byte store; consecutive lanes write consecutive 16 bytes.  The
+// footprint is gathered straight from memory (flows are arbitrary: nothing to tile); for small motion a wave's taps fall
+// into the cache lines its neighbours' taps fetched.  Tap offsets are clamped or -1 (warp_modes_index): no flow value,
+// NaN and infinities included, forms an address outside the image.
+template <int INTERP, int PAD>
+__global__ __launch_bounds__(256) void warp_modes_kernel(const float *__restrict__ x, const float *__restrict__ flow,
+                                                         int n, int h, int w, int cg, int align_corners,
+                                                         float *__restrict__ out) {
+  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (size_t)n * h * w * cg) return;
+  const size_t pix = gid / cg;
+  const int g = (int)(gid % cg);
+  const int q = (int)(pix % w), r = (int)((pix / w) % h), b = (int)(pix / ((size_t)w * h));
+  const float2 v = reinterpret_cast<const float2 *>(flow)[pix];
+  const WarpModesTaps<INTERP> t = warp_modes_taps<INTERP, PAD>(h, w, v.x, v.y, r, q, align_corners != 0);
+  float4 res = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (t.keep) {
+    constexpr int NN = WarpModesTaps<INTERP>::N * WarpModesTaps<INTERP>::N;
+    const float4 *img = reinterpret_cast<const float4 *>(x) + (size_t)b * h * w * cg + g;
+    float4 tap[NN];
+#pragma unroll
+    for (int k = 0; k < NN; ++k)
+      tap[k] = t.off[k] >= 0 ? img[(size_t)t.off[k] * cg] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    res.x = warp_modes_sum<INTERP>(t, [&](int k) { return tap[k].x; });
+    res.y = warp_modes_sum<INTERP>(t, [&](int k) { return tap[k].y; });
+    res.z = warp_modes_sum<INTERP>(t, [&](int k) { return tap[k].z; });
+    res.w = warp_modes_sum<INTERP>(t, [&](int k) { return tap[k].w; });
+  }
+  reinterpret_cast<float4 *>(out)[gid] = res;
+}
+
+template <int INTERP, int PAD>
+static int launch_warp_modes(const float *x, const float *flow, int n, int h, int w, int c, int align_corners, float *out,
+                             hipStream_t s) {
+  const size_t total = (size_t)n * h * w * (c / 4);
+  hipLaunchKernelGGL((warp_modes_kernel<INTERP, PAD>), dim3(cdiv(total, 256)), dim3(256), 0, s, x, flow, n, h, w, c / 4,
+                     align_corners, out);
+  return check_launch("warp_modes");
 }
 
 struct BlendArgs {
@@ -548,6 +591,31 @@ AIVC_EXPORT int aivc_warp(const float *x, const float *flow, int32_t n, int32_t 
   hipLaunchKernelGGL(warp_kernel, dim3(cdiv((size_t)n * h * w, 256)), dim3(256), 0, to_stream(stream), x, flow, n, h,
                      w, c, out);
   return check_launch("warp");
+}
+
+AIVC_EXPORT int aivc_warp_modes(const float *x, const float *flow, int32_t n, int32_t h, int32_t w, int32_t c,
+                                int32_t interp, int32_t pad, int32_t align_corners, float *out, aivc_stream_t stream) {
+  if (interp < AIVC_WARP_BILINEAR || interp > AIVC_WARP_BICUBIC || pad < AIVC_WARP_BORDER || pad > AIVC_WARP_REFLECTION)
+    return AIVC_ERR_ARG;
+  if (interp == AIVC_WARP_BILINEAR && pad == AIVC_WARP_BORDER && align_corners)  // the codec's mode: same kernel, same bits
+    return aivc_warp(x, flow, n, h, w, c, out, stream);
+  if (!x || !flow || !out || n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 4 != 0) return AIVC_ERR_ARG;
+  if ((size_t)h * w > (size_t)INT32_MAX) return AIVC_ERR_ARG;  // (tap offsets are ints)
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15u) || (reinterpret_cast<uintptr_t>(flow) & 7u))
+    return AIVC_ERR_ARG;
+  if ((size_t)n * h * w * (c / 4) > (size_t)UINT32_MAX) return AIVC_ERR_ARG;  // (one thread each: a dispatch counts its work-items in 32 bits)
+  const hipStream_t s = to_stream(stream);
+  switch (interp * 3 + pad) {
+    case 0: return launch_warp_modes<AIVC_WARP_BILINEAR, AIVC_WARP_BORDER>(x, flow, n, h, w, c, align_corners, out, s);
+    case 1: return launch_warp_modes<AIVC_WARP_BILINEAR, AIVC_WARP_ZEROS>(x, flow, n, h, w, c, align_corners, out, s);
+    case 2: return launch_warp_modes<AIVC_WARP_BILINEAR, AIVC_WARP_REFLECTION>(x, flow, n, h, w, c, align_corners, out, s);
+    case 3: return launch_warp_modes<AIVC_WARP_NEAREST, AIVC_WARP_BORDER>(x, flow, n, h, w, c, align_corners, out, s);
+    case 4: return launch_warp_modes<AIVC_WARP_NEAREST, AIVC_WARP_ZEROS>(x, flow, n, h, w, c, align_corners, out, s);
+    case 5: return launch_warp_modes<AIVC_WARP_NEAREST, AIVC_WARP_REFLECTION>(x, flow, n, h, w, c, align_corners, out, s);
+    case 6: return launch_warp_modes<AIVC_WARP_BICUBIC, AIVC_WARP_BORDER>(x, flow, n, h, w, c, align_corners, out, s);
+    case 7: return launch_warp_modes<AIVC_WARP_BICUBIC, AIVC_WARP_ZEROS>(x, flow, n, h, w, c, align_corners, out, s);
+    default: return launch_warp_modes<AIVC_WARP_BICUBIC, AIVC_WARP_REFLECTION>(x, flow, n, h, w, c, align_corners, out, s);
+  }
 }
 
 AIVC_EXPORT int aivc_warp_blend_rows(const float *mof, int32_t hm, int32_t wm, int32_t cm, const float *prev,

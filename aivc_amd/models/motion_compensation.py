@@ -15,6 +15,7 @@ class MotionCompensation(Module):
         v_prev, v_next = get_value('v_prev', param, default), get_value('v_next', param, default)
         beta = get_value('beta', param, default)
         mode = get_value('interpol_mode', param, default)
-        # stand-alone API path (the codec itself uses the fused aivc_warp_blend kernel)
+        # stand-alone API path (the codec itself uses the fused aivc_warp_blend kernel); 'interpol_mode' may be any of
+        # grid_sample's: 'bilinear' is aivc_warp, 'nearest' / 'bicubic' run aivc_warp_modes
         wp, wn = warp(prev, v_prev, interpol_mode=mode), warp(nxt, v_next, interpol_mode=mode)
         return {'x_warp': beta * wp + (1 - beta) * wn}

@@ -486,12 +486,32 @@ def downsample2x(x, ch0, nch):
     return out
 
 
-def warp(x, flow):
+WARP_INTERP = {'bilinear': abi.WARP_BILINEAR, 'nearest': abi.WARP_NEAREST, 'bicubic': abi.WARP_BICUBIC}
+WARP_PAD = {'border': abi.WARP_BORDER, 'zeros': abi.WARP_ZEROS, 'reflection': abi.WARP_REFLECTION}
+
+
+def warp(x, flow, interp='bilinear', pad='border', align_corners=True):
+    """NHWC x [n, h, w, c], flow [n, h, w, 2] -> the reference's warp() in any of its sampling modes (include/aivc_hip_warp.h).
+    The default call is the codec's mode on aivc_warp, as ever; every other mode runs warp_modes_kernel, which works on groups
+    of 4 channels (other channel counts are zero padded for the call)."""
+    if interp not in WARP_INTERP or pad not in WARP_PAD:
+        raise ValueError('warp: interp %r / pad %r: expected one of %s and one of %s' % (interp, pad, sorted(WARP_INTERP), sorted(WARP_PAD)))
     x, flow = _dev(x, torch.float32, 'x'), _dev(flow, torch.float32, 'flow')
     n, h, w, c = x.shape
+    if interp == 'bilinear' and pad == 'border' and align_corners:
+        out = torch.empty_like(x)
+        call('aivc_warp', _p(x), _p(flow), n, h, w, c, _p(out), _stream())
+        return out
+    if tuple(flow.shape) != (n, h, w, 2):
+        raise ValueError('warp: flow %s does not go with x %s' % (tuple(flow.shape), tuple(x.shape)))
+    c4 = (c + 3) // 4 * 4
+    x = pad_channels(x, c4)
     out = torch.empty_like(x)
-    call('aivc_warp', _p(x), _p(flow), n, h, w, c, _p(out), _stream())
-    return out
+    # algorithmic bytes: the frame in, the flow, the frame out (the footprints overlap: each input value counts once)
+    _hbm_profiled('warp_modes', n * h * w * 4 * (2 * c4 + 2),
+                  lambda: call('aivc_warp_modes', _p(x), _p(flow), n, h, w, c4, WARP_INTERP[interp], WARP_PAD[pad],
+                               1 if align_corners else 0, _p(out), _stream()))
+    return out if c4 == c else out[..., :c].contiguous()
 
 
 def warp_blend(mof, prev, nxt, h, w, frame_type, co=4, want_aux=False, rows=None):

@@ -101,18 +101,23 @@ AIVC_EXPORT int aivc_split_weights_bf16x3(const float *w, int32_t c_out, int32_t
   return aivc::split_weights_bf16x3(w, c_out, k_total, out, aivc::to_stream(stream));
 }
 
+// the three forms of the Winograd weight transform take the same arguments
+static int validate_winograd_weights(const float *w, int32_t c_out, int32_t c_in, const float *u) {
+  return (!w || !u || c_out <= 0 || c_in <= 0 || c_out % 64 || c_in % 8) ? AIVC_ERR_ARG : AIVC_OK;
+}
+
 AIVC_EXPORT int aivc_winograd_weights(const float *w, int32_t c_out, int32_t c_in, float *u, aivc_stream_t stream) {
-  if (!w || !u || c_out <= 0 || c_in <= 0 || c_out % 64 || c_in % 8) return AIVC_ERR_ARG;
+  if (const int rc = validate_winograd_weights(w, c_out, c_in, u)) return rc;
   return aivc::winograd_weights(w, c_out, c_in, u, aivc::to_stream(stream));
 }
 
 AIVC_EXPORT int aivc_winograd_weights_poly5(const float *w, int32_t c_out, int32_t c_in, float *u, aivc_stream_t stream) {
-  if (!w || !u || c_out <= 0 || c_in <= 0 || c_out % 64 || c_in % 8) return AIVC_ERR_ARG;
+  if (const int rc = validate_winograd_weights(w, c_out, c_in, u)) return rc;
   return aivc::winograd_weights_poly5(w, c_out, c_in, u, aivc::to_stream(stream));
 }
 
 AIVC_EXPORT int aivc_winograd_weights_tconv5(const float *w, int32_t c_out, int32_t c_in, float *u, aivc_stream_t stream) {
-  if (!w || !u || c_out <= 0 || c_in <= 0 || c_out % 64 || c_in % 8) return AIVC_ERR_ARG;
+  if (const int rc = validate_winograd_weights(w, c_out, c_in, u)) return rc;
   return aivc::winograd_weights_tconv5(w, c_out, c_in, u, aivc::to_stream(stream));
 }
 

@@ -31,11 +31,10 @@
 // 75 / 150 / 225 multiply-adds per output), not by the matrix pipe (50 % busy).
 #include <type_traits>
 
-#include "common.h"
+#include "mfma_util.h"
 
 namespace aivc {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct ImgArgs {
   aivc_image_src src[AIVC_MAX_IMAGES];

@@ -25,14 +25,9 @@
 //                  other's MFMAs.
 #include <stdlib.h>
 
-#include <type_traits>
-#include <utility>
-
-#include "common.h"
+#include "mfma_util.h"
 
 namespace aivc {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct WinoArgs {
   aivc_conv_params p;
@@ -43,10 +38,6 @@ struct WinoArgs {
   int poly;      // 1: the 5x5 stride-2 convolution as four stride-1 3x3 convolutions of the input's polyphase components
   int cpp_shift; // log2 of the chunks per phase (c_in / 8)
 };
-
-__device__ __forceinline__ void wino_glds16(const float *base, uint32_t voff, uint32_t lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(base), "s"(lds_dst) : "memory", "m0");
-}
 
 constexpr int WINO_RAW_STAGE = 11 * 1024;  // 648 slots of 16 bytes (4 parity planes x 81 pixels x 2 channel quads), 11 DMA instructions
 constexpr int WINO_U_STAGE = 32 * 1024;    // [16 positions][2 quads][64 channels][4 floats]
@@ -75,13 +66,12 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ph = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;  // waves w and w + 4 (one SIMD) = the two position halves of a sub-tile
   // H x W: the pixel grid the blocks walk = the OUTPUT's (stride 1: also the input's); Hi x Wi: the input's.  Polyphase form
-  // (a.poly, 5x5 stride 2, include/aivc_hip.h): the reduction runs over 4 phases x c_in channels, chunk c belongs to phase
+  // (MODE 1, 5x5 stride 2, include/aivc_hip.h): the reduction runs over 4 phases x c_in channels, chunk c belongs to phase
   // c >> cpp_shift = 2 py + px, whose patch pixel (y, x) is input pixel (clamp(2 y + py), clamp(2 x + px)) -- the replicate
   // padding of the ORIGINAL image -- and whose 3x3 kernel is the phase's taps padded with zeros: positions with i == 3 (py = 1)
   // or j == 3 (px = 1) have U = 0 and are not issued (49 instead of 64 of the 4 x 16 position products).
   const int H = TC ? p.h_in : p.h_out, W = TC ? p.w_in : p.w_out, Hi = p.h_in, Wi = p.w_in, Cin = p.c_in, Cout = p.c_out;
   const int gyc = TC ? 4 * a.gy : a.gy;  // entries of the block list per pixel block: channel blocks (x 4 classes)
-  constexpr int poly = POLY ? 1 : 0;
   const int cpp_shift = a.cpp_shift, cpp_mask = (1 << a.cpp_shift) - 1;
 
   // Persistent workgroups (one per CU: a.nwg of them) walk the blocks.  The dispatcher deals consecutive workgroup ids
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     s_py[k] = 2 * hy + (plane >> 1);
     s_px[k] = 2 * hx + (plane & 1);
   }
-  const int nch = poly ? 4 * (Cin >> 3) : (Cin >> 3);  // chunks of 8 (virtual) input channels per block
+  const int nch = POLY ? 4 * (Cin >> 3) : (Cin >> 3);  // chunks of 8 (virtual) input channels per block
   auto make_desc = [&](uint32_t blk) {
     Desc d;
     d.cb = (int)(blk % (uint32_t)gyc);
@@ -137,7 +127,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   // issue stream enters a phase (every c_in / 8 chunks), kept in two registers in between
   uint32_t iss_off[2];
   auto patch_offsets = [&](const Desc &d_, int ph2) {
-    const int st = poly ? 2 : 1, py = ph2 >> 1, px = ph2 & 1;
+    const int st = POLY ? 2 : 1, py = ph2 >> 1, px = ph2 & 1;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int iy = max(min(st * (16 * d_.byi - 1 + s_py[k]) + py, Hi - 1), 0), ix = max(min(st * (16 * d_.bxi - 1 + s_px[k]) + px, Wi - 1), 0);
@@ -180,12 +170,12 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       if ((c & cpp_mask) == 0) patch_offsets(d_, c >> cpp_shift);  // the issue stream enters a phase
       const float *src = uniform_ptr(d_.xbase + 8 * (c & cpp_mask));
       const uint32_t du = __builtin_amdgcn_readfirstlane(d);  // (under register pressure the compiler parks the uniform in a VGPR)
-      wino_glds16(src, iss_off[0], du);
-      if (wave < 3) wino_glds16(src, iss_off[1], du + 8192u);
+      glds16(src, iss_off[0], du);
+      if (wave < 3) glds16(src, iss_off[1], du + 8192u);
     } else {
       const float *src = d_.xbase + 8 * c;
-      wino_glds16(src, d_.r_off[0], d);
-      if (wave < 3) wino_glds16(src, d_.r_off[1], d + 8192u);
+      glds16(src, d_.r_off[0], d);
+      if (wave < 3) glds16(src, d_.r_off[1], d + 8192u);
     }
   };
   // zero-by-construction positions (polyphase / transposed forms): is position (i, j) of phase / class `pc` zero?
@@ -333,10 +323,6 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       }
       __builtin_amdgcn_sched_barrier(0);
       const float4 x0 = af[set][0], y0 = bf[set][0], x1 = af[set][1], y1 = bf[set][1];
-#ifdef WINO_EXP_NOMFMA
-      acc[q][0] += x0.x * y0.x + x0.y * y0.y + x0.z * y0.z + x0.w * y0.w;
-      acc[q + 1][0] += x1.x * y1.x + x1.y * y1.y + x1.z * y1.z + x1.w * y1.w;
-#else
       if constexpr (first && TC) {
         // the block's first chunk: a position the class does not issue gets a cleared accumulator (one MFMA of zeros), the others
         // start from the inline zero
@@ -382,12 +368,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
           acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, y1.w, acc[q + 1], 0, 0, 0);
         }
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
-#ifndef WINO_EXP_NOXFORM
       if ((tm >> q) & 1u) transform_step(NEXT{}, integral_constant<int, q>{});
       if ((tm >> (q + 1)) & 1u) transform_step(NEXT{}, integral_constant<int, q + 1>{});
-#endif
       __builtin_amdgcn_sched_barrier(0);
     };
     using std::integral_constant;
@@ -416,10 +399,6 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   const int act1 = p.act1, act2 = p.act2;
-  auto act_cheap = [](int act, float v) {  // NONE / LEAKY / RELU of act_apply() without branches
-    const float neg = act == AIVC_ACT_LEAKY ? v * 0.01f : (act == AIVC_ACT_RELU ? 0.0f : v);
-    return v > 0.0f ? v : neg;
-  };
   for (uint32_t kb = 0; kb < n_mine; ++kb) {
     // two chunks per trip (stage parities 0, 1: compile-time LDS offsets); the block's first chunk starts the accumulators
     auto chunk = [&](auto STAGE, auto FIRST, int c) {
@@ -427,12 +406,10 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       // (chunks beyond this block's are the first ones of the next block).  The transform of chunk c + 1 rides along (always,
       // except behind the last chunk of the workgroup's last block: a run-time flag -- as a third instantiation of the chunk
       // the register allocator spilled 213 registers)
-#ifndef WINO_EXP_NODMA
       issue_raw_at(kb, c + 2);
       issue_u_at(kb, c + 1);
-#endif
       uint32_t pm = 0xFFu;
-      if (poly) {  // phase 2 py + px of this chunk: j == 3 (q = 3, 7) is zero for px = 1, i == 3 (the upper half's q = 4 .. 7) for py = 1
+      if constexpr (POLY) {  // phase 2 py + px of this chunk: j == 3 (q = 3, 7) is zero for px = 1, i == 3 (the upper half's q = 4 .. 7) for py = 1
         const int ph2 = c >> cpp_shift;
         pm = 0xFFu & ~((ph2 & 1) ? 0x88u : 0u) & ~(((ph2 >> 1) && ph) ? 0xF0u : 0u);
       }
@@ -465,9 +442,6 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       }
     }
 
-#ifdef WINO_EXP_NOEPI
-    if (kb + 1u < n_mine) { cur = nxt; if (kb + 2u < n_mine) nxt = make_desc(block_of(kb + 2u)); continue; }
-#endif
     // ---- fold: S[a][b] = sum over this wave's positions (ascending, from +0) of T[a][i] T[b][j] M_p -------------------------------
     // keep[b]: output row a = ph (this wave finishes it), give[b]: row 1 - ph (handed to the partner).  The position half is a
     // compile-time constant inside each instantiation: the coefficients are, and the fold is the 18 block additions /
@@ -548,9 +522,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
         uint32_t lane_b = (uint32_t)(2 * (8 * cur.bxi + 4 * hh)) * sx + (uint32_t)pxc * c4 + (uint32_t)co * 4u;
         asm volatile("" : "+v"(lane_b));
         const size_t img_b = (size_t)cur.img * (size_t)Ho_ * Wo_ * c4;
-        auto rows = [&](auto RES, auto KIND, auto EDGE) {
+        auto rows = [&](auto RES, auto KIND, auto INSIDE) {
           constexpr bool has_res = decltype(RES)::value;
-          constexpr bool edge = decltype(EDGE)::value;
+          constexpr bool edge = !decltype(INSIDE)::value;  // the block's right columns lie outside the image
           constexpr int kind = decltype(KIND)::value;  // act1 / act2 combination, see below
           bool ok[8];  // column 2 (4 hh + rr) + b of the block exists
 #pragma unroll
@@ -584,9 +558,6 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
                 if constexpr (has_res) v = v + rv[rr * 2 + b];
                 if constexpr (kind == 3) v = v > 0.0f ? v : 0.0f;                 // act2 relu
                 if constexpr (kind == 4) v = __builtin_fmaxf(v, v * 0.01f);       // act2 leaky
-#ifdef WINO_EXP_NOSTORE
-                if (v == 123.456f)
-#endif
                 if (ok[rr * 2 + b]) *reinterpret_cast<gfloat *>(yb + lane_b + (uint32_t)((2 * rr + b) * 512) * (sx / 512u)) = v;
               }
           }
@@ -598,21 +569,21 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
         else if (act2 == AIVC_ACT_NONE) kind = act1 == AIVC_ACT_LEAKY ? 1 : 2;
         else if (act1 == AIVC_ACT_NONE) kind = act2 == AIVC_ACT_RELU ? 3 : 4;
         if (kind >= 0 && sx % 512u == 0u) {
-          auto go = [&](auto RES, auto EDGE) {
+          auto go = [&](auto RES, auto INSIDE) {
             switch (kind) {
-              case 0: rows(RES, integral_constant<int, 0>{}, EDGE); break;
-              case 1: rows(RES, integral_constant<int, 1>{}, EDGE); break;
-              case 2: rows(RES, integral_constant<int, 2>{}, EDGE); break;
-              case 3: rows(RES, integral_constant<int, 3>{}, EDGE); break;
-              default: rows(RES, integral_constant<int, 4>{}, EDGE); break;
+              case 0: rows(RES, integral_constant<int, 0>{}, INSIDE); break;
+              case 1: rows(RES, integral_constant<int, 1>{}, INSIDE); break;
+              case 2: rows(RES, integral_constant<int, 2>{}, INSIDE); break;
+              case 3: rows(RES, integral_constant<int, 3>{}, INSIDE); break;
+              default: rows(RES, integral_constant<int, 4>{}, INSIDE); break;
             }
           };
           if (inside_x) {
-            if (g_res) go(integral_constant<bool, true>{}, integral_constant<bool, false>{});
-            else go(integral_constant<bool, false>{}, integral_constant<bool, false>{});
-          } else {
             if (g_res) go(integral_constant<bool, true>{}, integral_constant<bool, true>{});
             else go(integral_constant<bool, false>{}, integral_constant<bool, true>{});
+          } else {
+            if (g_res) go(integral_constant<bool, true>{}, integral_constant<bool, false>{});
+            else go(integral_constant<bool, false>{}, integral_constant<bool, false>{});
           }
           goto epilogue_done;
         }
@@ -635,9 +606,6 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
             if (g_mul) v = g_mul[o] * v;
             if (g_res) v = v + g_res[o];
             v = act_cheap(act2, v);
-#ifdef WINO_EXP_NOSTORE
-            if (v == 123.456f)
-#endif
             g_y[o] = v;
           }
         }
@@ -656,16 +624,52 @@ __device__ __forceinline__ void wino_g(double g0, double g1, double g2, double (
   out[2] = 0.5 * ((g0 - g1) + g2);
   out[3] = g2;
 }
+
+// The three forms of the weight transform differ in where thread idx finds its 3x3 kernel g[r][l] and where its U goes
+// (AIVC_WINO_U_INDEX: the staging order of the product kernel); COUNT = transforms per (c_out, c_in) pair.
+struct WinoForm3x3 {  // stride-1 3x3: the kernel itself
+  static constexpr int COUNT = 1;
+  int co, ci, c_in;
+  __device__ WinoForm3x3(size_t idx, int, int c_in_) : co((int)(idx / c_in_)), ci((int)(idx % c_in_)), c_in(c_in_) {}
+  __device__ double tap(const float *w, int r, int l) const { return (double)w[(((size_t)co * 3 + r) * 3 + l) * c_in + ci]; }
+  __device__ size_t out(int pos) const { return AIVC_WINO_U_INDEX(co, pos, ci, c_in); }
+};
+// 5x5 taps (ky, kx) of (co, ci); zero where ky or kx would be 5
+__device__ __forceinline__ double wino_tap5(const float *w, int co, int ci, int c_in, int ky, int kx) {
+  return ky < 5 && kx < 5 ? (double)w[(((size_t)co * 5 + ky) * 5 + kx) * c_in + ci] : 0.0;
+}
+// Polyphase form of the 5x5 stride-2 kernel (include/aivc_hip.h): phase 2 py + px holds the taps ky = 2 r + py, kx = 2 l + px;
+// virtual input channel phase * c_in + ci of a 4 c_in-channel layer.
+struct WinoFormPoly5 {
+  static constexpr int COUNT = 4;
+  int co, ci, c_in, phase;
+  __device__ WinoFormPoly5(size_t idx, int, int c_in_)
+      : co((int)(idx / ((size_t)4 * c_in_))), ci((int)((idx / 4) % c_in_)), c_in(c_in_), phase((int)(idx % 4)) {}
+  __device__ double tap(const float *w, int r, int l) const { return wino_tap5(w, co, ci, c_in, 2 * r + (phase >> 1), 2 * l + (phase & 1)); }
+  __device__ size_t out(int pos) const { return AIVC_WINO_U_INDEX(co, pos, phase * c_in + ci, 4 * c_in); }
+};
+// Transposed 5x5 stride-2 kernel, class by class (include/aivc_hip.h): class 2 pyc + pxc holds the taps ky = pyc + 4 - 2 r,
+// kx = pxc + 4 - 2 l (r = 0 is zero for pyc = 1); output channel block class * (c_out / 64) + co / 64 of a layer of 4 c_out
+// "virtual" output channels.
+struct WinoFormTconv5 {
+  static constexpr int COUNT = 4;
+  int co, ci, c_in, c_out, cls;
+  __device__ WinoFormTconv5(size_t idx, int c_out_, int c_in_)
+      : co((int)((idx / c_in_) % c_out_)), ci((int)(idx % c_in_)), c_in(c_in_), c_out(c_out_), cls((int)(idx / ((size_t)c_in_ * c_out_))) {}
+  __device__ double tap(const float *w, int r, int l) const { return wino_tap5(w, co, ci, c_in, (cls >> 1) + 4 - 2 * r, (cls & 1) + 4 - 2 * l); }
+  __device__ size_t out(int pos) const { return AIVC_WINO_U_INDEX(cls * c_out + co, pos, ci, c_in); }
+};
+
+template <class FORM>
 __global__ void __launch_bounds__(256) winograd_weights_kernel(const float *w, int c_out, int c_in, float *u) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)c_out * c_in) return;
-  const int co = (int)(idx / c_in), ci = (int)(idx % c_in);
+  if (idx >= (size_t)c_out * c_in * FORM::COUNT) return;
+  const FORM f(idx, c_out, c_in);
   double t[4][3], uu[4][4];
 #pragma unroll
   for (int l = 0; l < 3; ++l) {
     double col[4];
-    wino_g((double)w[(((size_t)co * 3 + 0) * 3 + l) * c_in + ci], (double)w[(((size_t)co * 3 + 1) * 3 + l) * c_in + ci],
-           (double)w[(((size_t)co * 3 + 2) * 3 + l) * c_in + ci], col);
+    wino_g(f.tap(w, 0, l), f.tap(w, 1, l), f.tap(w, 2, l), col);
 #pragma unroll
     for (int i = 0; i < 4; ++i) t[i][l] = col[i];
   }
@@ -674,78 +678,22 @@ __global__ void __launch_bounds__(256) winograd_weights_kernel(const float *w, i
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) u[AIVC_WINO_U_INDEX(co, 4 * i + j, ci, c_in)] = (float)uu[i][j];
+    for (int j = 0; j < 4; ++j) u[f.out(4 * i + j)] = (float)uu[i][j];
 }
 
+template <class FORM>
+static int winograd_weights_launch(const char *what, const float *w, int c_out, int c_in, float *u, hipStream_t s) {
+  hipLaunchKernelGGL(winograd_weights_kernel<FORM>, dim3(cdiv((size_t)c_out * c_in * FORM::COUNT, 256)), dim3(256), 0, s, w, c_out, c_in, u);
+  return check_launch(what);
+}
 int winograd_weights(const float *w, int c_out, int c_in, float *u, hipStream_t s) {
-  hipLaunchKernelGGL(winograd_weights_kernel, dim3(cdiv((size_t)c_out * c_in, 256)), dim3(256), 0, s, w, c_out, c_in, u);
-  return check_launch("winograd_weights");
+  return winograd_weights_launch<WinoForm3x3>("winograd_weights", w, c_out, c_in, u, s);
 }
-
-// Polyphase form of the 5x5 stride-2 kernel (include/aivc_hip.h): phase 2 py + px holds the taps ky = 2 r + py, kx = 2 l + px
-// as a 3x3 kernel g[r][l] (zero where ky or kx would be 5), U = G g G^T as above; virtual input channel phase * c_in + ci of a
-// 4 c_in-channel layer in the staging order of AIVC_WINO_U_INDEX.
-__global__ void __launch_bounds__(256) winograd_weights_poly5_kernel(const float *w, int c_out, int c_in, float *u) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)c_out * c_in * 4) return;
-  const int phase = (int)(idx % 4), ci = (int)((idx / 4) % c_in), co = (int)(idx / ((size_t)4 * c_in));
-  const int py = phase >> 1, px = phase & 1;
-  auto tap = [&](int r, int l) -> double {
-    const int ky = 2 * r + py, kx = 2 * l + px;
-    return ky < 5 && kx < 5 ? (double)w[(((size_t)co * 5 + ky) * 5 + kx) * c_in + ci] : 0.0;
-  };
-  double t[4][3], uu[4][4];
-#pragma unroll
-  for (int l = 0; l < 3; ++l) {
-    double col[4];
-    wino_g(tap(0, l), tap(1, l), tap(2, l), col);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) t[i][l] = col[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) wino_g(t[i][0], t[i][1], t[i][2], uu[i]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) u[AIVC_WINO_U_INDEX(co, 4 * i + j, phase * c_in + ci, 4 * c_in)] = (float)uu[i][j];
-}
-
 int winograd_weights_poly5(const float *w, int c_out, int c_in, float *u, hipStream_t s) {
-  hipLaunchKernelGGL(winograd_weights_poly5_kernel, dim3(cdiv((size_t)c_out * c_in * 4, 256)), dim3(256), 0, s, w, c_out, c_in, u);
-  return check_launch("winograd_weights_poly5");
+  return winograd_weights_launch<WinoFormPoly5>("winograd_weights_poly5", w, c_out, c_in, u, s);
 }
-
-// Transposed 5x5 stride-2 kernel, class by class (include/aivc_hip.h): class 2 pyc + pxc holds the taps ky = pyc + 4 - 2 r,
-// kx = pxc + 4 - 2 l as a 3x3 kernel g[r][l] (zero where ky or kx would be 5: r = 0 for pyc = 1), U = G g G^T; output channel
-// block class * (c_out / 64) + co / 64 of a layer of 4 c_out "virtual" output channels in the staging order of AIVC_WINO_U_INDEX.
-__global__ void __launch_bounds__(256) winograd_weights_tconv5_kernel(const float *w, int c_out, int c_in, float *u) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)c_out * c_in * 4) return;
-  const int ci = (int)(idx % c_in), co = (int)((idx / c_in) % c_out), cls = (int)(idx / ((size_t)c_in * c_out));
-  const int pyc = cls >> 1, pxc = cls & 1;
-  auto tap = [&](int r, int l) -> double {
-    const int ky = pyc + 4 - 2 * r, kx = pxc + 4 - 2 * l;
-    return ky < 5 && kx < 5 ? (double)w[(((size_t)co * 5 + ky) * 5 + kx) * c_in + ci] : 0.0;
-  };
-  double t[4][3], uu[4][4];
-#pragma unroll
-  for (int l = 0; l < 3; ++l) {
-    double col[4];
-    wino_g(tap(0, l), tap(1, l), tap(2, l), col);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) t[i][l] = col[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) wino_g(t[i][0], t[i][1], t[i][2], uu[i]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) u[AIVC_WINO_U_INDEX(cls * c_out + co, 4 * i + j, ci, c_in)] = (float)uu[i][j];
-}
-
 int winograd_weights_tconv5(const float *w, int c_out, int c_in, float *u, hipStream_t s) {
-  hipLaunchKernelGGL(winograd_weights_tconv5_kernel, dim3(cdiv((size_t)c_out * c_in * 4, 256)), dim3(256), 0, s, w, c_out, c_in, u);
-  return check_launch("winograd_weights_tconv5");
+  return winograd_weights_launch<WinoFormTconv5>("winograd_weights_tconv5", w, c_out, c_in, u, s);
 }
 
 // what the kernel can address: 32-bit byte offsets inside one image

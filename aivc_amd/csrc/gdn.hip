@@ -21,13 +21,9 @@
 //                  different bank octets).  Applied on the SOURCE address of the DMA.
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "mfma_util.h"
 
 namespace aivc {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct GdnArgs {
   aivc_conv_params p;
@@ -36,10 +32,6 @@ struct GdnArgs {
 };
 
 constexpr int GDN_BM = 64;
-
-__device__ __forceinline__ void gdn_glds16(const float *base, uint32_t voff, uint32_t lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(base), "s"(lds_dst) : "memory", "m0");
-}
 
 __device__ __forceinline__ int gdn_swz(int row) { return (row & 15) ^ ((row & 4) << 1); }
 
@@ -98,13 +90,13 @@ __global__ __launch_bounds__(64 * GdnCfg<C>::NW, GdnCfg<C>::WGS) void gdn_reside
     if (m0 + GDN_BM <= M) {
 #pragma unroll
       for (int k = 0; k < PPW; ++k)
-        if (PIECES % NW == 0 || wave + NW * k < PIECES) gdn_glds16(src, d_voff[k], dst + (uint32_t)(NW * k) * 1024u);
+        if (PIECES % NW == 0 || wave + NW * k < PIECES) glds16(src, d_voff[k], dst + (uint32_t)(NW * k) * 1024u);
     } else {  // last, partial tile: rows beyond M fetch the last pixel again (computed, never stored)
       const int last = M - 1 - m0;
 #pragma unroll
       for (int k = 0; k < PPW; ++k)
         if (PIECES % NW == 0 || wave + NW * k < PIECES)
-          gdn_glds16(src, (uint32_t)min((int)(d_voff[k] / ROWB), last) * (uint32_t)ROWB + d_voff[k] % ROWB, dst + (uint32_t)(NW * k) * 1024u);
+          glds16(src, (uint32_t)min((int)(d_voff[k] / ROWB), last) * (uint32_t)ROWB + d_voff[k] % ROWB, dst + (uint32_t)(NW * k) * 1024u);
     }
   };
 

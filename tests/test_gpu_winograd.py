@@ -295,6 +295,20 @@ def test_polyphase_5x5_stride_2_hip_equals_oracle_bit_for_bit(idx, cuda, oracle,
     assert np.abs(g - v1).max() <= 2e-5 * max(1.0, float(np.abs(v1).max()))
 
 
+@pytest.mark.parametrize('c_in', [8, 32])  # one and four chunks of 8 channels per phase / class
+@pytest.mark.parametrize('form', ['3x3', 'poly5', 'tconv5'])
+def test_each_weight_transform_form_equals_oracle_at_the_smallest_shapes(form, c_in, cuda, oracle):
+    """The three forms share one kernel body: every form's U image, bit for bit, at the smallest c_out the entry points accept."""
+    from aivc_amd import ops
+    k = 3 if form == '3x3' else 5
+    w = (np.random.default_rng(100 + c_in + k).standard_normal((64, k, k, c_in)) * 3).astype(np.float32)
+    tr = form == 'tconv5'
+    u = ops.winograd_weights(T(w, cuda), transposed=tr).cpu().numpy()
+    want = oracle.winograd_weights(w, transposed=tr)
+    assert u.size == want.size == 64 * 16 * c_in * (1 if form == '3x3' else 4)
+    assert np.array_equal(u.ravel(), np.asarray(want).ravel())
+
+
 def test_polyphase_weight_transform_equals_oracle(cuda, oracle):
     from aivc_amd import ops
     rng = np.random.default_rng(19)

@@ -97,8 +97,12 @@ def test_conv_family_bit_exact(case, algo, oracle, cuda):
     eq(got, ref)
 
 
-@pytest.mark.parametrize('grid', [1, 3, 7])
-@pytest.mark.parametrize('co,k,ci,h,w', [(3, 5, 64, 21, 100), (6, 5, 64, 9, 70), (3, 3, 16, 13, 65)])
+THIN_WALK_GRIDS = [1, 3, 7]
+THIN_WALK_CASES = [(3, 5, 64, 21, 100), (6, 5, 64, 9, 70), (3, 3, 16, 13, 65)]  # co, k, ci, h, w
+
+
+@pytest.mark.parametrize('grid', THIN_WALK_GRIDS)
+@pytest.mark.parametrize('co,k,ci,h,w', THIN_WALK_CASES)
 def test_thin_layer_tile_walk(grid, co, k, ci, h, w, oracle, cuda, monkeypatch):
     """The thin output layer's persistent groups walk several tiles each (origins advanced without divisions across tile
     rows and images, double-buffered patches, epilogue of the previous tile inside the next chain): forced here at
@@ -486,7 +490,7 @@ def test_range_coder_many_streams_concurrently(oracle, cuda):
         eq(dec[i], want[i])
 
 
-@pytest.mark.parametrize('case', [
+FUSED_GDN_CASES = [
     # mode, k, stride, pad, cin, cout, h, w, inverse, res
     (abi.MODE_CONV, 5, 2, 2, 12, 64, 31, 45, False, False),
     (abi.MODE_CONV, 5, 2, 2, 64, 128, 33, 29, False, False),
@@ -496,7 +500,10 @@ def test_range_coder_many_streams_concurrently(oracle, cuda):
     (abi.MODE_TCONV, 5, 2, 0, 128, 64, 23, 21, True, False),
     (abi.MODE_CONV, 3, 1, 1, 32, 32, 9, 9, False, False),
     (abi.MODE_CONV, 3, 1, 1, 8, 8, 9, 9, False, True),      # not fusable: two launches
-])
+]
+
+
+@pytest.mark.parametrize('case', FUSED_GDN_CASES)
 def test_fused_gdn_bit_exact(case, oracle, cuda):
     """conv + (I)GDN fused in one launch == oracle fused == oracle conv followed by oracle GDN"""
     from aivc_amd import ops
@@ -558,7 +565,7 @@ def test_fused_gdn_operand_range_fallback(scale, zero_bias, inv, oracle, cuda):
     np.testing.assert_array_equal(got_i.cpu().numpy().view(np.uint32), want_i.view(np.uint32))
 
 
-@pytest.mark.parametrize('case', [
+FUSED_TAIL_CASES = [
     # k, stride, cin, c_mid, c_tail, n, h, w, act1, act2, res
     (3, 1, 64, 64, 128, 2, 16, 32, abi.ACT_LEAKY, abi.ACT_LEAKY, True),   # whole 128-pixel tiles (the bottleneck block)
     (3, 1, 64, 64, 128, 2, 17, 19, abi.ACT_LEAKY, abi.ACT_LEAKY, True),   # ragged last tile
@@ -572,7 +579,10 @@ def test_fused_gdn_operand_range_fallback(scale, zero_bias, inv, oracle, cuda):
     # an attention block 128 wide (bench.py --widths n=256) at 96 x 96 >= AIVC_WINO_MIN_PIXELS, size rule in force: under fp32w the
     # 3x3 is covered, the library declines the fused request, the two launches take 301 then the 1x1
     (3, 1, 128, 128, 256, 1, 96, 96, abi.ACT_LEAKY, abi.ACT_LEAKY, True),
-])
+]
+
+
+@pytest.mark.parametrize('case', FUSED_TAIL_CASES)
 def test_fused_tail_bit_exact(case, oracle, cuda):
     """conv + activation + 1x1 conv (+ residual, activation) in one launch == the oracle's two convolutions; a tail leaves the
     contract version of its conv unchanged (the Winograd chain where version 2 covers the conv, else none)"""
@@ -677,7 +687,10 @@ def test_fused_tail_is_one_launch(cuda):
     assert load()['aivc_conv2d_variant'](C.byref(p)) < 0
 
 
-@pytest.mark.parametrize('h,w,n', [(9, 13, 2), (16, 128, 1), (35, 131, 2), (64, 64, 3)])
+CONV_IMAGES_CASES = [(9, 13, 2), (16, 128, 1), (35, 131, 2), (64, 64, 3)]  # h, w, n
+
+
+@pytest.mark.parametrize('h,w,n', CONV_IMAGES_CASES)
 @pytest.mark.parametrize('use_gdn', [True, False])
 def test_conv_images_bit_exact(h, w, n, use_gdn, cuda, oracle, monkeypatch):
     """aivc_conv_images (first analysis layer straight from the image sources) == oracle conv over the packed tensor

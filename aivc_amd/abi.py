@@ -1,4 +1,4 @@
-"""ctypes mirror of include/aivc_hip.h and include/aivc_hip_warp.h (struct layouts, constants, prototypes).
+"""ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h and include/aivc_hip_color.h (struct layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -6,7 +6,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -150,6 +150,13 @@ PROTOTYPES = {
     'aivc_table_prob': [_f, _f, _sz, _sz, _i32, _f],
 }
 
+# include/aivc_hip_color.h: device only, like aivc_warp_modes (the CPU oracle has no `_ref` twin of these; their CPU statement is
+# Pillow itself, tests/test_color_tables.py)
+COLOR_PROTOTYPES = {
+    'aivc_rgb8_to_yuv420u8': [_f, _i32, _i32, _i32, _f, _f, _f],
+    'aivc_yuv8_to_rgb8': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f],
+}
+
 
 def declare(lib, suffix=''):
     """Attach argtypes/restype for every entry of the header; raises AttributeError when the
@@ -173,6 +180,11 @@ def declare(lib, suffix=''):
         wm.argtypes = [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, C.c_void_p]
         wm.restype = C.c_int
         fns['aivc_warp_modes'] = wm
+        for name, args in COLOR_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = list(args) + [C.c_void_p]
+            fn.restype = C.c_int
+            fns[name] = fn
     mws = getattr(lib, 'aivc_metrics_workspace' + suffix)
     mws.argtypes = [_i32, _i32, _i32]
     mws.restype = C.c_size_t

@@ -53,6 +53,9 @@ def main(argv=None):
     from aivc_amd import parallel
     if parallel.rank_world()[0] != 0:  # multi-rank job: rank 0 evaluates
         return status
+    if os.path.isdir(a.i) or dec_cli.is_png_folder(a.o):  # (evaluate.py scores planar files)
+        print('[INFO] evaluation skipped: it compares two planar .yuv files, -i / -o name picture folders')
+        return status
     print(('*' * 80).center(120))
     print('Starting evaluation'.center(120))
     eval_cli.main(['--raw', a.i, '--compressed', a.o, '--bitstream', a.bitstream_out, '--start_frame', str(a.start_frame)])

@@ -3,7 +3,7 @@
 import argparse
 
 from aivc_amd.cli_common import get_model, resolve_device
-from aivc_amd.real_life.decode import Decoder, decode_one_video
+from aivc_amd.real_life.decode import Decoder, decode_one_video, is_png_folder
 
 
 def main(argv=None):
@@ -15,7 +15,7 @@ def main(argv=None):
     p.add_argument('--rng_seed', default=666, type=int)
     a = p.parse_args(argv)
     dev = resolve_device(a.cpu)
-    out = a.o if a.o.endswith('.yuv') else a.o + '.yuv'
+    out = a.o if a.o.endswith('.yuv') or is_png_folder(a.o) else a.o + '.yuv'  # ('dir/' or an existing directory: <idx>.png)
     dec = Decoder({'full_net': get_model(a.model, dev)}).eval()
     from aivc_amd.real_life.cat_binary_files import ContainerError
     try:

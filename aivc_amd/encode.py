@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""encode.py CLI (flags of src/encode.py:27-66).  python -m aivc_amd.encode -i clip_WxH_fps_420.yuv ..."""
+"""encode.py CLI (flags of src/encode.py:27-66).  python -m aivc_amd.encode -i clip_WxH_fps_420.yuv ...
+-i may also name a folder of the reference's pictures: PNG triplets (<idx>_{y,u,v}.png, or the CLIC layout) or <idx>.png RGB."""
 import argparse
 
 from aivc_amd.cli_common import get_model, resolve_device

@@ -1,8 +1,35 @@
-"""Image helpers with the reference's names (src/func_util/img_processing.py)."""
+"""Image helpers with the reference's names (src/func_util/img_processing.py).
+
+PNG decoding and encoding is file I/O and stays Pillow on the host; colour conversion and chroma resampling run on the device
+(ops.rgb8_to_yuv420u8 / ops.yuv8_to_rgb8, include/aivc_hip_color.h), bit for bit what Pillow computes for the reference.
+
+The loaders return what the reference returns -- float tensors in [0, 1], value k / 255 for the 8-bit level k -- but on the
+device (`device` argument / param entry, default 'cuda'), and as a YuvDic: a dict that also carries the uint8 planes it was made
+from (`.u8`, {'y','u','v'} of [1, h, w]), which is what the codec's 8-bit first layer takes (u8_planes()).
+
+Chroma sizes: a frame loaded from an RGB PNG has the reference's FLOOR-sized chroma planes (h // 2, w // 2); the planar .yuv
+path of this package stores CEIL-sized ones.  They agree for even h and w."""
+import os
+
+import numpy as np
 import torch
 
 from .. import ops
 from .nn_util import get_value
+
+
+class YuvDic(dict):
+    """{'y','u','v'} float tensors; .u8: the same planes as uint8 [1, h, w] tensors"""
+    u8 = None
+
+
+def u8_planes(frame):
+    """uint8 planes {'y','u','v'} of [1, h, w] of a loaded frame: the ones it was made from, or round(255 x) of its floats
+    (exact for k / 255)"""
+    if getattr(frame, 'u8', None) is not None:
+        return frame.u8
+    return {k: (frame[k] if frame[k].dtype == torch.uint8 else torch.round(frame[k].float() * 255.0).to(torch.uint8))
+            .reshape(1, frame[k].shape[-2], frame[k].shape[-1]) for k in ('y', 'u', 'v')}
 
 
 def get_y_u_v(x):
@@ -30,3 +57,153 @@ def cast_before_png_saving(param):
 
 def interpolate_nearest(x, scale=2):
     return torch.nn.functional.interpolate(x, scale_factor=scale, mode='nearest')
+
+
+def _frame_storage_name(sequence_path, absolute_idx, loading_mode):
+    if loading_mode == 'old':
+        return sequence_path + str(absolute_idx)
+    if loading_mode == 'clic':
+        return sequence_path + sequence_path.split('/')[-2] + '_' + str(absolute_idx).zfill(5)
+    raise ValueError('load_frames: loading_mode %r (expected old or clic)' % (loading_mode,))
+
+
+def load_frames(param):
+    """{'frame_0': {'y','u','v'}, 'frame_1': ...} from the folder <sequence_path> (src/func_util/img_processing.py:78-176):
+    <idx>_{y,u,v}.png ('old'), <folder name>_<idx, 5 digits>_{y,u,v}.png ('clic'), or one RGB <name>.png per frame (rgb).
+    nb_frame_to_load frames from idx_starting_frame on; the last nb_pad_frame of them are not read but repeat the last frame
+    that was.  Every plane is a [1, 1, h, w] float tensor on param['device'] (default 'cuda')."""
+    default = {'sequence_path': None, 'idx_starting_frame': 0, 'nb_frame_to_load': 3, 'nb_pad_frame': 0, 'rgb': False,
+               'loading_mode': 'old', 'device': 'cuda'}
+    sequence_path = get_value('sequence_path', param, default)
+    first = get_value('idx_starting_frame', param, default)
+    nb = get_value('nb_frame_to_load', param, default)
+    nb_pad = get_value('nb_pad_frame', param, default)
+    rgb = get_value('rgb', param, default)
+    loading_mode = get_value('loading_mode', param, default)
+    device = get_value('device', param, default)
+    if not sequence_path.endswith('/'):
+        sequence_path += '/'
+    last_loaded = first + nb - nb_pad - 1
+    frames = {}
+    for gop_idx in range(nb):
+        name = _frame_storage_name(sequence_path, min(first + gop_idx, last_loaded), loading_mode)
+        if rgb:
+            frames['frame_' + str(gop_idx)] = load_RGB_as_YUV420_dic(name, device)
+        else:
+            frames['frame_' + str(gop_idx)] = _with_batch_dim(load_YUV_as_dic_tensor(name, device))
+    return frames
+
+
+def _with_batch_dim(x):
+    out = YuvDic({k: x[k].view(1, *x[k].shape) for k in ('y', 'u', 'v')})
+    out.u8 = x.u8
+    return out
+
+
+_LEVELS = {}
+
+
+def _levels(device):
+    """k / 255 for k = 0 .. 255 as to_tensor computes it on the host, the correctly rounded quotient, on `device`.  Dividing a
+    device tensor by the number 255 multiplies by the rounded reciprocal instead and is one ulp off for some k."""
+    device = torch.device(device)
+    if device not in _LEVELS:
+        _LEVELS[device] = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(device)
+    return _LEVELS[device]
+
+
+def _from_u8(planes, ndim):
+    """uint8 planes [1, h, w] -> YuvDic of k / 255 floats (to_tensor's division) with ndim dimensions"""
+    out = YuvDic({k: _levels(p.device)[p.long()].view(*((1,) * (ndim - 2)), p.shape[-2], p.shape[-1])
+                  for k, p in planes.items()})
+    out.u8 = planes
+    return out
+
+
+def load_RGB_as_YUV420_dic(path_img, device='cuda'):
+    """<path_img>.png, an RGB picture -> {'y': [1,1,h,w], 'u','v': [1,1,h//2,w//2]} (src/func_util/img_processing.py:179-196):
+    Pillow's 8-bit RGB -> YCbCr, chroma sample (2i, 2j) kept (nearest, scale 0.5), on the device.  A PNG of another mode
+    (palette, grey, alpha) is first brought to 8-bit RGB by Pillow, as part of decoding the file."""
+    from PIL import Image
+    img = Image.open(path_img + '.png')
+    if img.mode != 'RGB':
+        img = img.convert('RGB')
+    rgb = torch.from_numpy(np.asarray(img).copy()).to(device)
+    y, u, v = ops.rgb8_to_yuv420u8(rgb.view(1, *rgb.shape))
+    return _from_u8({'y': y, 'u': u, 'v': v}, 4)
+
+
+def load_YUV_as_dic_tensor(path_img, device='cuda'):
+    """<path_img>_{y,u,v}.png, 8-bit grey pictures -> {'y','u','v'} of 3-D tensors [1, h, w], no batch dimension
+    (src/func_util/img_processing.py:199-218)."""
+    from PIL import Image
+    planes = {}
+    for k in ('y', 'u', 'v'):
+        img = Image.open(path_img + '_' + k + '.png')
+        if img.mode != 'L':
+            img = img.convert('L')
+        a = np.asarray(img)
+        planes[k] = torch.from_numpy(a.copy()).to(device).view(1, *a.shape)
+    return _from_u8(planes, 3)
+
+
+def _to_u8(t):
+    """to_pil_image's cast of a float tensor: mul(255).byte(), a truncation.  8-bit tensors pass through."""
+    return t if t.dtype == torch.uint8 else t.mul(255).byte()
+
+
+def _chw(x):
+    return x[0] if x.ndim == 4 else x
+
+
+def _save_png(a, path_img, mode):
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(a.cpu().numpy()), mode).save(path_img)
+
+
+def save_tensor_as_img(x, path_img, mode='yuv420'):
+    """src/func_util/img_processing.py:221-287.  x holds floats in [0, 1] (cast like to_pil_image: mul(255), truncated) or uint8
+    levels, on the device.
+      'yuv420'        x: dict, chroma at half resolution -> nearest x 2, cropped to the luma size, YCbCr -> RGB on the device
+      'yuv444'        x: dict, chroma at full resolution
+      'yuv444_nodic'  x: [1,3,h,w] or [3,h,w] tensor (Y, Cb, Cr)
+      'rgb'           x: [1,3,h,w] or [3,h,w] tensor; the planar -> interleaved step is a torch permute of the uint8 tensor
+      'L'             x: [1,1,h,w] or [1,h,w] tensor
+    Only batch entry 0 is written, as in the reference.  'yuv420' with floor-sized chroma and an odd luma size repeats the
+    last chroma row / column (the reference raises there: its upsampled planes are one short)."""
+    if mode in ('yuv420', 'yuv444'):
+        y, u, v = (_to_u8(_chw(t)) for t in get_y_u_v(x))
+        y, u, v = (t.reshape(1, t.shape[-2], t.shape[-1]) for t in (y, u, v))
+        rgb = ops.yuv8_to_rgb8(y, u, v, chroma_shift=1 if mode == 'yuv420' else 0)
+        _save_png(rgb[0], path_img, 'RGB')
+    elif mode == 'yuv444_nodic':
+        p = _to_u8(_chw(x))
+        rgb = ops.yuv8_to_rgb8(p[0:1], p[1:2], p[2:3], chroma_shift=0)
+        _save_png(rgb[0], path_img, 'RGB')
+    elif mode == 'rgb':
+        _save_png(_to_u8(_chw(x)).permute(1, 2, 0), path_img, 'RGB')
+    elif mode == 'L':
+        _save_png(_to_u8(_chw(x))[0], path_img, 'L')
+    else:
+        raise ValueError('save_tensor_as_img: mode %r' % (mode,))
+
+
+def save_yuv_separately(x, path_img):
+    """every entry <key> of the dict x -> <path_img>_<key>.png, an 8-bit grey picture (src/func_util/img_processing.py:290-301)"""
+    for key in x:
+        _save_png(_to_u8(_chw(x[key]))[0], path_img + '_' + key + '.png', 'L')
+
+
+# ---- a folder of such pictures as the encoder's input -------------------------------------------------------------------
+def detect_folder_layout(sequence_path):
+    """-> (loading_mode, rgb, [frame indices present, ascending]) from the file names of the folder:
+    <idx>_y.png -> ('old', False), <folder>_<00idx>_y.png -> ('clic', False), <idx>.png / <folder>_<00idx>.png -> rgb."""
+    import re
+    folder = os.path.basename(os.path.normpath(sequence_path))
+    names = os.listdir(sequence_path)
+    for mode, rgb, pat in (('old', False, r'(\d+)_y\.png'), ('clic', False, re.escape(folder) + r'_(\d{5,})_y\.png'),
+                           ('old', True, r'(\d+)\.png'), ('clic', True, re.escape(folder) + r'_(\d{5,})\.png')):
+        idx = sorted(int(m.group(1)) for m in (re.fullmatch(pat, n) for n in names) if m)
+        if idx:
+            return mode, rgb, idx
+    raise ValueError('%s holds no <idx>_{y,u,v}.png, <folder>_<idx>_{y,u,v}.png or <idx>.png pictures' % sequence_path)

@@ -477,6 +477,38 @@ def frame_to_yuv420(x, h, w, skip=None, want_float=True, want_u8=True):
     return tuple(f), tuple(b)
 
 
+def rgb8_to_yuv420u8(rgb):
+    """interleaved uint8 RGB [n,h,w,3] -> uint8 planes y [n,h,w], u and v [n,h//2,w//2]: Pillow's convert('YCbCr') bit for bit,
+    chroma from sample (2i, 2j) alone (include/aivc_hip_color.h).  The chroma planes have the reference's FLOOR size, not the
+    ceil size of the planar .yuv path (yuv420_to_444, frame_to_yuv420); the two agree for even h and w."""
+    rgb = _dev(rgb, torch.uint8, 'rgb')
+    if rgb.dim() != 4 or rgb.shape[-1] != 3:
+        raise ValueError('rgb8_to_yuv420u8: expected [n, h, w, 3], got %s' % (tuple(rgb.shape),))
+    n, h, w, _ = rgb.shape
+    y = torch.empty((n, h, w), dtype=torch.uint8, device=rgb.device)
+    u = torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=rgb.device)
+    v = torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=rgb.device)
+    empty = u.numel() == 0
+    _hbm_profiled('rgb8_to_yuv420u8', n * (h * w * 4 + 2 * (h // 2) * (w // 2)),
+                  lambda: call('aivc_rgb8_to_yuv420u8', _p(rgb), n, h, w, _p(y), None if empty else _p(u), None if empty else _p(v),
+                               _stream()))
+    return y, u, v
+
+
+def yuv8_to_rgb8(y, u, v, chroma_shift=1):
+    """uint8 planes y [n,h,w], u and v [n,ch,cw] -> interleaved uint8 RGB [n,h,w,3]: Pillow's YCbCr -> RGB bit for bit.
+    chroma_shift = 1: half-resolution chroma of the floor or the ceil size, nearest x 2 and cropped; 0: full resolution."""
+    y, u, v = _dev(y, torch.uint8, 'y'), _dev(u, torch.uint8, 'u'), _dev(v, torch.uint8, 'v')
+    if y.dim() != 3 or u.dim() != 3 or u.shape != v.shape or u.shape[0] != y.shape[0]:
+        raise ValueError('yuv8_to_rgb8: planes %s / %s / %s' % (tuple(y.shape), tuple(u.shape), tuple(v.shape)))
+    n, h, w = y.shape
+    ch, cw = u.shape[1:]
+    rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=y.device)
+    _hbm_profiled('yuv8_to_rgb8', n * (h * w * 4 + 2 * ch * cw),
+                  lambda: call('aivc_yuv8_to_rgb8', _p(y), _p(u), _p(v), n, h, w, ch, cw, chroma_shift, _p(rgb), _stream()))
+    return rgb
+
+
 def downsample2x(x, ch0, nch):
     """NHWC x -> planar [n, nch, h//2, w//2] 2x2 means of channels ch0..ch0+nch-1 (OutputLayer)."""
     x = _dev(x, torch.float32, 'x')

@@ -1,7 +1,7 @@
 """Frame / GOP / video decoder with the reference's class and function names
 (src/real_life/decode.py).  Decoder.decode keeps the reference's dictionary contract (float YUV
 dicts, one bitstream file per frame); decode_one_video reads the container and writes planar YUV
-directly (the reference's PNG triplets + per-frame `dd` forks are out of scope)."""
+directly, or on request a folder of RGB pictures (the reference's per-frame `dd` forks are out of scope)."""
 import os
 import time
 
@@ -88,6 +88,20 @@ def write_yuv(frames, path):
                 f.write(np.ascontiguousarray(a).tobytes())
 
 
+def write_png_folder(frames, first, directory, device):
+    """decoded frames -> <directory>/<idx>.png, RGB pictures (func_util.img_processing.save_tensor_as_img, mode 'yuv420':
+    the colour conversion runs on the device, straight from the decoder's 8-bit planes)"""
+    from ..func_util.img_processing import save_tensor_as_img
+    os.makedirs(directory, exist_ok=True)
+    for i, fr in enumerate(frames):
+        save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % (first + i)), mode='yuv420')
+
+
+def is_png_folder(out_file):
+    """the opt-in of -o: a name that ends in '/' or an existing directory asks for RGB pictures, anything else for a .yuv"""
+    return bool(out_file) and (out_file.endswith('/') or os.path.isdir(out_file))
+
+
 def decode_one_video(param):
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False}
     decoder = get_value('decoder', param, default).eval()
@@ -126,7 +140,9 @@ def decode_one_video(param):
     print_log_msg('RESULT', 'Number of frames', '[frame]', int(n))
     print_log_msg('RESULT', 'Decoding time', '[s]', '%.1f' % dt)
     print_log_msg('RESULT', 'Decoding FPS', '[frame/s]', '%.1f' % (n / dt))
-    if out_file:
+    if is_png_folder(out_file):
+        write_png_folder(frames, first, out_file, dev)
+    elif out_file:
         write_yuv(frames, out_file)
     dist_barrier_after_write(world)
     if get_value('flag_bitstream_debug', param, default):

@@ -1,5 +1,5 @@
-"""encode(param) with the reference's signature and RESULT lines (src/real_life/encode.py), reading
-planar YUV directly instead of PNG triplets."""
+"""encode(param) with the reference's signature and RESULT lines (src/real_life/encode.py), reading a
+planar .yuv file, or -- when sequence_path is a directory -- the reference's folders of PNG pictures."""
 import os
 import time
 
@@ -38,6 +38,27 @@ def read_yuv(path, first=0, last=-1, device=None):
     return frames, first, last
 
 
+def read_png_folder(path, first=0, last=-1, device=None):
+    """A folder of the reference's pictures (func_util.img_processing.load_frames: PNG triplets in the old or the clic
+    layout, or one RGB PNG per frame; detected from the file names) -> the same list of uint8 plane dicts as read_yuv.
+    Frame indices are the ones in the file names; the frame size is the first picture's.  RGB pictures are converted on
+    the device and have the reference's floor-sized chroma planes, the codec stores ceil-sized ones: an odd frame size is
+    refused for them."""
+    from ..func_util import img_processing as ip
+    mode, rgb, present = ip.detect_folder_layout(path)
+    last = present[-1] if last < 0 else last
+    loaded = ip.load_frames({'sequence_path': path, 'idx_starting_frame': first, 'nb_frame_to_load': last - first + 1,
+                             'rgb': rgb, 'loading_mode': mode, 'device': device})
+    frames = [ip.u8_planes(loaded['frame_%d' % i]) for i in range(last - first + 1)]
+    h, w = frames[0]['y'].shape[-2:]
+    for fr in frames:
+        if tuple(fr['y'].shape[-2:]) != (h, w) or tuple(fr['u'].shape[-2:]) != ((h + 1) // 2, (w + 1) // 2):
+            raise ValueError('%s: luma %s with chroma %s: every frame must have the size of the first (%d x %d) and 4:2:0 '
+                             'chroma of the ceil size (RGB pictures: even sides)'
+                             % (path, tuple(fr['y'].shape[-2:]), tuple(fr['u'].shape[-2:]), w, h))
+    return frames, first, last
+
+
 def encode(param):
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1}
@@ -51,7 +72,7 @@ def encode(param):
     if first > last and last != -1:
         print('ERROR: First frame index bigger than last frame index')
         return
-    frames, first, last = read_yuv(seq, first, last, dev)
+    frames, first, last = (read_png_folder if os.path.isdir(seq) else read_yuv)(seq, first, last, dev)
     print_log_msg('INFO', 'Start encoding', '', '')
     t0 = time.time()
     fc = FrameCodec(model)

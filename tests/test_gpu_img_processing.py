@@ -1,0 +1,131 @@
+"""func_util.img_processing's loaders and savers against tests/golden/img_processing.npz, which tools/gen_golden_img.py made by
+running the reference's own functions; then the command-line path on a folder of RGB pictures, end to end.  The folders are
+written here with PIL from the fixture's pictures.  Every comparison is exact."""
+import os
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+pytestmark = pytest.mark.gpu
+
+CLIC_NAME = 'clip_a'
+
+
+@pytest.fixture(scope='module')
+def fx(golden):
+    return golden('img_processing')
+
+
+@pytest.fixture(scope='module')
+def folders(fx, tmp_path_factory):
+    root = tmp_path_factory.mktemp('img_processing')
+    paths = {k: str(root / (CLIC_NAME if k == 'clic' else k)) for k in ('old', 'clic', 'rgb')}
+    for p in paths.values():
+        os.makedirs(p)
+    for i in range(len(fx['in_rgb'])):
+        Image.fromarray(fx['in_rgb'][i], 'RGB').save(os.path.join(paths['rgb'], '%d.png' % i))
+        for c in 'yuv':
+            Image.fromarray(fx['in_' + c][i], 'L').save(os.path.join(paths['old'], '%d_%s.png' % (i, c)))
+            Image.fromarray(fx['in_' + c][i], 'L').save(os.path.join(paths['clic'], '%s_%05d_%s.png' % (CLIC_NAME, i, c)))
+    return paths
+
+
+@pytest.mark.parametrize('layout', ['old', 'clic', 'rgb'])
+def test_load_frames_equals_the_reference(cuda, fx, folders, layout):
+    from aivc_amd.func_util import img_processing as ip
+    assert int(fx['first']) != 0 and int(fx['nb_pad']) == 2
+    frames = ip.load_frames({'sequence_path': folders[layout], 'idx_starting_frame': int(fx['first']),
+                             'nb_frame_to_load': int(fx['nb_load']), 'nb_pad_frame': int(fx['nb_pad']), 'rgb': layout == 'rgb',
+                             'loading_mode': 'old' if layout == 'rgb' else layout, 'device': cuda})
+    assert list(frames) == [str(s) for s in fx['load_%s_names' % layout]]
+    for name, fr in frames.items():
+        assert sorted(fr) == ['u', 'v', 'y']
+        for c in 'yuv':
+            want = fx['load_%s_%s_%s' % (layout, name, c)]
+            assert fr[c].is_cuda and fr[c].dtype == torch.float32 and tuple(fr[c].shape) == want.shape
+            assert np.array_equal(fr[c].cpu().numpy(), want), (name, c)
+            # the 8-bit planes stay reachable and are the same levels
+            u8 = ip.u8_planes(fr)[c]
+            assert u8.dtype == torch.uint8 and tuple(u8.shape) == (1,) + want.shape[-2:]
+            assert np.array_equal(u8.cpu().numpy().astype(np.float32) / np.float32(255), want.reshape(u8.shape))
+    assert ip.detect_folder_layout(folders[layout])[:2] == ('old' if layout == 'rgb' else layout, layout == 'rgb')
+
+
+def test_single_frame_loaders_have_the_reference_shapes(cuda, fx, folders):
+    from aivc_amd.func_util import img_processing as ip
+    a = ip.load_RGB_as_YUV420_dic(os.path.join(folders['rgb'], '1'), cuda)
+    assert np.array_equal(a['u'].cpu().numpy(), fx['load_rgb_frame_0_u']) and a['y'].ndim == 4
+    b = ip.load_YUV_as_dic_tensor(os.path.join(folders['old'], '1'), cuda)
+    assert b['y'].ndim == 3 and np.array_equal(b['v'].cpu().numpy(), fx['load_old_frame_0_v'][0])
+
+
+@pytest.mark.parametrize('mode', ['yuv420', 'yuv444', 'rgb', 'yuv444_nodic', 'L'])
+def test_save_tensor_as_img_equals_the_reference(cuda, fx, tmp_path, mode):
+    from aivc_amd.func_util import img_processing as ip
+    if mode in ('yuv420', 'yuv444'):
+        x = {c: torch.from_numpy(fx['save_%s_in_%s' % (mode, c)]).to(cuda) for c in 'yuv'}
+    else:
+        x = torch.from_numpy(fx['save_%s_in' % mode]).to(cuda)
+    path = str(tmp_path / ('%s.png' % mode))
+    ip.save_tensor_as_img(x, path, mode=mode)
+    got = Image.open(path)
+    assert got.mode == ('L' if mode == 'L' else 'RGB')
+    assert np.array_equal(np.asarray(got), fx['save_%s_png' % mode])
+
+
+def test_save_yuv_separately_round_trips(cuda, fx, tmp_path):
+    from aivc_amd.func_util import img_processing as ip
+    x = {c: torch.from_numpy(fx['save_yuv420_in_' + c]).to(cuda) for c in 'yuv'}
+    ip.save_yuv_separately(x, str(tmp_path / 'sep'))
+    for c in 'yuv':
+        assert np.array_equal(np.asarray(Image.open(str(tmp_path / ('sep_%s.png' % c)))), fx['sep_png_' + c])
+    back = ip.load_YUV_as_dic_tensor(str(tmp_path / 'sep'), cuda)
+    for c in 'yuv':  # what was written (255 x, truncated) comes back as k / 255, and saving that again changes nothing ...
+        assert np.array_equal(ip.u8_planes(back)[c][0].cpu().numpy(), fx['sep_png_' + c])
+    # ... once the levels are exact: k / 255 * 255 truncates below k for some k, which is why cast_before_png_saving exists
+    ip.save_yuv_separately({c: ip.u8_planes(back)[c] for c in 'yuv'}, str(tmp_path / 'again'))
+    for c in 'yuv':
+        assert np.array_equal(np.asarray(Image.open(str(tmp_path / ('again_%s.png' % c)))), fx['sep_png_' + c])
+
+
+def test_rgb_folder_end_to_end(cuda, tmp_path):
+    """-i a folder of RGB pictures, -o a folder: the bitstream is the one of the .yuv file holding the same converted planes,
+    the pictures written are yuv8_to_rgb8 of the decoded planes.  64 x 48: even sides, floor- and ceil-sized chroma agree."""
+    from aivc_amd import ops, synth
+    from aivc_amd.func_util.GOP_structure import generate_gop_struct
+    from aivc_amd.models import arch
+    from aivc_amd.real_life.decode import Decoder, decode_one_video, write_yuv
+    from aivc_amd.real_life.encode import encode
+    w, h, n = 64, 48, 3
+    rng = np.random.default_rng(3)
+    base = rng.integers(0, 256, (h // 8, w // 8, 3), dtype=np.uint8).repeat(8, 0).repeat(8, 1).astype(np.int16)
+    src = str(tmp_path / 'clip')
+    os.makedirs(src)
+    rgb = np.stack([np.clip(np.roll(base, 2 * i, axis=1) + rng.integers(-6, 7, base.shape), 0, 255).astype(np.uint8) for i in range(n)])
+    for i in range(n):
+        Image.fromarray(rgb[i], 'RGB').save(os.path.join(src, '%d.png' % i))
+    y, u, v = ops.rgb8_to_yuv420u8(torch.from_numpy(rgb).to(cuda))
+    yuv = str(tmp_path / ('clip_%dx%d_25_420.yuv' % (w, h)))
+    write_yuv([{'y': y[i:i + 1], 'u': u[i:i + 1], 'v': v[i:i + 1]} for i in range(n)], yuv)
+
+    model = synth.make_model(arch.TINY_WIDTHS, seed=7, device=cuda)
+    blobs = {}
+    for name, seq in (('png', src), ('yuv', yuv)):
+        out = str(tmp_path / (name + '.bin'))
+        res = encode({'model': model, 'sequence_path': seq, 'GOP_struct': generate_gop_struct('1_GOP_2'), 'GOP_struct_name': '1_GOP_2',
+                      'idx_rate': 0, 'final_file': out})
+        assert res['nb_frames_to_code'] == n
+        with open(out, 'rb') as f:
+            blobs[name] = f.read()
+    assert blobs['png'] == blobs['yuv']
+
+    out_dir = str(tmp_path / 'decoded') + '/'
+    dec = Decoder({'full_net': model}).eval()
+    frames = decode_one_video({'decoder': dec, 'bitstream_path': str(tmp_path / 'png.bin'), 'device': str(cuda), 'out_file': out_dir})
+    assert sorted(os.listdir(out_dir)) == ['%d.png' % i for i in range(n)]
+    for i, fr in enumerate(frames):
+        want = ops.yuv8_to_rgb8(*(torch.as_tensor(fr[c]).to(cuda) for c in 'yuv'))[0].cpu().numpy()
+        got = Image.open(os.path.join(out_dir, '%d.png' % i))
+        assert got.mode == 'RGB' and np.array_equal(np.asarray(got), want)

@@ -1,0 +1,357 @@
+"""The conv family's part of tests/op_cases.py (read its docstring first): the case tables of tests/test_gpu_ops.py,
+test_gpu_winograd.py, test_gpu_gdn_resident.py and tests/test_gpu_memory_discipline.py and one builder per kind of launch.  Every
+builder's call passes keyword arguments on to ops.conv2d / ops.gdn (algo=...).  Not a test module."""
+import numpy as np
+
+from aivc_amd import abi
+from op_cases import Case
+
+CONV_CASES = [
+    # mode, k, stride, pad, cin, cout, h, w, act1, act2, mul, res
+    (abi.MODE_CONV, 5, 2, 2, 4, 8, 17, 23, 0, 0, False, False),
+    (abi.MODE_CONV, 3, 1, 1, 8, 8, 9, 11, abi.ACT_LEAKY, 0, False, True),
+    (abi.MODE_CONV, 3, 2, 1, 12, 16, 10, 14, abi.ACT_RELU, 0, False, False),
+    (abi.MODE_CONV, 1, 2, 0, 8, 8, 9, 13, 0, 0, False, False),
+    (abi.MODE_CONV, 1, 1, 0, 8, 8, 6, 10, abi.ACT_SIGMOID, 0, True, True),
+    (abi.MODE_CONV, 3, 1, 1, 8, 8, 7, 9, 0, abi.ACT_RELU, False, True),
+    (abi.MODE_TCONV, 5, 2, 0, 8, 6, 7, 9, 0, 0, False, False),
+    (abi.MODE_TCONV, 3, 2, 0, 8, 8, 5, 6, abi.ACT_LEAKY, 0, False, True),
+    (abi.MODE_TCONV, 5, 2, 0, 64, 3, 6, 5, 0, 0, False, False),
+    (abi.MODE_GDN, 1, 1, 0, 8, 8, 5, 7, 0, 0, False, False),
+    (abi.MODE_IGDN, 1, 1, 0, 16, 16, 5, 7, 0, 0, False, True),
+    (abi.MODE_CONV, 5, 2, 2, 64, 128, 33, 47, 0, 0, False, False),
+    (abi.MODE_CONV, 3, 1, 1, 128, 128, 19, 21, abi.ACT_LEAKY, 0, False, True),
+    (abi.MODE_CONV, 3, 2, 1, 128, 128, 40, 44, abi.ACT_LEAKY, 0, False, False),
+    (abi.MODE_CONV, 5, 2, 2, 12, 64, 47, 61, 0, 0, False, False),
+    (abi.MODE_CONV, 5, 2, 2, 128, 64, 30, 34, 0, 0, False, False),
+    (abi.MODE_CONV, 1, 1, 0, 128, 64, 23, 29, abi.ACT_LEAKY, 0, False, False),
+    (abi.MODE_CONV, 1, 2, 0, 128, 128, 31, 29, 0, 0, False, False),
+    (abi.MODE_TCONV, 5, 2, 0, 128, 128, 17, 19, 0, 0, False, False),
+    (abi.MODE_TCONV, 3, 2, 0, 128, 128, 17, 19, abi.ACT_LEAKY, 0, False, True),
+    (abi.MODE_TCONV, 5, 2, 0, 128, 64, 33, 35, 0, 0, False, False),
+    (abi.MODE_TCONV, 5, 2, 0, 32, 128, 9, 11, abi.ACT_LEAKY, 0, False, False),
+    (abi.MODE_GDN, 1, 1, 0, 128, 128, 33, 31, 0, 0, False, False),
+    (abi.MODE_IGDN, 1, 1, 0, 64, 64, 33, 31, 0, 0, False, True),
+    (abi.MODE_CONV, 3, 1, 1, 128, 192, 9, 11, 0, 0, False, False),
+    (abi.MODE_CONV, 3, 1, 1, 64, 256, 20, 20, 0, 0, False, False),
+    (abi.MODE_TCONV, 5, 2, 0, 64, 6, 37, 41, 0, 0, False, False),
+    (abi.MODE_TCONV, 3, 2, 0, 64, 3, 17, 33, abi.ACT_LEAKY, 0, False, True),
+    (abi.MODE_TCONV, 5, 2, 0, 128, 3, 9, 19, 0, 0, False, False),
+    (abi.MODE_TCONV, 5, 2, 0, 16, 6, 16, 16, 0, abi.ACT_RELU, False, True),
+    # thin outputs on the 16x16x4 MFMA kernel: partial tiles in x and y, several tiles, gate + residual
+    (abi.MODE_TCONV, 5, 2, 0, 64, 3, 19, 70, abi.ACT_LEAKY, 0, True, False),
+    (abi.MODE_TCONV, 3, 2, 0, 32, 6, 9, 40, 0, 0, False, False),
+    (abi.MODE_TCONV, 5, 2, 0, 48, 6, 8, 33, 0, abi.ACT_LEAKY, True, True),
+    (abi.MODE_TCONV, 3, 2, 0, 96, 3, 1, 1, 0, 0, False, False),
+    (abi.MODE_TCONV, 5, 2, 0, 64, 6, 6, 10, abi.ACT_SIGMOID, 0, False, False),  # falls back to the VALU kernel
+    (abi.MODE_TCONV, 5, 2, 0, 64, 3, 7, 70, abi.ACT_RELU, 0, False, False),     # lean epilogue, relu (+0.0 for negatives)
+    (abi.MODE_TCONV, 5, 2, 0, 32, 6, 5, 33, abi.ACT_LEAKY, 0, False, False),
+    # LDS-DMA K loop corner cases: a reduction of ONE K-tile (1x1, c_in 32), of an odd number (3x3 x 32 = 9), two
+    # tiles; transposed with image-border zero fill on every tile; c_out beyond the tile width; rows beyond M
+    (abi.MODE_CONV, 1, 1, 0, 32, 64, 9, 13, 0, 0, False, False),
+    (abi.MODE_CONV, 3, 1, 1, 32, 32, 11, 7, abi.ACT_LEAKY, 0, False, True),
+    (abi.MODE_CONV, 1, 2, 0, 64, 128, 5, 3, 0, abi.ACT_RELU, False, True),
+    (abi.MODE_TCONV, 3, 2, 0, 32, 64, 7, 9, 0, 0, False, False),
+    (abi.MODE_TCONV, 5, 2, 0, 64, 128, 1, 3, abi.ACT_LEAKY, 0, False, False),
+    (abi.MODE_CONV, 5, 2, 2, 96, 160, 13, 9, 0, 0, False, False),
+]
+
+THIN_WALK_GRIDS = [1, 3, 7]
+THIN_WALK_CASES = [(3, 5, 64, 21, 100), (6, 5, 64, 9, 70), (3, 3, 16, 13, 65)]  # co, k, ci, h, w
+
+FUSED_GDN_CASES = [
+    # mode, k, stride, pad, cin, cout, h, w, inverse, res
+    (abi.MODE_CONV, 5, 2, 2, 12, 64, 31, 45, False, False),
+    (abi.MODE_CONV, 5, 2, 2, 64, 128, 33, 29, False, False),
+    (abi.MODE_CONV, 3, 1, 1, 128, 128, 17, 19, False, True),
+    (abi.MODE_CONV, 3, 1, 1, 128, 128, 17, 19, True, True),
+    (abi.MODE_TCONV, 5, 2, 0, 128, 128, 9, 11, True, False),
+    (abi.MODE_TCONV, 5, 2, 0, 128, 64, 23, 21, True, False),
+    (abi.MODE_CONV, 3, 1, 1, 32, 32, 9, 9, False, False),
+    (abi.MODE_CONV, 3, 1, 1, 8, 8, 9, 9, False, True),      # not fusable: two launches
+]
+
+FUSED_TAIL_CASES = [
+    # k, stride, cin, c_mid, c_tail, n, h, w, act1, act2, res
+    (3, 1, 64, 64, 128, 2, 16, 32, abi.ACT_LEAKY, abi.ACT_LEAKY, True),   # whole 128-pixel tiles (the bottleneck block)
+    (3, 1, 64, 64, 128, 2, 17, 19, abi.ACT_LEAKY, abi.ACT_LEAKY, True),   # ragged last tile
+    (3, 1, 64, 64, 128, 1, 9, 5, abi.ACT_RELU, abi.ACT_NONE, True),       # a single partial tile
+    (3, 1, 64, 64, 128, 2, 13, 21, abi.ACT_NONE, abi.ACT_RELU, False),
+    (5, 2, 32, 64, 128, 2, 31, 27, abi.ACT_LEAKY, abi.ACT_NONE, False),
+    (1, 1, 128, 64, 128, 3, 11, 23, abi.ACT_RELU, abi.ACT_LEAKY, True),
+    (3, 1, 64, 64, 64, 2, 9, 9, abi.ACT_LEAKY, abi.ACT_LEAKY, True),      # not fusable (tail width): two launches
+    (3, 1, 8, 12, 24, 2, 9, 9, abi.ACT_LEAKY, abi.ACT_LEAKY, True),       # not fusable (narrow): two launches
+    (3, 1, 12, 6, 12, 1, 7, 9, abi.ACT_LEAKY, abi.ACT_LEAKY, True),       # intermediate width not a multiple of 4
+    # an attention block 128 wide (bench.py --widths n=256) at 96 x 96 >= AIVC_WINO_MIN_PIXELS, size rule in force: under fp32w the
+    # 3x3 is covered, the library declines the fused request, the two launches take 301 then the 1x1
+    (3, 1, 128, 128, 256, 1, 96, 96, abi.ACT_LEAKY, abi.ACT_LEAKY, True),
+]
+
+CONV_IMAGES_CASES = [(9, 13, 2), (16, 128, 1), (35, 131, 2), (64, 64, 3)]  # h, w, n
+
+GDN_RESIDENT_CASES = [
+    # c, n, h, w, inverse, res
+    (128, 1, 8, 8, False, False),      # one whole tile
+    (128, 1, 5, 7, False, False),      # one partial tile (35 of 64 rows)
+    (128, 2, 33, 31, False, True),     # 2046 pixels: 31 whole tiles + 62 rows
+    (128, 2, 33, 31, True, False),
+    (128, 1, 9, 13, True, True),
+    (64, 1, 33, 31, False, False),
+    (64, 2, 17, 19, True, True),
+    (64, 1, 3, 5, False, True),
+    (128, 3, 136, 120, False, False),  # 765 tiles: more than the 512 persistent workgroups of a 256-CU part
+    (128, 3, 136, 120, True, True),
+]
+
+WINO_CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, mul, res
+    (1, 8, 8, 32, 128, 0, 0, True, False, False),
+    (2, 7, 9, 32, 128, 1, 0, True, False, False),      # odd sizes: half-filled last tile row / column
+    (3, 13, 21, 64, 128, 0, 2, True, False, True),     # residual + relu
+    (1, 17, 30, 128, 128, 1, 0, True, False, True),    # leaky then residual (ChengResBlock)
+    (5, 5, 3, 128, 128, 0, 1, False, True, True),      # no bias, gate multiplicand, tiny images: a tile spans images
+    (1, 1, 1, 32, 128, 0, 0, True, False, False),      # a single pixel
+    (2, 34, 60, 128, 128, 0, 0, True, False, False),
+    (1, 9, 40, 64, 256, 2, 0, True, False, False),     # c_out 256: four 64-channel blocks
+    (1, 68, 120, 128, 128, 0, 0, True, False, True),   # the 1/16-resolution shape of 1080p
+    (2, 33, 50, 64, 128, 1, 0, True, False, True),     # interior blocks (lean epilogue) + right-edge / bottom-edge blocks
+    (1, 47, 64, 32, 128, 0, 1, True, False, False),    # leaky after the (absent) residual
+    (1, 32, 48, 32, 256, 2, 0, False, False, False),   # relu, no bias
+]
+
+# the 5x5 stride-2 layers in polyphase form (ABI 17: four stride-1 3x3 convolutions of the input's phases, 49 multiplications per
+# 2x2 outputs instead of 100; include/aivc_hip.h, aivc_winograd_covers)
+POLY_CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, res
+    (1, 8, 8, 32, 128, 0, 0, True, False),
+    (2, 15, 17, 64, 128, 1, 0, True, False),     # odd input sizes: the last phase row / column clamps into the other phase's samples
+    (1, 33, 47, 64, 128, 0, 2, True, True),
+    (1, 64, 96, 64, 128, 0, 0, True, False),     # 32 x 48 outputs: 2 x 3 blocks
+    (3, 9, 7, 32, 256, 2, 0, False, False),      # four 64-channel blocks, tiny images
+    (1, 136, 240, 64, 128, 0, 0, True, True),    # 68 x 120 outputs: right-edge column, bottom block row mostly outside
+    (1, 7, 5, 128, 128, 0, 1, True, True),
+    (1, 1, 1, 32, 128, 0, 0, True, False),       # a single pixel: every tap clamps onto it
+    (2, 34, 62, 64, 128, 1, 0, True, True),
+]
+
+# the transposed 5x5 stride-2 layers class by class (ABI 17: each output parity class a stride-1 3x3 correlation of the
+# zero-extended input, 49 multiplications per 2x2 grid pixels instead of 100)
+TC_CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, res
+    (1, 8, 8, 32, 64, 0, 0, True, False),
+    (2, 7, 9, 64, 64, 1, 0, True, False),        # odd sizes: half-filled last tile row / column, zero extension on every side
+    (1, 17, 30, 128, 64, 0, 0, True, True),
+    (1, 33, 50, 128, 128, 0, 2, True, True),     # c_out 128: two channel blocks per class; interior + edge blocks
+    (3, 5, 3, 32, 128, 0, 0, False, False),      # tiny images: a block spans nothing but border
+    (1, 68, 120, 128, 64, 0, 0, True, False),    # the 1/16-resolution shape of 1080p: right-edge column
+    (1, 1, 1, 32, 64, 0, 0, True, False),
+    (2, 34, 60, 64, 128, 2, 0, True, True),
+]
+
+WINO_FORMS = {301: (3, 1, 1, abi.MODE_CONV), 302: (5, 2, 2, abi.MODE_CONV), 303: (5, 2, 0, abi.MODE_TCONV)}  # variant: k, stride, pad, mode
+
+BF16X3_CASES = [  # mode, k, stride, pad, c_in, c_out, h, w, fused gdn (0 / 1 / 2), variant with the weights split ahead, in the K loop
+    (abi.MODE_CONV, 3, 1, 1, 64, 128, 9, 11, 0, 1100, 1100),
+    (abi.MODE_CONV, 5, 2, 2, 128, 64, 13, 15, 0, 1106, 1102),
+    (abi.MODE_TCONV, 5, 2, 0, 128, 128, 5, 7, 2, 1165, 1160),
+]
+
+
+def _conv_call(names, **fixed):
+    """ops.conv2d(x, w, bias, ...) from the placed inputs: those in `names` as the keyword arguments of their name"""
+    def call(ops, d, **kw):
+        return ops.conv2d(d['x'], d['w'], d['bias'], **fixed, **{nm: d[nm] for nm in names}, **kw)
+    return call
+
+
+def conv_case(oracle, row, seed, n=2):
+    """a row of CONV_CASES: bias, two activations, gate multiplicand, residual; the GDN modes with positive gamma and beta"""
+    mode, k, s, pad, ci, co, h, w, a1, a2, use_mul, use_res = row
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, h, w, ci), dtype=np.float32)
+    wt = (rng.standard_normal((co, k, k, ci), dtype=np.float32) / np.sqrt(k * k * ci)).astype(np.float32)
+    bias = rng.standard_normal(co, dtype=np.float32)
+    if mode in (abi.MODE_GDN, abi.MODE_IGDN):
+        wt = np.abs(wt) * 0.1
+        bias = np.abs(bias) + 0.1
+    ho, wo = abi.conv_out_size(mode, h, w, k, s, pad)
+    mul = rng.standard_normal((n, ho, wo, co), dtype=np.float32) if use_mul else None
+    res = rng.standard_normal((n, ho, wo, co), dtype=np.float32) if use_res else None
+    fixed = dict(mode=mode, stride=s, pad=pad, act1=a1, act2=a2)
+    return Case({'x': x, 'w': wt, 'bias': bias, 'mul': mul, 'res': res}, _conv_call(('mul', 'res'), **fixed),
+                oracle.conv2d(x, wt, bias, mul=mul, res=res, **fixed))
+
+
+def thin_walk_case(oracle, row, seed, with_bias=True):
+    """a row of THIN_WALK_CASES over 3 images: the transposed thin output layer, leaky, with or without its bias (drawn either way)"""
+    co, k, ci, h, w = row
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((3, h, w, ci), dtype=np.float32)
+    wt = (rng.standard_normal((co, k, k, ci), dtype=np.float32) / np.sqrt(k * k * ci)).astype(np.float32)
+    bias = rng.standard_normal(co, dtype=np.float32)
+    if not with_bias:
+        bias = None
+    fixed = dict(mode=abi.MODE_TCONV, stride=2, pad=0, act1=abi.ACT_LEAKY)
+    return Case({'x': x, 'w': wt, 'bias': bias}, _conv_call((), **fixed), oracle.conv2d(x, wt, bias, **fixed))
+
+
+def _gdn_params(rng, co, floor=0.2, scale=0.05):
+    return (np.abs(rng.standard_normal(co)) + floor).astype(np.float32), (np.abs(rng.standard_normal((co, co))) * scale).astype(np.float32)
+
+
+def fused_gdn_case(oracle, row, seed):
+    """a row of FUSED_GDN_CASES: conv + (I)GDN (+ residual) in one request; want: the oracle's fused evaluation"""
+    mode, k, s, pad, ci, co, h, w, inv, use_res = row
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((2, h, w, ci), dtype=np.float32)
+    wt = (rng.standard_normal((co, k, k, ci), dtype=np.float32) / np.sqrt(k * k * ci)).astype(np.float32)
+    bias = rng.standard_normal(co, dtype=np.float32)
+    beta, gamma = _gdn_params(rng, co)
+    ho, wo = abi.conv_out_size(mode, h, w, k, s, pad)
+    res = rng.standard_normal((2, ho, wo, co), dtype=np.float32) if use_res else None
+    fixed = dict(mode=mode, stride=s, pad=pad)
+    return Case({'x': x, 'w': wt, 'bias': bias, 'beta': beta, 'gamma': gamma, 'res': res},
+                lambda ops, d, **kw: ops.conv2d(d['x'], d['w'], d['bias'], res=d['res'], gdn=(d['beta'], d['gamma'], inv), **fixed, **kw),
+                oracle.conv2d(x, wt, bias, res=res, gdn=(beta, gamma, inv), **fixed))
+
+
+def fused_tail_case(oracle, row, seed):
+    """a row of FUSED_TAIL_CASES: conv + activation + 1x1 conv (+ residual, activation) in one request; want: the oracle's two
+    convolutions, the intermediate zero padded to a multiple of 4 channels as the tail's weights are.  covered: version 2 of the
+    contract runs the 3x3 on the Winograd chain (size rule in force) and the library declines the fusion."""
+    k, s, ci, cm, ct, n, h, w, a1, a2, use_res = row
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, h, w, ci), dtype=np.float32)
+    wt = (rng.standard_normal((cm, k, k, ci), dtype=np.float32) / np.sqrt(k * k * ci)).astype(np.float32)
+    b1 = rng.standard_normal(cm, dtype=np.float32)
+    cm4 = (cm + 3) // 4 * 4
+    w3 = np.zeros((ct, 1, 1, cm4), dtype=np.float32)
+    w3[..., :cm] = rng.standard_normal((ct, 1, 1, cm), dtype=np.float32) / np.sqrt(cm)
+    b3 = rng.standard_normal(ct, dtype=np.float32)
+    ho, wo = abi.conv_out_size(abi.MODE_CONV, h, w, k, s, k // 2)
+    res = rng.standard_normal((n, ho, wo, ct), dtype=np.float32) if use_res else None
+    t = oracle.conv2d(x, wt, b1, stride=s, pad=k // 2, act1=a1)
+    if cm4 != cm:
+        t = np.concatenate([t, np.zeros(t.shape[:3] + (cm4 - cm,), np.float32)], axis=-1)
+    fixed = dict(stride=s, pad=k // 2, act1=a1, act2=a2)
+    return Case({'x': x, 'w': wt, 'bias': b1, 'w3': w3, 'b3': b3, 'res': res},
+                lambda ops, d, **kw: ops.conv2d(d['x'], d['w'], d['bias'], res=d['res'], tail=(d['w3'], d['b3']), **fixed, **kw),
+                oracle.conv2d(t, w3, b3, res=res, act2=a2), fixed=fixed,
+                covered=k == 3 and s == 1 and ci % 32 == 0 and cm % 128 == 0 and h * w >= 8000)
+
+
+def gdn_resident_case(oracle, row, with_oracle=True):
+    """a row of GDN_RESIDENT_CASES: the stand-alone (I)GDN; want is None where the test leaves the CPU oracle out (large sizes)"""
+    c, n, h, w, inv, use_res = row
+    rng = np.random.default_rng(c * 1000 + n * 100 + h + w + (5 if inv else 0))
+    x = rng.standard_normal((n, h, w, c), dtype=np.float32)
+    beta, gamma = _gdn_params(rng, c)
+    res = rng.standard_normal((n, h, w, c), dtype=np.float32) if use_res else None
+    return Case({'x': x, 'beta': beta, 'gamma': gamma, 'res': res},
+                lambda ops, d, **kw: ops.gdn(d['x'], d['beta'], d['gamma'], inverse=inv, res=d['res'], **kw),
+                oracle.gdn(x, beta, gamma, inverse=inv, res=res) if with_oracle else None)
+
+
+def wino_case(oracle, variant, row, seed):
+    """a row of WINO_CASES (variant 301), POLY_CASES (302) or TC_CASES (303, weights scaled for its 4 classes); the 5x5 tables have
+    no gate multiplicand.  Needs version 2 of the contract with the size rule lifted on both sides (the tests' fixture)."""
+    n, h, w, ci, co, a1, a2, has_b, has_m, has_r = row if len(row) == 10 else row[:8] + (False, row[8])
+    k, s, pad, mode = WINO_FORMS[variant]
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, h, w, ci)).astype(np.float32)
+    wt = (rng.standard_normal((co, k, k, ci)) / np.sqrt(k * k * ci / (4 if mode == abi.MODE_TCONV else 1))).astype(np.float32)
+    b = (rng.standard_normal(co) * 0.1).astype(np.float32) if has_b else None
+    ho, wo = abi.conv_out_size(mode, h, w, k, s, pad)
+    m = rng.standard_normal((n, ho, wo, co)).astype(np.float32) if has_m else None
+    r = rng.standard_normal((n, ho, wo, co)).astype(np.float32) if has_r else None
+    fixed = dict(mode=mode, stride=s, pad=pad, act1=a1, act2=a2)
+    return Case({'x': x, 'w': wt, 'bias': b, 'mul': m, 'res': r}, _conv_call(('mul', 'res'), **fixed),
+                oracle.conv2d(x, wt, b, mul=m, res=r, **fixed))
+
+
+def wino_weights_case(oracle, form, c_in):
+    """the U image of a [64, k, k, c_in] weight in the form '3x3', 'poly5' or 'tconv5', flat"""
+    k = 3 if form == '3x3' else 5
+    wt = (np.random.default_rng(100 + c_in + k).standard_normal((64, k, k, c_in)) * 3).astype(np.float32)
+    tr = form == 'tconv5'
+    want = np.asarray(oracle.winograd_weights(wt, transposed=tr)).ravel()
+    assert want.size == 64 * 16 * c_in * (1 if form == '3x3' else 4)
+    return Case({'w': wt}, lambda ops, d: ops.winograd_weights(d['w'], transposed=tr), want)
+
+
+def bf16x3_case(row, seed):
+    """a row of BF16X3_CASES.  The precision mode has no oracle (its bits are its own): want is for the test to set, from a run
+    of the same launch that it trusts"""
+    mode, k, s, pad, ci, co, h, w, gdn = row[:9]
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((2, h, w, ci), dtype=np.float32)
+    wt = (rng.standard_normal((co, k, k, ci), dtype=np.float32) / np.sqrt(k * k * ci)).astype(np.float32)
+    b = rng.standard_normal(co, dtype=np.float32)
+    beta, gamma = _gdn_params(rng, co, 0.5, 0.02)
+
+    def call(ops, d):
+        g = (d['beta'], d['gamma'], gdn == 2) if gdn else None
+        return ops.conv2d(d['x'], d['w'], d['bias'], mode=mode, stride=s, pad=pad, gdn=g)
+    return Case({'x': x, 'w': wt, 'bias': b, 'beta': beta, 'gamma': gamma}, call, None)
+
+
+def mfma_tile_case(oracle, seed, c_in):
+    """M = 2 * 9 * 13 = 234 rows and 72 output channels (multiples of no tile side): partial tiles along both; 3x3, leaky, residual"""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((2, 9, 13, c_in), dtype=np.float32)
+    wt = (rng.standard_normal((72, 3, 3, c_in), dtype=np.float32) / np.sqrt(9 * c_in)).astype(np.float32)
+    b = rng.standard_normal(72, dtype=np.float32)
+    res = rng.standard_normal((2, 9, 13, 72), dtype=np.float32)
+    fixed = dict(stride=1, pad=1, act1=abi.ACT_LEAKY)
+    return Case({'x': x, 'w': wt, 'bias': b, 'res': res}, _conv_call(('res',), **fixed), oracle.conv2d(x, wt, b, res=res, **fixed))
+
+
+# ---- conv_images and pack_images -------------------------------------------------------------------------------------------------
+def _image_sources(rng, n, h, w, zero_pad, with_f3):
+    """'a', 'b': 8-bit 4:2:0 planes; 'f': a float source of 4 channels (the pad channel zero or not); 'f3': one of 3, drawn last"""
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+
+    def planes():
+        return {'y': rng.integers(0, 256, (n, h, w), dtype=np.uint8), 'u': rng.integers(0, 256, (n, hc, wc), dtype=np.uint8),
+                'v': rng.integers(0, 256, (n, hc, wc), dtype=np.uint8)}
+    src = {'a': planes(), 'b': planes(), 'f': rng.standard_normal((n, h, w, 4)).astype(np.float32), None: None}
+    if zero_pad:
+        src['f'][..., 3] = 0.0
+    if with_f3:
+        src['f3'] = rng.standard_normal((n, h, w, 3)).astype(np.float32)
+    return src
+
+
+def conv_images_cases(oracle, h, w, n, use_gdn, part_lists):
+    """the first analysis layer (5x5 stride 2 -> 64, GDN or leaky) on every list of image sources in part_lists (names of
+    _image_sources), weights drawn per list from one stream: call(ops, d) runs it from an ops.ImageStack, which the fused kernel
+    must take (no packed tensor); call(ops, d, packed=True) is the pack + conv pair it replaces"""
+    rng = np.random.default_rng(h * 1000 + w + (7 if use_gdn else 0))
+    src = _image_sources(rng, n, h, w, True, any('f3' in pl for pl in part_lists))
+    act1 = 0 if use_gdn else abi.ACT_LEAKY
+    cases = []
+    for pl in part_lists:
+        parts = [src[nm] for nm in pl]
+        ni = len(parts)
+        wt = np.zeros((64, 5, 5, 4 * ni), np.float32)
+        for i in range(ni):
+            wt[..., 4 * i:4 * i + 3] = rng.standard_normal((64, 5, 5, 3)).astype(np.float32) / np.sqrt(75 * ni)
+        bias = rng.standard_normal(64, dtype=np.float32)
+        beta, gamma = _gdn_params(rng, 64) if use_gdn else (None, None)
+
+        def call(ops, d, packed=False):
+            dev = d['w'].device
+            stack = ops.pack_images(d['parts'], h, w, dev) if packed else ops.ImageStack(d['parts'], h, w, dev)
+            got = ops.conv2d(stack, d['w'], d['bias'], stride=2, pad=2, act1=act1, gdn=(d['beta'], d['gamma'], False) if use_gdn else None)
+            assert packed or stack._packed is None, 'the fused kernel must have taken this layer (no packed tensor)'
+            return got
+        want = oracle.conv2d(oracle.pack_images(parts, h, w), wt, bias, stride=2, pad=2, act1=act1, gdn=(beta, gamma, False) if use_gdn else None)
+        cases.append(Case({'parts': parts, 'w': wt, 'bias': bias, 'beta': beta, 'gamma': gamma}, call, want, act1=act1))
+    return cases
+
+
+def pack_images_cases(oracle, h, w, n, part_lists):
+    """ops.pack_images on every list of image sources in part_lists"""
+    src = _image_sources(np.random.default_rng(h * 1000 + w), n, h, w, False, any('f3' in pl for pl in part_lists))
+
+    def call(ops, d):
+        first = next(t for t in d['parts'] if t is not None)
+        return ops.pack_images(d['parts'], h, w, (first['y'] if isinstance(first, dict) else first).device)
+    return [Case({'parts': parts}, call, oracle.pack_images(parts, h, w)) for parts in ([src[nm] for nm in pl] for pl in part_lists)]

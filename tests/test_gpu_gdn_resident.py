@@ -8,12 +8,10 @@ import pytest
 import torch
 
 from aivc_amd import abi
+from conv_cases import GDN_RESIDENT_CASES, gdn_resident_case
+from op_cases import T, on
 
 pytestmark = pytest.mark.gpu
-
-
-def T(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _variant(c, n, h, w, inverse, dev):
@@ -26,38 +24,18 @@ def _variant(c, n, h, w, inverse, dev):
     return _lib.load()['aivc_conv2d_variant'](C.byref(p))
 
 
-CASES = [
-    # c, n, h, w, inverse, res
-    (128, 1, 8, 8, False, False),      # one whole tile
-    (128, 1, 5, 7, False, False),      # one partial tile (35 of 64 rows)
-    (128, 2, 33, 31, False, True),     # 2046 pixels: 31 whole tiles + 62 rows
-    (128, 2, 33, 31, True, False),
-    (128, 1, 9, 13, True, True),
-    (64, 1, 33, 31, False, False),
-    (64, 2, 17, 19, True, True),
-    (64, 1, 3, 5, False, True),
-    (128, 3, 136, 120, False, False),  # 765 tiles: more than the 512 persistent workgroups of a 256-CU part
-    (128, 3, 136, 120, True, True),
-]
-
-
-@pytest.mark.parametrize('case', CASES)
+@pytest.mark.parametrize('case', GDN_RESIDENT_CASES)
 def test_resident_gdn_bit_exact(case, oracle, cuda):
     from aivc_amd import ops
-    c, n, h, w, inv, use_res = case
+    c, n, h, w, inv, _ = case
     assert _variant(c, n, h, w, inv, cuda) == 400  # the kernel under test takes the launch
-    rng = np.random.default_rng(c * 1000 + n * 100 + h + w + (5 if inv else 0))
-    x = rng.standard_normal((n, h, w, c), dtype=np.float32)
-    beta = (np.abs(rng.standard_normal(c)) + 0.2).astype(np.float32)
-    gamma = (np.abs(rng.standard_normal((c, c))) * 0.05).astype(np.float32)
-    res = rng.standard_normal((n, h, w, c), dtype=np.float32) if use_res else None
-    rt = None if res is None else T(res, cuda)
-    got = ops.gdn(T(x, cuda), T(beta, cuda), T(gamma, cuda), inverse=inv, res=rt)
-    generic = ops.gdn(T(x, cuda), T(beta, cuda), T(gamma, cuda), inverse=inv, res=rt, algo=abi.ALGO_MFMA)
-    assert torch.equal(got, generic)
-    if n * h * w <= 4096:  # (the CPU oracle at the large sizes: the generic kernel stands in, itself pinned above and in test_gpu_ops)
-        want = oracle.gdn(x, beta, gamma, inverse=inv, res=res)
-        np.testing.assert_array_equal(got.cpu().numpy(), want)
+    # (the CPU oracle at the large sizes: the generic kernel stands in, itself pinned here and in test_gpu_ops)
+    gc = gdn_resident_case(oracle, case, with_oracle=n * h * w <= 4096)
+    d = gc.place(on(cuda))
+    got = gc.call(ops, d)
+    assert torch.equal(got, gc.call(ops, d, algo=abi.ALGO_MFMA))
+    if gc.want is not None:
+        gc.check(got)
 
 
 @pytest.mark.parametrize('inv', [False, True])

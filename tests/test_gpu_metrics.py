@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from op_cases import metrics_case, on
+
 pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'metrics.npz'))
 CASES = list(range(int(G['n_cases'])))
@@ -23,22 +25,9 @@ def cuda():
 @pytest.mark.parametrize('h,w,ws', [(16, 16, 11), (11, 11, 11), (37, 53, 11), (9, 30, 9), (5, 7, 5), (3, 4, 3), (64, 129, 6), (2, 2, 1)])
 def test_ssim_scale_pool_and_sqerr_match_oracle(h, w, ws, cuda):
     from aivc_amd import ops
-    from oracle import metrics, oracle
-    rng = np.random.default_rng(h * 100 + w)
-    a = rng.uniform(0, 255, (3, h, w))
-    b = np.clip(a + rng.normal(0, 9, a.shape), 0, 255)
-    win = metrics.window_clic(ws, ws * 1.5 / 11)
-    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
-    ta, tb = torch.from_numpy(a).to(cuda), torch.from_numpy(b).to(cuda)
-    got = ops.ssim_means(ta, tb, win, c1, c2).cpu().numpy()
-    np.testing.assert_allclose(got, oracle.ssim_means(a, b, win, c1, c2), rtol=0, atol=1e-12)
-    for edge in (0, 1):
-        np.testing.assert_array_equal(ops.pool2x2(ta, edge).cpu().numpy(), oracle.pool2x2(a, edge))
-    se, se_ref = ops.sq_err(ta, tb).item(), oracle.sq_err(a, b)[0]
-    assert abs(se - se_ref) <= 1e-12 * se_ref
-    # integer-valued planes: the sum of squares is exact in fp64
-    ia, ib = np.rint(a), np.rint(b)
-    assert ops.sq_err(torch.from_numpy(ia).to(cuda), torch.from_numpy(ib).to(cuda)).item() == oracle.sq_err(ia, ib)[0]
+    from oracle import oracle
+    c = metrics_case(oracle, h, w, ws)
+    c.check(c.run(ops, on(cuda)))
 
 
 @pytest.mark.parametrize('i', CASES)

@@ -120,7 +120,7 @@ def test_mode_takes_the_covered_shapes_only(cuda):
 def test_wide_reference_fixtures_in_bf16x3(cuda, golden):
     """the reference's own outputs at the hot-path widths (tests/golden/wide_*.npz): the mode meets the bound the fp32
     kernels are held to (2e-5 relative to max(1, |y|)); the error of each case is printed next to the fp32 kernels'"""
-    from test_wide_golden import NAMES, _build, _run_gpu
+    from wide_cases import NAMES, build as _build, run_gpu as _run_gpu
     from aivc_amd import ops
     worst = {}
     took = set()

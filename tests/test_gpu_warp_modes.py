@@ -18,33 +18,25 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from warp_modes_cases import BICUBIC_REFERENCE_DEVIATION, CASES, INTERP, PAD, case_key, left_out  # noqa: E402
+from op_cases import BICUBIC_ATOL, warp_modes_case  # noqa: E402
+from warp_modes_cases import CASES, INTERP, PAD, case_key  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-BICUBIC_ATOL = 4 * BICUBIC_REFERENCE_DEVIATION  # 4 x 3.216e-6 (measured: 3.2160e-06, case 0_bicubic_border_0) = 1.2864e-5
-assert BICUBIC_ATOL == 4 * 3.216e-6
+assert BICUBIC_ATOL == 4 * 3.216e-6  # (measured: 3.2160e-06, case 0_bicubic_border_0) = 1.2864e-5
 
 
 @pytest.mark.parametrize('s,mode,pad,ac', CASES, ids=[case_key(*c) for c in CASES])
 def test_warp_matches_the_reference_in_every_mode(s, mode, pad, ac, cuda, golden):
     from aivc_amd.func_util.optical_flow import warp
     g = golden('warp_modes')
+    c = warp_modes_case(g, s, mode, pad, ac)
     with torch.no_grad():
         y = warp(torch.from_numpy(g['x_%d' % s]).to(cuda), torch.from_numpy(g['flow_%d' % s]).to(cuda), mode, pad, ac)
-    want = g['y_' + case_key(s, mode, pad, ac)]
-    assert y.is_cuda and tuple(y.shape) == want.shape
-    keep = np.broadcast_to(~left_out(g, s, mode, pad, ac)[:, None], want.shape)
-    got = y.cpu().numpy()
+    assert y.is_cuda and tuple(y.shape) == c.want.shape
     print('%-30s max |y - reference| = %.3e over %d values (%d left out)'
-          % (case_key(s, mode, pad, ac), np.abs(got - want)[keep].max(), keep.sum(), (~keep).sum()))
-    if mode == 'bicubic':
-        np.testing.assert_allclose(got[keep], want[keep], rtol=0, atol=BICUBIC_ATOL)
-    else:
-        np.testing.assert_allclose(got[keep], want[keep], rtol=1e-5, atol=2e-6)
-    # what the mask zeroes is zero, not small
-    gone = np.broadcast_to((g['m_' + case_key(s, mode, pad, ac)] < 0.9998)[:, None], want.shape)
-    assert (got[gone] == 0).all()
+          % (case_key(s, mode, pad, ac), np.abs(y.cpu().numpy() - c.want)[c.keep].max(), c.keep.sum(), (~c.keep).sum()))
+    c.check(y)
 
 
 def test_three_channel_frames_go_through_every_mode(cuda, golden):

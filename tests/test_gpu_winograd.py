@@ -9,39 +9,27 @@ import pytest
 import torch
 
 from aivc_amd import abi
+from conv_cases import POLY_CASES, TC_CASES, WINO_CASES, wino_case, wino_weights_case
+from op_cases import T, on, profiled
 
 pytestmark = pytest.mark.gpu
 
 
-def T(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, mul, res
-    (1, 8, 8, 32, 128, 0, 0, True, False, False),
-    (2, 7, 9, 32, 128, 1, 0, True, False, False),      # odd sizes: half-filled last tile row / column
-    (3, 13, 21, 64, 128, 0, 2, True, False, True),     # residual + relu
-    (1, 17, 30, 128, 128, 1, 0, True, False, True),    # leaky then residual (ChengResBlock)
-    (5, 5, 3, 128, 128, 0, 1, False, True, True),      # no bias, gate multiplicand, tiny images: a tile spans images
-    (1, 1, 1, 32, 128, 0, 0, True, False, False),      # a single pixel
-    (2, 34, 60, 128, 128, 0, 0, True, False, False),
-    (1, 9, 40, 64, 256, 2, 0, True, False, False),     # c_out 256: four 64-channel blocks
-    (1, 68, 120, 128, 128, 0, 0, True, False, True),   # the 1/16-resolution shape of 1080p
-    (2, 33, 50, 64, 128, 1, 0, True, False, True),     # interior blocks (lean epilogue) + right-edge / bottom-edge blocks
-    (1, 47, 64, 32, 128, 0, 1, True, False, False),    # leaky after the (absent) residual
-    (1, 32, 48, 32, 256, 2, 0, False, False, False),   # relu, no bias
-]
-
-
-def _inputs(case, seed):
-    n, h, w, ci, co, a1, a2, has_b, has_m, has_r = case
-    rng = np.random.default_rng(seed)
-    x = rng.standard_normal((n, h, w, ci)).astype(np.float32)
-    wt = (rng.standard_normal((co, 3, 3, ci)) / np.sqrt(9 * ci)).astype(np.float32)
-    b = (rng.standard_normal(co) * 0.1).astype(np.float32) if has_b else None
-    m = rng.standard_normal((n, h, w, co)).astype(np.float32) if has_m else None
-    r = rng.standard_normal((n, h, w, co)).astype(np.float32) if has_r else None
-    return x, wt, b, m, r
+def _runs_on(variant, c, cuda, next_to_version_1=True):
+    """the case's launch takes the Winograd variant and gives the oracle's bits; the 5x5 forms also sit within summation noise of
+    version 1 (the tap chains) on the same inputs"""
+    from aivc_amd import ops
+    got, variants = profiled(lambda: c.run(ops, on(cuda)))
+    assert variants == [variant], variants
+    g = got.cpu().numpy()
+    assert np.array_equal(g, c.want), float(np.abs(g - c.want).max())
+    if next_to_version_1:
+        prev = ops.set_precision('fp32')
+        try:
+            v1 = c.run(ops, on(cuda)).cpu().numpy()
+        finally:
+            ops.set_precision(prev)
+        assert np.abs(g - v1).max() <= 2e-5 * max(1.0, float(np.abs(v1).max()))
 
 
 @pytest.fixture()
@@ -55,23 +43,9 @@ def fp32w(oracle):
     oracle.set_precision(prev_o)
 
 
-@pytest.mark.parametrize('idx', range(len(CASES)))
+@pytest.mark.parametrize('idx', range(len(WINO_CASES)))
 def test_hip_equals_oracle_bit_for_bit(idx, cuda, oracle, fp32w):
-    from aivc_amd import ops
-    case = CASES[idx]
-    n, h, w, ci, co, a1, a2, _, _, _ = case
-    x, wt, b, m, r = _inputs(case, 100 + idx)
-    want = oracle.conv2d(x, wt, b, stride=1, pad=1, act1=a1, act2=a2, mul=m, res=r)
-    dv = lambda a: None if a is None else T(a, cuda)
-    ops.PROFILE = []
-    try:
-        got = ops.conv2d(dv(x), dv(wt), dv(b), stride=1, pad=1, act1=a1, act2=a2, mul=dv(m), res=dv(r))
-        torch.cuda.synchronize()
-        variants = [pr[0] for pr in ops.PROFILE]
-    finally:
-        ops.PROFILE = None
-    assert variants == [301], variants
-    assert np.array_equal(got.cpu().numpy(), want), (case, float(np.abs(got.cpu().numpy() - want).max()))
+    _runs_on(301, wino_case(oracle, 301, WINO_CASES[idx], 100 + idx), cuda, next_to_version_1=False)
 
 
 def test_weight_transform_equals_oracle(cuda, oracle):
@@ -222,8 +196,7 @@ def test_wide_reference_fixtures_in_version_2(cuda, golden):
     """the reference's own outputs at the hot-path widths (tests/golden/wide_*.npz: CustomConvLayer 3x3 128 -> 128 + GDN, the
     ChengResBlocks, the attention modules ...) with the covered layers on Winograd chains (size rule lifted: the fixtures are
     small): version 2 meets the bound the version 1 kernels are held to (2e-5 relative to max(1, |y|)); printed side by side"""
-    from test_wide_golden import NAMES, _build, _run_gpu
-    from wide_cases import WINO_VARIANTS
+    from wide_cases import NAMES, WINO_VARIANTS, build as _build, run_gpu as _run_gpu
     from aivc_amd import ops
     worst, took = {}, {}
     for name in NAMES:
@@ -249,50 +222,9 @@ def test_wide_reference_fixtures_in_version_2(cuda, golden):
     assert max(e[1] for e in worst.values()) <= 2e-5, worst
 
 
-# ---- the 5x5 stride-2 layers in polyphase form (ABI 17: four stride-1 3x3 convolutions of the input's phases, 49 multiplications per
-# 2x2 outputs instead of 100; include/aivc_hip.h, aivc_winograd_covers) -------------------------------------------------------------
-POLY_CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, res
-    (1, 8, 8, 32, 128, 0, 0, True, False),
-    (2, 15, 17, 64, 128, 1, 0, True, False),     # odd input sizes: the last phase row / column clamps into the other phase's samples
-    (1, 33, 47, 64, 128, 0, 2, True, True),
-    (1, 64, 96, 64, 128, 0, 0, True, False),     # 32 x 48 outputs: 2 x 3 blocks
-    (3, 9, 7, 32, 256, 2, 0, False, False),      # four 64-channel blocks, tiny images
-    (1, 136, 240, 64, 128, 0, 0, True, True),    # 68 x 120 outputs: right-edge column, bottom block row mostly outside
-    (1, 7, 5, 128, 128, 0, 1, True, True),
-    (1, 1, 1, 32, 128, 0, 0, True, False),       # a single pixel: every tap clamps onto it
-    (2, 34, 62, 64, 128, 1, 0, True, True),
-]
-
-
 @pytest.mark.parametrize('idx', range(len(POLY_CASES)))
 def test_polyphase_5x5_stride_2_hip_equals_oracle_bit_for_bit(idx, cuda, oracle, fp32w):
-    from aivc_amd import ops
-    n, h, w, ci, co, a1, a2, has_b, has_r = POLY_CASES[idx]
-    rng = np.random.default_rng(500 + idx)
-    x = rng.standard_normal((n, h, w, ci)).astype(np.float32)
-    wt = (rng.standard_normal((co, 5, 5, ci)) / np.sqrt(25 * ci)).astype(np.float32)
-    b = (rng.standard_normal(co) * 0.1).astype(np.float32) if has_b else None
-    ho, wo = abi.conv_out_size(abi.MODE_CONV, h, w, 5, 2, 2)
-    r = rng.standard_normal((n, ho, wo, co)).astype(np.float32) if has_r else None
-    want = oracle.conv2d(x, wt, b, stride=2, pad=2, act1=a1, act2=a2, res=r)
-    dv = lambda a: None if a is None else T(a, cuda)
-    ops.PROFILE = []
-    try:
-        got = ops.conv2d(dv(x), dv(wt), dv(b), stride=2, pad=2, act1=a1, act2=a2, res=dv(r))
-        torch.cuda.synchronize()
-        variants = [pr[0] for pr in ops.PROFILE]
-    finally:
-        ops.PROFILE = None
-    assert variants == [302], variants
-    g = got.cpu().numpy()
-    assert np.array_equal(g, want), (POLY_CASES[idx], float(np.abs(g - want).max()))
-    # and within summation noise of version 1 (the tap chain) on the same inputs
-    prev = ops.set_precision('fp32')
-    try:
-        v1 = ops.conv2d(dv(x), dv(wt), dv(b), stride=2, pad=2, act1=a1, act2=a2, res=dv(r)).cpu().numpy()
-    finally:
-        ops.set_precision(prev)
-    assert np.abs(g - v1).max() <= 2e-5 * max(1.0, float(np.abs(v1).max()))
+    _runs_on(302, wino_case(oracle, 302, POLY_CASES[idx], 500 + idx), cuda)
 
 
 @pytest.mark.parametrize('c_in', [8, 32])  # one and four chunks of 8 channels per phase / class
@@ -300,13 +232,9 @@ def test_polyphase_5x5_stride_2_hip_equals_oracle_bit_for_bit(idx, cuda, oracle,
 def test_each_weight_transform_form_equals_oracle_at_the_smallest_shapes(form, c_in, cuda, oracle):
     """The three forms share one kernel body: every form's U image, bit for bit, at the smallest c_out the entry points accept."""
     from aivc_amd import ops
-    k = 3 if form == '3x3' else 5
-    w = (np.random.default_rng(100 + c_in + k).standard_normal((64, k, k, c_in)) * 3).astype(np.float32)
-    tr = form == 'tconv5'
-    u = ops.winograd_weights(T(w, cuda), transposed=tr).cpu().numpy()
-    want = oracle.winograd_weights(w, transposed=tr)
-    assert u.size == want.size == 64 * 16 * c_in * (1 if form == '3x3' else 4)
-    assert np.array_equal(u.ravel(), np.asarray(want).ravel())
+    c = wino_weights_case(oracle, form, c_in)
+    u = c.check(c.run(ops, on(cuda)))
+    assert u.numel() == c.want.size == 64 * 16 * c_in * (1 if form == '3x3' else 4)
 
 
 def test_polyphase_weight_transform_equals_oracle(cuda, oracle):
@@ -365,47 +293,9 @@ def test_polyphase_fused_gdn_request_is_two_launches_with_the_oracle_bits(cuda, 
     assert np.array_equal(got.cpu().numpy(), want)
 
 
-# ---- the transposed 5x5 stride-2 layers class by class (ABI 17: each output parity class a stride-1 3x3 correlation of the
-# zero-extended input, 49 multiplications per 2x2 grid pixels instead of 100) ---------------------------------------------------------
-TC_CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, res
-    (1, 8, 8, 32, 64, 0, 0, True, False),
-    (2, 7, 9, 64, 64, 1, 0, True, False),        # odd sizes: half-filled last tile row / column, zero extension on every side
-    (1, 17, 30, 128, 64, 0, 0, True, True),
-    (1, 33, 50, 128, 128, 0, 2, True, True),     # c_out 128: two channel blocks per class; interior + edge blocks
-    (3, 5, 3, 32, 128, 0, 0, False, False),      # tiny images: a block spans nothing but border
-    (1, 68, 120, 128, 64, 0, 0, True, False),    # the 1/16-resolution shape of 1080p: right-edge column
-    (1, 1, 1, 32, 64, 0, 0, True, False),
-    (2, 34, 60, 64, 128, 2, 0, True, True),
-]
-
-
 @pytest.mark.parametrize('idx', range(len(TC_CASES)))
 def test_transposed_5x5_stride_2_hip_equals_oracle_bit_for_bit(idx, cuda, oracle, fp32w):
-    from aivc_amd import ops
-    n, h, w, ci, co, a1, a2, has_b, has_r = TC_CASES[idx]
-    rng = np.random.default_rng(700 + idx)
-    x = rng.standard_normal((n, h, w, ci)).astype(np.float32)
-    wt = (rng.standard_normal((co, 5, 5, ci)) / np.sqrt(6.25 * ci)).astype(np.float32)
-    b = (rng.standard_normal(co) * 0.1).astype(np.float32) if has_b else None
-    r = rng.standard_normal((n, 2 * h, 2 * w, co)).astype(np.float32) if has_r else None
-    want = oracle.conv2d(x, wt, b, mode=abi.MODE_TCONV, stride=2, act1=a1, act2=a2, res=r)
-    dv = lambda a: None if a is None else T(a, cuda)
-    ops.PROFILE = []
-    try:
-        got = ops.conv2d(dv(x), dv(wt), dv(b), mode=abi.MODE_TCONV, stride=2, act1=a1, act2=a2, res=dv(r))
-        torch.cuda.synchronize()
-        variants = [pr[0] for pr in ops.PROFILE]
-    finally:
-        ops.PROFILE = None
-    assert variants == [303], variants
-    g = got.cpu().numpy()
-    assert np.array_equal(g, want), (TC_CASES[idx], float(np.abs(g - want).max()))
-    prev = ops.set_precision('fp32')  # within summation noise of version 1 (the tap chains of the classes)
-    try:
-        v1 = ops.conv2d(dv(x), dv(wt), dv(b), mode=abi.MODE_TCONV, stride=2, act1=a1, act2=a2, res=dv(r)).cpu().numpy()
-    finally:
-        ops.set_precision(prev)
-    assert np.abs(g - v1).max() <= 2e-5 * max(1.0, float(np.abs(v1).max()))
+    _runs_on(303, wino_case(oracle, 303, TC_CASES[idx], 700 + idx), cuda)
 
 
 def test_transposed_weight_transform_equals_oracle(cuda, oracle):

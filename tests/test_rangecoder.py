@@ -2,6 +2,8 @@
 against an independent pure-Python big-integer implementation and closed-loop identity."""
 import numpy as np
 
+from op_cases import FORCED, forced_case
+
 
 def py_encode(lo_hi):
     """Reference-free arithmetic coder with exact rational intervals, emitting the same bits a
@@ -99,15 +101,6 @@ def test_windows_twin_matches_full_rows(oracle):
     np.testing.assert_array_equal(win, rows[:, abi.CDF_WIN0:abi.CDF_WIN0 + abi.CDF_WIN])
     n = 2 * 35
     np.testing.assert_array_equal(oracle.range_decode_windows(payload, win, sp, n), oracle.range_decode(payload, rows, n))
-
-
-FORCED = [-256, -255, -33, -32, 30, 31, 32, 254, 255, 256]  # symbols 0, 1, 223, 224, 286, 287, 288, 510, 511, 512
-
-
-def forced_case(sigma, repeat=7):
-    """a stream that visits the edges of the decoder's window, of the alphabet and of the last octet, at one sigma"""
-    q = np.array((FORCED + [0, 1, -1]) * repeat, np.int16).reshape(1, 1, -1, 1)
-    return np.full(q.shape, sigma, np.float32), q
 
 
 def test_symbol_512_and_window_edges(oracle):

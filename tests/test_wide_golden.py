@@ -16,25 +16,10 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 import wide_cases
+from wide_cases import NAMES, build as _build, run_gpu as _run_gpu
 from oracle import spec as ospec
-
-NAMES = [c[0] for c in wide_cases.CASES]
-
-
-def _build(name):
-    """the aivc_amd module of a case with the seeded parameters loaded -> (module, input, fixture sha check)"""
-    from aivc_amd.layers.misc import attention, custom_conv_layers as ccl
-    _, build, kw, _, _, _, _ = wide_cases.CASE[name]
-    if build == 'first_layer':
-        m = ccl.CustomConvLayer(k_size=5, in_ft=3 * kw['n_img'], out_ft=64, non_linearity='gdn', conv_stride=2)
-    else:
-        m = (getattr(attention, build, None) or getattr(ccl, build))(**kw)
-    x, sha = wide_cases.load_seeded(m.eval(), name)
-    return m, x, sha
-
 
 def _close(y, ref, tol=2e-5):
     err = np.abs(y - ref) / np.maximum(1.0, np.abs(ref))
@@ -64,26 +49,6 @@ def test_oracle_matches_reference_at_hot_path_widths(name, oracle, golden):
 
 
 # ---- GPU half -------------------------------------------------------------------------------------------------------
-def _run_gpu(m, x, cuda):
-    """-> (NCHW numpy output, set of kernel variants the launches took)"""
-    from aivc_amd import ops
-    m = m.to(cuda)
-    ops.PROFILE = []
-    try:
-        with torch.no_grad():
-            if isinstance(x, list):
-                h, w = x[0]['y'].shape[1:]
-                parts = [{k: torch.from_numpy(p[k]).to(cuda) for k in 'yuv'} for p in x]
-                y = ops.to_nchw_view(m.forward_nhwc(ops.ImageStack(parts, h, w, cuda)))
-            else:
-                y = m(torch.from_numpy(x).to(cuda))
-        torch.cuda.synchronize()
-        variants = {rec[0] for rec in ops.PROFILE}
-    finally:
-        ops.PROFILE = None
-    return y.cpu().numpy(), variants
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('name', NAMES)
 def test_gpu_wide_layer_matches_reference_on_the_bench_kernels(name, cuda, golden):

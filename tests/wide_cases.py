@@ -123,3 +123,39 @@ def load_seeded(module, name):
     missing, unexpected = module.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
     assert not missing and not unexpected
     return x, digest(params, x)
+
+
+NAMES = [c[0] for c in CASES]
+
+
+def build(name):
+    """the aivc_amd module of a case with the seeded parameters loaded -> (module, input, fixture sha check)"""
+    from aivc_amd.layers.misc import attention, custom_conv_layers as ccl
+    _, kind, kw, _, _, _, _ = CASE[name]
+    if kind == 'first_layer':
+        m = ccl.CustomConvLayer(k_size=5, in_ft=3 * kw['n_img'], out_ft=64, non_linearity='gdn', conv_stride=2)
+    else:
+        m = (getattr(attention, kind, None) or getattr(ccl, kind))(**kw)
+    x, sha = load_seeded(m.eval(), name)
+    return m, x, sha
+
+
+def run_gpu(m, x, cuda):
+    """-> (NCHW numpy output, set of kernel variants the launches took)"""
+    import torch
+    from aivc_amd import ops
+    m = m.to(cuda)
+    ops.PROFILE = []
+    try:
+        with torch.no_grad():
+            if isinstance(x, list):
+                h, w = x[0]['y'].shape[1:]
+                parts = [{k: torch.from_numpy(p[k]).to(cuda) for k in 'yuv'} for p in x]
+                y = ops.to_nchw_view(m.forward_nhwc(ops.ImageStack(parts, h, w, cuda)))
+            else:
+                y = m(torch.from_numpy(x).to(cuda))
+        torch.cuda.synchronize()
+        variants = {rec[0] for rec in ops.PROFILE}
+    finally:
+        ops.PROFILE = None
+    return y.cpu().numpy(), variants

@@ -39,6 +39,61 @@ def _unstack(planes, n):
     return [{k: planes[k][i:i + 1] for k in 'yuv'} for i in range(n)]
 
 
+def make_data_dim(h, w, dim_y, dim_z):
+    return {'x': (h, w), 'y': dim_y, 'z': dim_z, 'x_uv': ((h + 1) // 2, (w + 1) // 2)}
+
+
+def _refs444(prev, nxt, frame_type):
+    """the references of P / B frames (planar 4:2:0) as NHWC [n,h,w,4] (y,u,v,0); zeros where there is no next one"""
+    prev444 = ops.yuv420_to_444(prev['y'], prev['u'], prev['v'], c_store=4)
+    if frame_type != FRAME_B:
+        return prev444, torch.zeros_like(prev444)
+    return prev444, ops.yuv420_to_444(nxt['y'], nxt['u'], nxt['v'], c_store=4)
+
+
+def _pend_sections(net, a, sections, k):
+    """queue the z and y streams of one network's analyse result as sections k, k + 1 of every frame of the batch"""
+    for i, (sz, sy) in enumerate(zip(net.ac.pend_z(a['q_z']), net.ac.pend_y(a['q_y'], a['sigma']))):
+        sections[i][k], sections[i][k + 1] = sz, sy
+
+
+# ---- the plan of one dependency level: which frames, in which batches, on which rank, and what the ranks of a group
+# exchange afterwards.  FrameCodec.encode_units / decode_units and the generic drivers of aivc_amd.parallel (which the
+# CPU tests run over gloo) all walk it through these functions: every rank of a group sees the same levels, frame types
+# (sorted) and frames in the same order, which is what keeps their collectives paired.
+def frame_types(gop, frames):
+    return sorted({gop[f]['type'] for f in frames})
+
+
+def level_items(gop, level, unit_ids, ftype):
+    """[(unit, frame name), ...] of one frame type in a level: unit-major, then the level's order"""
+    return [(u, f) for u in unit_ids for f in level if gop[f]['type'] == ftype]
+
+
+def level_batches(gop, level, unit_ids, max_batch, shard=None):
+    """(frame type, [(unit, frame name), ...]) batches of at most max_batch same-type frames of one
+    dependency level (a level of a chained GOP mixes P and B frames); with a shard, this rank's share."""
+    for ftype in frame_types(gop, level):
+        items = level_items(gop, level, unit_ids, ftype)
+        if shard is not None:
+            items = shard.mine(items)
+        for s in range(0, len(items), max_batch):
+            yield ftype, items[s:s + max_batch]
+
+
+def share_level(shard, rec, gop, level, unit_ids, h, w, device):
+    """Every rank of the group has written the reconstructions of ITS frames of the level into rec[unit][frame]; one
+    exchange per frame type fills in those of its peers (they are the references of the next levels).  A collective:
+    all ranks of the group call it for a level, or none does."""
+    if shard is None or shard.R == 1:
+        return
+    for ftype in frame_types(gop, level):
+        every = level_items(gop, level, unit_ids, ftype)
+        got = shard.exchange_frames(every, [rec[u][f] for u, f in shard.mine(every)], h, w, device)
+        for (u, f), r in zip(every, got):
+            rec[u][f] = r
+
+
 class FrameCodec:
     """max_batch bounds how many frames of one dependency level are pushed through the transforms
     together (activations of a 1080p frame at 1/2 resolution are 133 MB per 64-channel tensor; 16 frames
@@ -62,21 +117,6 @@ class FrameCodec:
             if getattr(net, 'ac', None) is not None:
                 net.ac.flag_md5sum = bool(flag_md5sum)
 
-    # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def to444(planes, out=None, c_off=0):
-        """planar 4:2:0 -> 4 stored channels (y,u,v,0) of an NHWC tensor (a fresh [n,h,w,4] one, or
-        channels c_off..c_off+3 of `out`)"""
-        return ops.yuv420_to_444(planes['y'], planes['u'], planes['v'], c_store=4, c_off=c_off, out=out)
-
-    @staticmethod
-    def _images(parts, h, w, device):
-        """Concatenation of 3-channel images, each padded to 4 stored channels (layout of aivc_pack_images):
-        parts are plane dicts (converted), NHWC [n,h,w,4] float tensors (first 3 channels copied) or
-        None (zeros).  The result carries the stored position of every real channel for the first conv."""
-        # lazy: the first conv reads the sources itself (aivc_conv_images); packed only if a layer cannot
-        return ops.ImageStack(parts, h, w, device)
-
     def encode_batch(self, cur, prev, nxt, frame_type, idx_rate=0., want_aux=False, on_sections=None, want_rec=True):
         """Encode n frames of the same type together.  cur/prev/nxt: lists of uint8 plane dicts
         (prev/nxt ignored where the frame type has no such reference).
@@ -97,34 +137,37 @@ class FrameCodec:
         if frame_type != FRAME_I:
             prev_p = _stack(prev)
             next_p = _stack(nxt) if frame_type == FRAME_B else None
-            prev444 = self.to444(prev_p)
-            next444 = self.to444(next_p) if next_p is not None else torch.zeros_like(prev444)
-            a = self.mof.analyse(self._images((cur_p, prev_p, next_p), h, w, dev), frame_type, idx_rate)
-            short_in = self._images((prev_p, next_p), h, w, dev) if frame_type == FRAME_B else None
-            for i, (sz, sy) in enumerate(zip(self.mof.ac.pend_z(a['q_z']), self.mof.ac.pend_y(a['q_y'], a['sigma']))):
-                sections[i][0], sections[i][1] = sz, sy
-            mof_out = self.mof.synthesise(a['y_hat'], short_in)
-            wb = ops.warp_blend(mof_out, prev444, next444, h, w, frame_type, co=4, want_aux=want_aux)
-            pred, skip = wb['pred'], wb['skip']
-            pred._aivc_cmap = (0, 1, 2)  # 3 real channels + a zero pad channel
+            # lazy stacks of 3-channel images: the first conv reads the sources itself (aivc_conv_images); they are packed
+            # only if a layer cannot
+            a = self.mof.analyse(ops.ImageStack((cur_p, prev_p, next_p), h, w, dev), frame_type, idx_rate)
+            _pend_sections(self.mof, a, sections, 0)
+            pred, skip, wb = self._predict(a['y_hat'], prev_p, next_p, frame_type, h, w, want_aux)
             if want_aux:
                 aux.update(alpha=wb['alpha'], beta=wb['beta'], warping=wb['x_warp'][..., :3])
-        c = self.cod.analyse(self._images((cur_p, pred), h, w, dev), frame_type, idx_rate)
-        for i, (sz, sy) in enumerate(zip(self.cod.ac.pend_z(c['q_z']), self.cod.ac.pend_y(c['q_y'], c['sigma']))):
-            sections[i][2], sections[i][3] = sz, sy
+        c = self.cod.analyse(ops.ImageStack((cur_p, pred), h, w, dev), frame_type, idx_rate)
+        _pend_sections(self.cod, c, sections, 2)
         if on_sections is not None:
             on_sections(sections)
-        data_dim = {'x': (h, w), 'y': c['dim_y'], 'z': c['dim_z'],
-                    'x_uv': (math.ceil(h / 2), math.ceil(w / 2))}
-        if want_rec:
-            cod_out = self.cod.synthesise(c['y_hat'], pred)
-            _, rec8 = ops.frame_to_yuv420(cod_out, h, w, skip=skip, want_float=False)
-            recs = _unstack(dict(zip('yuv', rec8)), n)
-        else:
-            recs = [None] * n
+        recs = self._reconstruct(self.cod.synthesise(c['y_hat'], pred), skip, h, w, n) if want_rec else [None] * n
         if want_aux:
             aux['code'] = ops.yuv420_to_444(cur_p['y'], cur_p['u'], cur_p['v'], c_store=3)
-        return {'sections': sections, 'rec': recs, 'data_dim': data_dim, 'aux': aux}
+        return {'sections': sections, 'rec': recs, 'data_dim': make_data_dim(h, w, c['dim_y'], c['dim_z']), 'aux': aux}
+
+    def _predict(self, y_hat_mof, prev_p, next_p, frame_type, h, w, want_aux=False):
+        """MOFNet synthesis + motion compensation of a batch of P / B frames (prev_p / next_p: their stacked references)
+        -> (prediction, skip part, everything warp_blend returned)"""
+        short_in = ops.ImageStack((prev_p, next_p), h, w, prev_p['y'].device) if frame_type == FRAME_B else None
+        mof_out = self.mof.synthesise(y_hat_mof, short_in)
+        prev444, next444 = _refs444(prev_p, next_p, frame_type)
+        wb = ops.warp_blend(mof_out, prev444, next444, h, w, frame_type, co=4, want_aux=want_aux)
+        wb['pred']._aivc_cmap = (0, 1, 2)  # 3 real channels + a zero pad channel
+        return wb['pred'], wb['skip'], wb
+
+    @staticmethod
+    def _reconstruct(cod_out, skip, h, w, n):
+        """CodecNet's output (+ the skip part) -> the n frames' 8-bit reconstructions as plane dicts"""
+        _, rec8 = ops.frame_to_yuv420(cod_out, h, w, skip=skip, want_float=False)
+        return _unstack(dict(zip('yuv', rec8)), n)
 
     # ---- one frame in row bands over the ranks of a unit group (aivc_amd/bands.py) --------------------------------
     def _band_frame(self, bands, h):
@@ -140,8 +183,7 @@ class FrameCodec:
     def _band_motion(self, bands, y_hat_mof, prev, nxt, frame_type, h, w, kf):
         """MOFNet synthesis + motion compensation in bands -> (pred band, skip band) of this rank's frame rows"""
         from .bands import Band, BandImages
-        prev444 = self.to444(prev)
-        next444 = self.to444(nxt) if frame_type == FRAME_B else torch.zeros_like(prev444)
+        prev444, next444 = _refs444(prev, nxt, frame_type)
         short_in = BandImages(bands, (prev, nxt), h, w, kf) if frame_type == FRAME_B else None
         mof_out = self.mof.synthesise(y_hat_mof, short_in, bands=bands)
         b0, b1 = bands.own(kf, h)
@@ -175,16 +217,15 @@ class FrameCodec:
         if frame_type != FRAME_I:
             nx = nxt if frame_type == FRAME_B else None
             a = self.mof.analyse(BandImages(bands, (cur, prev, nx), h, w, kf), frame_type, idx_rate, bands=bands)
-            sections[0][0], sections[0][1] = self.mof.ac.pend_z(a['q_z'])[0], self.mof.ac.pend_y(a['q_y'], a['sigma'])[0]
+            _pend_sections(self.mof, a, sections, 0)
             pred, skip = self._band_motion(bands, a['y_hat'], prev, nxt, frame_type, h, w, kf)
         c = self.cod.analyse(BandImages(bands, (cur, pred), h, w, kf), frame_type, idx_rate, bands=bands)
-        sections[0][2], sections[0][3] = self.cod.ac.pend_z(c['q_z'])[0], self.cod.ac.pend_y(c['q_y'], c['sigma'])[0]
+        _pend_sections(self.cod, c, sections, 2)
         if on_sections is not None:
             on_sections(sections)
         cod_out = self.cod.synthesise(c['y_hat'], None if pred is None else BandImages(bands, (pred,), h, w, kf), bands=bands)
         rec = self._band_reconstruct(bands, cod_out, skip, h, w, kf)
-        data_dim = {'x': (h, w), 'y': c['dim_y'], 'z': c['dim_z'], 'x_uv': (math.ceil(h / 2), math.ceil(w / 2))}
-        return {'sections': sections, 'rec': [rec], 'data_dim': data_dim, 'aux': {}}
+        return {'sections': sections, 'rec': [rec], 'data_dim': make_data_dim(h, w, c['dim_y'], c['dim_z']), 'aux': {}}
 
     def synthesise_banded(self, y_hats, prev, nxt, frame_type, data_dim, bands):
         """synthesise_batch for ONE frame in row bands (y_hats: the frame's decoded latents, on every rank)"""
@@ -276,16 +317,8 @@ class FrameCodec:
         if frame_type != FRAME_I:
             prev_p = _stack(prev)
             next_p = _stack(nxt) if frame_type == FRAME_B else None
-            prev444 = self.to444(prev_p)
-            next444 = self.to444(next_p) if next_p is not None else torch.zeros_like(prev444)
-            short_in = self._images((prev_p, next_p), h, w, prev444.device) if frame_type == FRAME_B else None
-            mof_out = self.mof.synthesise(y_hats['mof'], short_in)
-            wb = ops.warp_blend(mof_out, prev444, next444, h, w, frame_type, co=4)
-            pred, skip = wb['pred'], wb['skip']
-            pred._aivc_cmap = (0, 1, 2)
-        cod_out = self.cod.synthesise(y_hats['cod'], pred)
-        _, rec8 = ops.frame_to_yuv420(cod_out, h, w, skip=skip, want_float=False)
-        return _unstack(dict(zip('yuv', rec8)), n)
+            pred, skip, _ = self._predict(y_hats['mof'], prev_p, next_p, frame_type, h, w)
+        return self._reconstruct(self.cod.synthesise(y_hats['cod'], pred), skip, h, w, n)
 
     def decode_batch(self, frames_bytes, prev, nxt, frame_type, data_dim, idx_rate=0., device=None):
         y_hats = self.entropy_decode(frames_bytes, frame_type, data_dim, idx_rate, device)
@@ -299,9 +332,6 @@ class FrameCodec:
     # depend on earlier levels, so they are pushed through the networks as one batch and their
     # entropy streams are coded concurrently.  Frames are stored in display order in the container,
     # so this yields the same bytes as the reference's depth-first order.
-    def _side_stream(self):
-        return self._side_streams(1)[0]
-
     def _side_streams(self, k):
         """k high-priority streams for the entropy coder (few waves each, latency critical)"""
         pool = getattr(self, '_sides', None)
@@ -380,15 +410,12 @@ class FrameCodec:
             ts = self._param_list = list(self.net.parameters()) + list(self.net.buffers())
         return hash(tuple((t.data_ptr(), t._version) for t in ts))
 
-    def _chunks(self, gop, level, unit_ids, shard=None):
-        """(frame type, [(unit, frame name), ...]) batches of at most max_batch same-type frames of one
-        dependency level (a level of a chained GOP mixes P and B frames); with a shard, this rank's share."""
-        for ftype in sorted({gop[f]['type'] for f in level}):
-            items = [(u, f) for u in unit_ids for f in level if gop[f]['type'] == ftype]
-            if shard is not None:
-                items = shard.mine(items)
-            for s in range(0, len(items), self.max_batch):
-                yield ftype, items[s:s + self.max_batch]
+    def _level_work(self, shard, gop, level, unit_ids, h, w):
+        """-> (row-band context or None, this rank's batches of the level).  A banded level (_banded) is the same plan with
+        one-frame batches of EVERY frame: every rank of the group works on each of them, a band of rows each."""
+        if self._banded(shard, len(unit_ids) * len(level), h, w):
+            return shard.bands(), level_batches(gop, level, unit_ids, 1)
+        return None, level_batches(gop, level, unit_ids, self.max_batch, shard)
 
     def encode_units(self, units, gop_name, idx_rate=0., shard=None, recon='all'):
         """units: list of frame lists (display order, each len == len(GOP struct)).
@@ -426,49 +453,39 @@ class FrameCodec:
                 jobs.append((items, launch_finalize(secs, sides[k], prepared=prep,
                                                     fork_streams=sides[k + 1:] + sides[:k])))
 
+        uids = range(len(units))
+        h, w = units[0][0]['y'].shape[-2:]
         n_levels = 0
         for li, level in enumerate(coding_levels(gop)):
             n_levels = li + 1
             pending = []
-            banded = self._banded(shard, len(units) * len(level), *units[0][0]['y'].shape[-2:])
-            if banded:  # every rank of the group works on every frame of the level, a band of rows each
-                bands = shard.bands()
-                for ftype, chunk in self._chunks(gop, level, range(len(units)), None):
-                    for u, f in chunk:
-                        preps = []
-                        keep = shard.local == 0  # identical sections everywhere: the group's first rank codes them
-                        out = self.encode_banded(units[u][frame_index(f)], rec[u].get(gop[f]['prev_ref']),
-                                                 rec[u].get(gop[f]['next_ref']), ftype, idx_rate, bands,
-                                                 on_sections=(lambda secs: preps.append(prepare_finalize(secs))) if keep else None)
-                        data_dim = out['data_dim']
-                        rec[u][f] = out['rec'][0]
-                        if keep:
-                            pending.append(([(u, f)], out['sections'], preps[0]))
-            for ftype, chunk in ([] if banded else self._chunks(gop, level, range(len(units)), shard)):
+            bands, batches = self._level_work(shard, gop, level, uids, h, w)
+            # in bands the sections are identical on every rank: the group's first rank codes them
+            keep = bands is None or shard.local == 0
+            for ftype, chunk in batches:
                 # the flags of the batch start their trip to the host as soon as its latents are quantised, i.e.
                 # before its CodecNet synthesis is queued: the LAST level's range coding then runs under that level's
                 # own synthesis instead of after it (it was the exposed tail of the encoder)
                 preps = []
-                out = self.encode_batch([units[u][frame_index(f)] for u, f in chunk],
-                                        [rec[u].get(gop[f]['prev_ref']) for u, f in chunk],
-                                        [rec[u].get(gop[f]['next_ref']) for u, f in chunk], ftype, idx_rate,
-                                        on_sections=lambda secs: preps.append(prepare_finalize(secs)),
-                                        want_rec=recon == 'all' or any(f in referenced for _, f in chunk))
+                cur, prev, nxt = ([units[u][frame_index(f)] for u, f in chunk],
+                                  [rec[u].get(gop[f]['prev_ref']) for u, f in chunk],
+                                  [rec[u].get(gop[f]['next_ref']) for u, f in chunk])
+                on_secs = (lambda secs: preps.append(prepare_finalize(secs))) if keep else None
+                if bands is None:
+                    out = self.encode_batch(cur, prev, nxt, ftype, idx_rate, on_sections=on_secs,
+                                            want_rec=recon == 'all' or any(f in referenced for _, f in chunk))
+                else:
+                    out = self.encode_banded(cur[0], prev[0], nxt[0], ftype, idx_rate, bands, on_sections=on_secs)
                 data_dim = out['data_dim']
                 for (u, f), r in zip(chunk, out['rec']):
                     rec[u][f] = r
-                pending.append((chunk, out['sections'], preps[0]))
+                if keep:
+                    pending.append((chunk, out['sections'], preps[0]))
             # entropy coding runs on the side streams one level behind the transforms: the host picks the flags
             # up (and launches the range coder) only after the next level's transforms are queued, so the main
             # stream never drains on that wait
-            if split and not banded:  # every rank of the group needs this level's reconstructions before the next level
-                h, w = units[0][0]['y'].shape[-2:]
-                for ftype in sorted({gop[f]['type'] for f in level}):
-                    every = [(u, f) for u in range(len(units)) for f in level if gop[f]['type'] == ftype]
-                    got = shard.exchange_frames(every, [rec[u][f] for u, f in shard.mine(every)], h, w,
-                                                units[0][0]['y'].device)
-                    for (u, f), r in zip(every, got):
-                        rec[u][f] = r
+            if bands is None:  # every rank of the group needs this level's reconstructions before the next level
+                share_level(shard, rec, gop, level, uids, h, w, units[0][0]['y'].device)
             if waiting is not None:
                 flush(li - 1)
             waiting = pending if pending else None
@@ -558,9 +575,11 @@ class FrameCodec:
             lat, ready = {}, {}
             rr = [0]
 
-            def level_items(level, ftype):
-                items = [(i, f) for i in members for f in level if gop[f]['type'] == ftype]
-                if shard is not None and not self._banded(shard, len(members) * len(level), *data_dim['x']):
+            h, w = data_dim['x']
+
+            def my_items(level, ftype):
+                items = level_items(gop, level, members, ftype)
+                if shard is not None and not self._banded(shard, len(members) * len(level), h, w):
                     items = shard.mine(items)  # (a banded level's latents are decoded by every rank: no exchange)
                 return items
 
@@ -579,8 +598,8 @@ class FrameCodec:
                         ready[it] = evs
 
             def issue_entropy(level):
-                for ftype in sorted({gop[f]['type'] for f in level}):
-                    issue_items(ftype, level_items(level, ftype))
+                for ftype in frame_types(gop, level):
+                    issue_items(ftype, my_items(level, ftype))
 
             rec = {i: {} for i in members}
             ahead = self.entropy_lookahead
@@ -592,8 +611,8 @@ class FrameCodec:
                 # serial stream of the video is then in flight at once -- what bounds the entropy stage is its longest
                 # stream, not the number of levels times it (at high rate a 4K y stream decodes for > 0.3 s, and level
                 # by level the synthesis of every level waited for that again)
-                for ftype in sorted({gop[f]['type'] for f in names}):
-                    issue_items(ftype, [it for level in levels for it in level_items(level, ftype)])
+                for ftype in frame_types(gop, names):
+                    issue_items(ftype, [it for level in levels for it in my_items(level, ftype)])
                 ahead = len(levels)
                 yield 'entropy stage issued'  # (decode_units_begin returns here)
             else:
@@ -602,36 +621,23 @@ class FrameCodec:
             for li, level in enumerate(levels):
                 if li + ahead < len(levels):
                     issue_entropy(levels[li + ahead])
-                banded = self._banded(shard, len(members) * len(level), *data_dim['x'])
-                if banded:
-                    bands = shard.bands()
-                    for ftype, chunk in self._chunks(gop, level, members, None):
-                        for it in chunk:
-                            for ev in ready[it]:
-                                main.wait_event(ev)
-                            i, f = it
-                            rec[i][f] = self.synthesise_banded({k: (None if e is None else e[0][e[1]:e[1] + 1]) for k, e in lat[it].items()},
-                                                               rec[i].get(gop[f]['prev_ref']),
-                                                               rec[i].get(gop[f]['next_ref']), ftype, data_dim, bands)
-                            del lat[it]
-                for ftype, chunk in ([] if banded else self._chunks(gop, level, members, shard)):
+                bands, batches = self._level_work(shard, gop, level, members, h, w)
+                for ftype, chunk in batches:
                     for ev in {id(e): e for it in chunk for e in ready[it]}.values():
                         main.wait_event(ev)
                     yh = {k: (None if lat[chunk[0]][k] is None else _rows_of([lat[it][k] for it in chunk]))
                           for k in ('mof', 'cod')}
-                    dec = self.synthesise_batch(yh, [rec[i].get(gop[f]['prev_ref']) for i, f in chunk],
-                                                [rec[i].get(gop[f]['next_ref']) for i, f in chunk], ftype, data_dim)
+                    prev, nxt = ([rec[i].get(gop[f]['prev_ref']) for i, f in chunk],
+                                 [rec[i].get(gop[f]['next_ref']) for i, f in chunk])
+                    if bands is None:
+                        dec = self.synthesise_batch(yh, prev, nxt, ftype, data_dim)
+                    else:
+                        dec = [self.synthesise_banded(yh, prev[0], nxt[0], ftype, data_dim, bands)]
                     for (i, f), r in zip(chunk, dec):
                         rec[i][f] = r
                         del lat[(i, f)]
-                if shard is not None and shard.R > 1 and not banded:
-                    h, w = data_dim['x']
-                    for ftype in sorted({gop[f]['type'] for f in level}):
-                        every = [(i, f) for i in members for f in level if gop[f]['type'] == ftype]
-                        got = shard.exchange_frames(every, [rec[i][f] for i, f in shard.mine(every)], h, w,
-                                                    device or torch.device('cuda'))
-                        for (i, f), r in zip(every, got):
-                            rec[i][f] = r
+                if bands is None:
+                    share_level(shard, rec, gop, level, members, h, w, device or torch.device('cuda'))
             for i in members:
                 out[i] = [rec[i][f] for f in names]
         return out

@@ -369,6 +369,26 @@ def yuv420_to_444(y, u, v, c_store=4, c_off=0, out=None):
 _CONV_IMAGES_MAX = 2
 
 
+def _n_frames(parts):
+    return next(p['y'].shape[0] if isinstance(p, dict) else p.shape[0] for p in parts if p is not None)
+
+
+def _image_sources(parts):
+    """up to 3 image sources (plane dicts, float NHWC tensors, None) -> (frames per image, ImageSrc array, tensors to keep alive)"""
+    arr = (abi.ImageSrc * abi.MAX_IMAGES)()
+    keep = []
+    for i, p in enumerate(parts):
+        if isinstance(p, dict):
+            y, u, v = (_dev(p[k], torch.uint8, k) for k in 'yuv')
+            keep += [y, u, v]
+            arr[i].y, arr[i].u, arr[i].v = y.data_ptr(), u.data_ptr(), v.data_ptr()
+        elif p is not None:
+            f = _dev(p, torch.float32, 'image')
+            keep.append(f)
+            arr[i].f, arr[i].f_channels = f.data_ptr(), f.shape[-1]
+    return _n_frames(parts), arr, keep
+
+
 class ImageStack:
     """The concatenation of up to 3 images (each stored as 3 real channels + a zero) as the first analysis conv sees
     it -- NOT materialised: conv2d() runs aivc_conv_images straight on the sources when the kernel covers the layer,
@@ -377,7 +397,7 @@ class ImageStack:
 
     def __init__(self, parts, h, w, device):
         self.parts, self.h, self.w, self.device = list(parts), h, w, device
-        self.n = next(p['y'].shape[0] if isinstance(p, dict) else p.shape[0] for p in parts if p is not None)
+        self.n = _n_frames(parts)
         self.shape = (self.n, h, w, 4 * len(self.parts))
         self.dtype = torch.float32
         self._aivc_cmap = tuple(4 * i + c for i in range(len(self.parts)) for c in range(3))
@@ -385,18 +405,7 @@ class ImageStack:
 
     def sources(self):
         """(ImageSrc array, tensors to keep alive)"""
-        arr = (abi.ImageSrc * abi.MAX_IMAGES)()
-        keep = []
-        for i, p in enumerate(self.parts):
-            if isinstance(p, dict):
-                y, u, v = (_dev(p[k], torch.uint8, k) for k in 'yuv')
-                keep += [y, u, v]
-                arr[i].y, arr[i].u, arr[i].v = y.data_ptr(), u.data_ptr(), v.data_ptr()
-            elif p is not None:
-                f = _dev(p, torch.float32, 'image')
-                keep.append(f)
-                arr[i].f, arr[i].f_channels = f.data_ptr(), f.shape[-1]
-        return arr, keep
+        return _image_sources(self.parts)[1:]
 
     def tensor(self):
         if self._packed is None:
@@ -434,18 +443,7 @@ def pack_images(parts, h, w, device):
     """parts: up to 3 sources, each a dict of uint8 planes {'y','u','v'} ([n,h,w] / [n,ceil(h/2),ceil(w/2)]), a
     float NHWC tensor [n,h,w,c>=3] (its first 3 channels are taken) or None (zeros) -> NHWC [n,h,w,4*len(parts)]
     with every image stored as (c0, c1, c2, 0); carries the stored position of the real channels for the conv."""
-    n = next(p['y'].shape[0] if isinstance(p, dict) else p.shape[0] for p in parts if p is not None)
-    arr = (abi.ImageSrc * abi.MAX_IMAGES)()
-    keep = []
-    for i, p in enumerate(parts):
-        if isinstance(p, dict):
-            y, u, v = (_dev(p[k], torch.uint8, k) for k in 'yuv')
-            keep += [y, u, v]
-            arr[i].y, arr[i].u, arr[i].v = y.data_ptr(), u.data_ptr(), v.data_ptr()
-        elif p is not None:
-            f = _dev(p, torch.float32, 'image')
-            keep.append(f)
-            arr[i].f, arr[i].f_channels = f.data_ptr(), f.shape[-1]
+    n, arr, keep = _image_sources(parts)
     out = torch.empty((n, h, w, 4 * len(parts)), dtype=torch.float32, device=device)
     nb = n * h * w * (16 * len(parts) + sum(1.5 if isinstance(p, dict) else (12 if p is not None else 0) for p in parts))
     _hbm_profiled('pack_images', nb, lambda: call('aivc_pack_images', arr, len(parts), n, h, w, _p(out), _stream()))

@@ -122,6 +122,16 @@ def unit_owner(u, world):
     return u % world
 
 
+def _dd_ints(data_dim):
+    """frame and latent sizes as the six integers the ranks exchange (-1: this rank coded no frame and knows none)"""
+    return [-1] * 6 if data_dim is None else [int(x) for k in 'xyz' for x in data_dim[k]]
+
+
+def _dd_from_ints(v):
+    from .codec import make_data_dim
+    return make_data_dim(v[0], v[1], (v[2], v[3]), (v[4], v[5]))
+
+
 def gather_gops(local_gops, dst=0, device=None):
     """local_gops: list over ALL units with None for units coded elsewhere.  Returns the complete
     list on rank `dst` (None on the others).  Two tensor collectives (lengths, padded payload): no pickling."""
@@ -148,13 +158,11 @@ def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, id
     data_dim = enc['data_dim']
     if world > 1:  # ranks without a unit do not know the latent sizes: element-wise max of six int64
         cdev = _comm_device(None, dev)
-        v = [-1] * 6 if data_dim is None else [*data_dim['x'], *data_dim['y'], *data_dim['z']]
-        t = torch.tensor(v, dtype=torch.int64, device=cdev)
+        t = torch.tensor(_dd_ints(data_dim), dtype=torch.int64, device=cdev)
         _note('all_reduce latent sizes')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         with _host_wait('latent sizes to the host'):
-            v = [int(x) for x in t.cpu()]
-        data_dim = {'x': (v[0], v[1]), 'y': (v[2], v[3]), 'z': (v[4], v[5]), 'x_uv': ((v[0] + 1) // 2, (v[1] + 1) // 2)}
+            data_dim = _dd_from_ints([int(x) for x in t.cpu()])
     if gops is None:
         return (None, enc) if return_enc else None
     blob = frame_codec.assemble_video(dict(enc, gops=gops, data_dim=data_dim))
@@ -376,14 +384,12 @@ class ClipShard:
         if self.R == 1:
             return data_dim
         cdev = _comm_device(self.pg, self.device)
-        v = [-1] * 6 if data_dim is None else [*data_dim['x'], *data_dim['y'], *data_dim['z']]
-        t = torch.tensor(v, dtype=torch.int64, device=cdev)
+        t = torch.tensor(_dd_ints(data_dim), dtype=torch.int64, device=cdev)
         allv = torch.empty((self.R, 6), dtype=torch.int64, device=cdev)
         _note('all_gather latent sizes (group)')
         dist.all_gather_into_tensor(allv.view(-1), t, group=self.pg)
         with _host_wait('latent sizes (group) to the host'):
-            v = [int(x) for x in allv.cpu().max(dim=0).values]
-        return {'x': (v[0], v[1]), 'y': (v[2], v[3]), 'z': (v[4], v[5]), 'x_uv': ((v[0] + 1) // 2, (v[1] + 1) // 2)}
+            return _dd_from_ints([int(x) for x in allv.cpu().max(dim=0).values])
 
     # ---- across the groups ------------------------------------------------------------------------------------
     def gather_units(self, blobs_by_unit, data_dim=None):
@@ -395,12 +401,9 @@ class ClipShard:
         if self.active and self.local == 0:  # one contributor per group
             mine = dict(blobs_by_unit)
             if data_dim is not None and self.group_id == 0:
-                mine['dd'] = b''.join(int(x).to_bytes(4, 'big') for x in (*data_dim['x'], *data_dim['y'], *data_dim['z']))
+                mine['dd'] = b''.join(x.to_bytes(4, 'big') for x in _dd_ints(data_dim))
         allb = self._gather_bytes(mine, keys, None, self.world)
-        dd = None
-        if 'dd' in allb:
-            v = [int.from_bytes(allb['dd'][i:i + 4], 'big') for i in range(0, 24, 4)]
-            dd = {'x': (v[0], v[1]), 'y': (v[2], v[3]), 'z': (v[4], v[5]), 'x_uv': ((v[0] + 1) // 2, (v[1] + 1) // 2)}
+        dd = _dd_from_ints([int.from_bytes(allb['dd'][i:i + 4], 'big') for i in range(0, 24, 4)]) if 'dd' in allb else None
         return [allb[u] for u in range(self.n_units)], dd
 
 
@@ -426,12 +429,12 @@ def decode_clip(frame_codec, gop_blobs, data_dim, device=None, shard=None):
     return dict(zip(shard.units, recs))
 
 
-# ---- generic level-by-level drivers (any frame coder with encode_batch / decode_batch: the CPU tests run them
-# with the oracle behind that interface; the HIP codec has the same logic inside FrameCodec.encode_units /
-# decode_units, where it keeps the single-GPU stream scheduling) ----------------------------------------------------
+# ---- generic level-by-level drivers for any frame coder with encode_batch / decode_batch / max_batch (the CPU tests
+# run them over gloo with the oracle behind that interface).  They walk the level plan and the exchange of
+# aivc_amd.codec -- the ones FrameCodec.encode_units / decode_units walk -- without the single-GPU stream scheduling ------
 def encode_units_level_sharded(frame_codec, units, gop_name, idx_rate=0., shard=None):
     """Every rank passes the same `units` (those of its group) and returns the same (gop blobs, data_dim)."""
-    from .codec import frame_index
+    from .codec import frame_index, level_batches, share_level
     from .func_util.GOP_structure import coding_levels, generate_gop_struct
     from .real_life import cat_binary_files as container
     from .real_life import header as hdr
@@ -439,39 +442,32 @@ def encode_units_level_sharded(frame_codec, units, gop_name, idx_rate=0., shard=
     shard = shard or _whole_world_shard(units[0][0]['y'].device)
     gop = generate_gop_struct(gop_name)
     names = sorted(gop, key=frame_index)
+    uids = range(len(units))
     rec = [dict() for _ in units]
     fbytes = {}
     data_dim = None
     h, w = units[0][0]['y'].shape[-2:]
-    dev = units[0][0]['y'].device
     for level in coding_levels(gop):
-        for ftype in sorted({gop[f]['type'] for f in level}):
-            items = [(u, f) for u in range(len(units)) for f in level if gop[f]['type'] == ftype]
-            mine = shard.mine(items)
-            my_recs = []
-            for s in range(0, len(mine), frame_codec.max_batch):
-                chunk = mine[s:s + frame_codec.max_batch]
-                out = frame_codec.encode_batch([units[u][frame_index(f)] for u, f in chunk],
-                                               [rec[u].get(gop[f]['prev_ref']) for u, f in chunk],
-                                               [rec[u].get(gop[f]['next_ref']) for u, f in chunk], ftype, idx_rate)
-                data_dim = out['data_dim']
-                for it, b in zip(chunk, finalize_frames(out['sections'])):
-                    fbytes[it] = b
-                my_recs += out['rec']
-            for (u, f), rc in zip(items, shard.exchange_frames(items, my_recs, h, w, dev)):
-                rec[u][f] = rc
-    keys = [(u, f) for u in range(len(units)) for f in names]
+        for ftype, chunk in level_batches(gop, level, uids, frame_codec.max_batch, shard):
+            out = frame_codec.encode_batch([units[u][frame_index(f)] for u, f in chunk],
+                                           [rec[u].get(gop[f]['prev_ref']) for u, f in chunk],
+                                           [rec[u].get(gop[f]['next_ref']) for u, f in chunk], ftype, idx_rate)
+            data_dim = out['data_dim']
+            for (u, f), b, rc in zip(chunk, finalize_frames(out['sections']), out['rec']):
+                fbytes[(u, f)], rec[u][f] = b, rc
+        share_level(shard, rec, gop, level, uids, h, w, units[0][0]['y'].device)
+    keys = [(u, f) for u in uids for f in names]
     fbytes = shard.gather_bytes(fbytes, keys)
     data_dim = shard.agree(data_dim)
     head = hdr.gop_header_bytes(gop_name, idx_rate)
-    blobs = [container.pack_gop(head, [fbytes[(u, f)] for f in names]) for u in range(len(units))]
+    blobs = [container.pack_gop(head, [fbytes[(u, f)] for f in names]) for u in uids]
     return blobs, data_dim
 
 
 def decode_units_level_sharded(frame_codec, gop_blobs, data_dim, device=None, shard=None):
     """Like FrameCodec.decode_units for ONE GOP structure, frames of every dependency level round-robin over
     the ranks of the group; every rank returns the same reconstructions."""
-    from .codec import frame_index
+    from .codec import frame_index, level_batches, share_level
     from .func_util.GOP_structure import coding_levels, generate_gop_struct
     from .real_life import cat_binary_files as container
     device = device if device is not None else (torch.device('cuda', torch.cuda.current_device())
@@ -483,22 +479,19 @@ def decode_units_level_sharded(frame_codec, gop_blobs, data_dim, device=None, sh
         raise ValueError('decode_units_level_sharded: all units must share one GOP structure and rate index')
     gop = generate_gop_struct(gop_name)
     names = sorted(gop, key=frame_index)
+    uids = range(len(gop_blobs))
     h, w = data_dim['x']
     rec = [dict() for _ in gop_blobs]
     for level in coding_levels(gop):
-        for ftype in sorted({gop[f]['type'] for f in level}):
-            items = [(u, f) for u in range(len(gop_blobs)) for f in level if gop[f]['type'] == ftype]
-            mine = shard.mine(items)
-            my_recs = []
-            for s in range(0, len(mine), frame_codec.max_batch):
-                chunk = mine[s:s + frame_codec.max_batch]
-                my_recs += frame_codec.decode_batch([parsed[u][2][frame_index(f)] for u, f in chunk],
-                                                    [rec[u].get(gop[f]['prev_ref']) for u, f in chunk],
-                                                    [rec[u].get(gop[f]['next_ref']) for u, f in chunk], ftype, data_dim,
-                                                    idx_rate, device)
-            for (u, f), rc in zip(items, shard.exchange_frames(items, my_recs, h, w, device)):
+        for ftype, chunk in level_batches(gop, level, uids, frame_codec.max_batch, shard):
+            dec = frame_codec.decode_batch([parsed[u][2][frame_index(f)] for u, f in chunk],
+                                           [rec[u].get(gop[f]['prev_ref']) for u, f in chunk],
+                                           [rec[u].get(gop[f]['next_ref']) for u, f in chunk], ftype, data_dim,
+                                           idx_rate, device)
+            for (u, f), rc in zip(chunk, dec):
                 rec[u][f] = rc
-    return [[rec[u][f] for f in names] for u in range(len(gop_blobs))]
+        share_level(shard, rec, gop, level, uids, h, w, device)
+    return [[rec[u][f] for f in names] for u in uids]
 
 
 def _whole_world_shard(device):

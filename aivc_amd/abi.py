@@ -1,4 +1,5 @@
-"""ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h and include/aivc_hip_color.h (struct layouts, constants, prototypes).
+"""ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h and include/aivc_hip_quality.h (struct
+layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -6,7 +7,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -26,6 +27,7 @@ BALLE_PARAMS = 43
 MAX_MAPS = 256
 RC_MAX_STREAMS = 64
 RATE_LANES = 16384
+SSE_BLOCKS = 64  # include/aivc_hip_quality.h: AIVC_SSE_BLOCKS
 WINO_MIN_PIXELS = 8000  # include/aivc_hip.h: AIVC_WINO_MIN_PIXELS
 WINO_MIN_PIXELS_TCONV = 32768  # ... AIVC_WINO_MIN_PIXELS_TCONV
 
@@ -157,6 +159,12 @@ COLOR_PROTOTYPES = {
     'aivc_yuv8_to_rgb8': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f],
 }
 
+# include/aivc_hip_quality.h: device only as well (their CPU statement is numpy, tests/test_gpu_quality_stats.py)
+QUALITY_PROTOTYPES = {
+    'aivc_frame_sse_u8': [_f, _f, _f, _f, _f, _f, _i32, _i32, _i32, _f, _f],
+    'aivc_frame_aux_stats': [_f, _f, _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f],
+}
+
 
 def declare(lib, suffix=''):
     """Attach argtypes/restype for every entry of the header; raises AttributeError when the
@@ -180,7 +188,7 @@ def declare(lib, suffix=''):
         wm.argtypes = [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, C.c_void_p]
         wm.restype = C.c_int
         fns['aivc_warp_modes'] = wm
-        for name, args in COLOR_PROTOTYPES.items():
+        for name, args in list(COLOR_PROTOTYPES.items()) + list(QUALITY_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.argtypes = list(args) + [C.c_void_p]
             fn.restype = C.c_int

@@ -38,6 +38,7 @@ def main(argv=None):
     p.add_argument('-o', default='../compressed.yuv', type=str)
     p.add_argument('--rng_seed', default=666, type=int)
     p.add_argument('--cpu', action='store_true')
+    p.add_argument('--log_dir', default='', type=str, help="the encoder's per-frame table goes to <log_dir>/detailed.txt (encode.py)")
     a = p.parse_args(argv)
     gop = gop_name(a.coding_config, a.gop_size, a.intra_period)
     common = ['--model', a.model] + (['--cpu'] if a.cpu else [])
@@ -46,7 +47,7 @@ def main(argv=None):
     banner(('*' * 80).center(120))
     banner('Starting encoding'.center(120))
     enc_cli.main(['-i', a.i, '--gop', gop, '--start_frame', str(a.start_frame), '--end_frame', str(a.end_frame),
-                  '-o', a.bitstream_out] + common)
+                  '-o', a.bitstream_out] + common + (['--log_dir', a.log_dir] if a.log_dir else []))
     banner(('*' * 80).center(120))
     banner('Starting decoding'.center(120))
     status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common)

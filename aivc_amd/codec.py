@@ -148,9 +148,12 @@ class FrameCodec:
         _pend_sections(self.cod, c, sections, 2)
         if on_sections is not None:
             on_sections(sections)
-        recs = self._reconstruct(self.cod.synthesise(c['y_hat'], pred), skip, h, w, n) if want_rec else [None] * n
+        rec_p = self._reconstruct_planes(self.cod.synthesise(c['y_hat'], pred), skip, h, w) if want_rec else None
+        recs = _unstack(rec_p, n) if want_rec else [None] * n
         if want_aux:
             aux['code'] = ops.yuv420_to_444(cur_p['y'], cur_p['u'], cur_p['v'], c_store=3)
+            # the batch's planes as the kernels hold them, stacked per plane (the quality log scores them in place)
+            aux['cur_planes'], aux['rec_planes'] = cur_p, rec_p
         return {'sections': sections, 'rec': recs, 'data_dim': make_data_dim(h, w, c['dim_y'], c['dim_z']), 'aux': aux}
 
     def _predict(self, y_hat_mof, prev_p, next_p, frame_type, h, w, want_aux=False):
@@ -164,10 +167,15 @@ class FrameCodec:
         return wb['pred'], wb['skip'], wb
 
     @staticmethod
-    def _reconstruct(cod_out, skip, h, w, n):
-        """CodecNet's output (+ the skip part) -> the n frames' 8-bit reconstructions as plane dicts"""
+    def _reconstruct_planes(cod_out, skip, h, w):
+        """CodecNet's output (+ the skip part) -> the batch's 8-bit reconstructions, stacked per plane"""
         _, rec8 = ops.frame_to_yuv420(cod_out, h, w, skip=skip, want_float=False)
-        return _unstack(dict(zip('yuv', rec8)), n)
+        return dict(zip('yuv', rec8))
+
+    @classmethod
+    def _reconstruct(cls, cod_out, skip, h, w, n):
+        """... as the n frames' plane dicts"""
+        return _unstack(cls._reconstruct_planes(cod_out, skip, h, w), n)
 
     # ---- one frame in row bands over the ranks of a unit group (aivc_amd/bands.py) --------------------------------
     def _band_frame(self, bands, h):
@@ -417,7 +425,7 @@ class FrameCodec:
             return shard.bands(), level_batches(gop, level, unit_ids, 1)
         return None, level_batches(gop, level, unit_ids, self.max_batch, shard)
 
-    def encode_units(self, units, gop_name, idx_rate=0., shard=None, recon='all'):
+    def encode_units(self, units, gop_name, idx_rate=0., shard=None, recon='all', stats=None, stats_units=None):
         """units: list of frame lists (display order, each len == len(GOP struct)).
         -> ([gop bytes per unit], [reconstructions per unit], data_dim)
         recon: 'all' -- every frame is reconstructed, as the reference's encoder does (its forward pass returns x_hat
@@ -425,6 +433,12 @@ class FrameCodec:
         no other frame of the GOP structure references (the last dependency level of a random-access GOP: 16 of the 33
         frames of 1_GOP_32; the last P of a low-delay chain) skip their CodecNet synthesis and come back as None.
         Same bytes (tests/test_gpu_codec.py); single-process coding only.
+        stats (aivc_amd.quality.QualityStats, optional): the encoder's quality log.  Every level batch is then encoded
+        with want_aux and scored on the device right after its reconstruction (squared error, alpha / beta / warping
+        sums, MS-SSIM: a few launches per batch, no host synchronisation; the auxiliary tensors do not outlive the
+        batch), and the four section sizes of every frame are recorded, all under (stats_units[unit], display index) --
+        stats_units: the units' numbers in the video, default 0, 1, ...  Same bytes as without it.  Every frame must be
+        reconstructed to be scored (not with recon='refs'), by this process (not with a shard).
         shard (aivc_amd.parallel.ClipShard, optional): the frames of every dependency level are spread over the
         ranks of this process' group; each rank codes `shard.mine(items)` and the new 8-bit reconstructions are
         exchanged once per level (they are the references of the next levels).  Stream scheduling is the
@@ -443,6 +457,11 @@ class FrameCodec:
             raise ValueError("recon must be 'all' or 'refs'")
         if recon == 'refs' and shard is not None:
             raise ValueError("recon='refs' is a single-process option (the sharded paths exchange every reconstruction)")
+        if stats is not None and recon != 'all':
+            raise ValueError("a quality log scores every frame's reconstruction: stats= needs recon='all'")
+        if stats is not None and shard is not None:
+            raise ValueError('stats= is an option of unit-wise coding (the level-sharded paths spread a unit over ranks)')
+        stats_units = list(range(len(units))) if stats_units is None else list(stats_units)
         referenced = {gop[f][k] for f in gop for k in ('prev_ref', 'next_ref') if gop[f].get(k) is not None}
 
         def flush(li):
@@ -472,8 +491,10 @@ class FrameCodec:
                                   [rec[u].get(gop[f]['next_ref']) for u, f in chunk])
                 on_secs = (lambda secs: preps.append(prepare_finalize(secs))) if keep else None
                 if bands is None:
-                    out = self.encode_batch(cur, prev, nxt, ftype, idx_rate, on_sections=on_secs,
+                    out = self.encode_batch(cur, prev, nxt, ftype, idx_rate, want_aux=stats is not None, on_sections=on_secs,
                                             want_rec=recon == 'all' or any(f in referenced for _, f in chunk))
+                    if stats is not None:
+                        stats.score_batch([(stats_units[u], frame_index(f)) for u, f in chunk], out.pop('aux'))
                 else:
                     out = self.encode_banded(cur[0], prev[0], nxt[0], ftype, idx_rate, bands, on_sections=on_secs)
                 data_dim = out['data_dim']
@@ -494,6 +515,8 @@ class FrameCodec:
         for items, job in jobs:
             for (u, f), b in zip(items, job.collect()):
                 fbytes[u][f] = b
+                if stats is not None:
+                    stats.add_sections((stats_units[u], frame_index(f)), [len(sec) for sec in split_sections(b)])
             # (logging, real_life.bitstream.ESTIMATE_RATE: what the CDF bounds price this rank's streams at, and what the
             # range coder wrote for them)
             self.estimated_bits = getattr(self, 'estimated_bits', 0.0) + job.est_bits
@@ -651,11 +674,12 @@ class FrameCodec:
 
     # ------------------------------------------------------------------------------------------
     def encode_video(self, frames, gop_name, idx_starting_frame=0, idx_end_frame=None, idx_rate=0.,
-                     unit_filter=None, recon='all'):
+                     unit_filter=None, recon='all', stats=None):
         """frames[i] is the frame with absolute index idx_starting_frame + i.  The last intra-period
         unit is padded by repeating the last frame (src/model_mngt/model_management.py:142-153).
         unit_filter(u) -> bool selects the units this process codes (multi-GPU sharding); skipped
-        units come back as None in the returned list of GOP blobs."""
+        units come back as None in the returned list of GOP blobs.
+        stats: see encode_units; the rows are recorded under (unit number in the video, display index in the unit)."""
         n = len(frames)
         idx_end_frame = idx_starting_frame + n - 1 if idx_end_frame is None else idx_end_frame
         unit = len(generate_gop_struct(gop_name))
@@ -664,7 +688,7 @@ class FrameCodec:
         gops, recs, data_dim = [None] * nb_gop, [None] * nb_gop, None
         if mine:
             units = [[frames[min(u * unit + i, n - 1)] for i in range(unit)] for u in mine]
-            blobs, rr, data_dim = self.encode_units(units, gop_name, idx_rate, recon=recon)
+            blobs, rr, data_dim = self.encode_units(units, gop_name, idx_rate, recon=recon, stats=stats, stats_units=mine)
             for u, b, r in zip(mine, blobs, rr):
                 gops[u], recs[u] = b, r
         return {'gops': gops, 'recs': recs, 'data_dim': data_dim, 'nb_gop': nb_gop,

@@ -18,12 +18,15 @@ def main(argv=None):
     p.add_argument('--end_frame', default=-1, type=int)
     p.add_argument('--rng_seed', default=666, type=int)
     p.add_argument('--cpu', action='store_true')
+    p.add_argument('--log_dir', default='', type=str,
+                   help='write the per-frame table <log_dir>/detailed.txt (PSNR, rates, alpha, beta, loss, MS-SSIM) and print '
+                        'the Estimated MS-SSIM line; off by default')
     a = p.parse_args(argv)
     dev = resolve_device(a.cpu)
     model = get_model(a.model, dev)
     return encode({'model': model, 'sequence_path': a.i, 'GOP_struct': generate_gop_struct(a.gop),
                    'GOP_struct_name': a.gop, 'idx_rate': 0, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
-                   'idx_end_frame': a.end_frame})
+                   'idx_end_frame': a.end_frame, 'working_dir': a.log_dir})
 
 
 if __name__ == '__main__':

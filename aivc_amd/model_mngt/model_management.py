@@ -91,3 +91,36 @@ def infer_one_sequence(param):
         cat_one_video({'bitstream_dir': bdir, 'idx_starting_frame': first, 'idx_end_frame': last,
                        'final_bitstream_path': get_value('final_bitstream_path', param, default)})
     return seq
+
+
+# ---- the per-frame result table of a sequence (src/model_mngt/model_management.py:96-116,156-241) -----------------------------
+def lambda_tradeoff_of(model, idx_rate):
+    """the rate weight of the logged loss: model.model_param['lambda_tradeoff'][round(idx_rate)], 0.0 for a model without one"""
+    lambdas = (getattr(model, 'model_param', None) or {}).get('lambda_tradeoff')
+    return float(lambdas[int(round(idx_rate))]) if lambdas else 0.0
+
+
+def sequence_result_from_rows(rows, nb_gop, unit, idx_starting_frame, nb_frames, lambda_tradeoff=0.0):
+    """rows: {(unit number, display index): row of aivc_amd.quality} of all nb_gop x unit coded frames -> the reference's
+    sequence_result: {'frame_<index in the video>': result dictionary, ..., 'sequence': their average}, the frames in display
+    order; the frames past nb_frames are the padding of the last unit (rate counts, distortion does not)."""
+    from ..func_util.result_logging import average_N_frame, frame_result
+    seq = {}
+    for u in range(nb_gop):
+        for i in range(unit):
+            seq['frame_%d' % (u * unit + i + idx_starting_frame)] = frame_result(rows[(u, i)], lambda_tradeoff)
+    seq['sequence'] = average_N_frame(seq, nb_pad_frame=nb_gop * unit - nb_frames)
+    return seq
+
+
+def write_detailed_log(working_dir, sequence_result, sequence_name):
+    """<working_dir>/detailed.txt: the header, one row per coded frame, the sequence's average as the last line"""
+    from ..func_util.result_logging import generate_header_file, generate_log_metric_one_frame
+    os.makedirs(working_dir, exist_ok=True)
+    path = os.path.join(working_dir, 'detailed.txt')
+    with open(path, 'w') as f:
+        f.write(generate_header_file())
+        for name, res in sequence_result.items():
+            res['pic_name'], res['frame_idx'] = sequence_name, name
+            f.write(generate_log_metric_one_frame(res))
+    return path

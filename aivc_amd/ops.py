@@ -974,3 +974,72 @@ def sq_err(a, b):
     ws = _metrics_ws(1, 16, 16, a.device)
     call('aivc_sq_err', _p(a), _p(b), a.numel(), _p(ws), _p(out), _stream())
     return out
+
+
+# ---- per-frame statistics of the encoder's quality log (include/aivc_hip_quality.h) -------------------------------------
+def frame_sse_u8(src, rec):
+    """src, rec: dicts of the uint8 planes of n frames stacked per plane, 'y' [n,h,w], 'u' and 'v' [n,ceil(h/2),ceil(w/2)]
+    -> int64 CUDA tensor [n, 3]: the exact sum of (src - rec)^2 per frame and plane (y, u, v).  No sync."""
+    a = [_dev(src[k], torch.uint8, 'src ' + k) for k in 'yuv']
+    b = [_dev(rec[k], torch.uint8, 'rec ' + k) for k in 'yuv']
+    if a[0].dim() != 3:
+        raise ValueError('frame_sse_u8: expected planes [n, h, w], got %s' % (tuple(a[0].shape),))
+    n, h, w = a[0].shape
+    shapes = [(n, h, w)] + [(n, (h + 1) // 2, (w + 1) // 2)] * 2
+    if [tuple(t.shape) for t in a] != shapes or [tuple(t.shape) for t in b] != shapes:
+        raise ValueError('frame_sse_u8: planes %s against %s: expected %s'
+                         % ([tuple(t.shape) for t in a], [tuple(t.shape) for t in b], shapes))
+    partials = torch.empty((n, 3, abi.SSE_BLOCKS), dtype=torch.int64, device=a[0].device)
+    sse = torch.empty((n, 3), dtype=torch.int64, device=a[0].device)
+    _hbm_profiled('frame_sse_u8', 2 * n * (h * w + 2 * shapes[1][1] * shapes[1][2]),
+                  lambda: call('aivc_frame_sse_u8', _p(a[0]), _p(a[1]), _p(a[2]), _p(b[0]), _p(b[1]), _p(b[2]), n, h, w,
+                               _p(partials), _p(sse), _stream()))
+    return sse
+
+
+def _nhwc_store(t, c, name):
+    """t: fp32 [n,h,w,c'] holding its channels innermost with any pixel pitch (a contiguous tensor, or the leading channels of
+    one: x[..., :3]) -> (tensor whose data_ptr is pixel 0, stored channels per pixel)"""
+    if t.dim() != 4 or t.shape[-1] < c:
+        raise ValueError('%s: expected [n, h, w, >= %d channels], got %s' % (name, c, tuple(t.shape)))
+    n, h, w, _ = t.shape
+    cs = t.stride(2)
+    if t.stride(3) != 1 or cs < t.shape[-1] or t.stride(1) != w * cs or t.stride(0) != h * w * cs:
+        t = t.contiguous()
+        cs = t.shape[-1]
+    return t, cs
+
+
+def frame_aux_stats(alpha, beta, warping, code, c=3):
+    """The auxiliary outputs of a batch of n frames (FrameCodec.encode_batch(want_aux=True)): alpha, beta fp32 [n,h,w],
+    warping and code fp32 NHWC with the first c channels used (a channel slice of a wider tensor is read in place).
+    alpha / beta / warping None: an I frame's (maps of ones, ones, zeros).
+    -> float64 CUDA tensor [n, 3]: sum alpha, sum beta, sum (warping - code)^2 per frame, fixed summation order.  No sync."""
+    code = _dev_strided(code, 'code')
+    code, cs_code = _nhwc_store(code, c, 'code')
+    n, h, w, _ = code.shape
+    cs_warp = 0
+    if warping is not None:
+        warping, cs_warp = _nhwc_store(_dev_strided(warping, 'warping'), c, 'warping')
+        if tuple(warping.shape[:3]) != (n, h, w):
+            raise ValueError('frame_aux_stats: warping %s does not go with code %s' % (tuple(warping.shape), tuple(code.shape)))
+    alpha, beta = _dev(alpha, torch.float32, 'alpha'), _dev(beta, torch.float32, 'beta')
+    for t, nm in ((alpha, 'alpha'), (beta, 'beta')):
+        if t is not None and tuple(t.shape) != (n, h, w):
+            raise ValueError('frame_aux_stats: %s %s does not go with code %s' % (nm, tuple(t.shape), tuple(code.shape)))
+    lanes = torch.empty((n, 3, abi.RATE_LANES), dtype=torch.float64, device=code.device)
+    out = torch.empty((n, 3), dtype=torch.float64, device=code.device)
+    n_maps = (alpha is not None) + (beta is not None)
+    _hbm_profiled('frame_aux_stats', n * h * w * 4 * (n_maps + c * (2 if warping is not None else 1)),
+                  lambda: call('aivc_frame_aux_stats', _p(alpha), _p(beta), _p(warping), _p(code), n, h, w, int(c), int(cs_warp),
+                               int(cs_code), _p(lanes), _p(out), _stream()))
+    return out
+
+
+def _dev_strided(t, name):
+    """_dev without the copy of a non-contiguous tensor (the caller looks at the strides itself)"""
+    if not t.is_cuda:
+        raise AivcNativeError('aivc_amd.ops: %s is on %s; the HIP path needs CUDA tensors (no CPU fallback)' % (name, t.device))
+    if t.dtype != torch.float32:
+        raise AivcNativeError('aivc_amd.ops: %s has dtype %s, expected %s' % (name, t.dtype, torch.float32))
+    return t

@@ -146,12 +146,15 @@ def gather_gops(local_gops, dst=0, device=None):
     return [allb[u] for u in keys]
 
 
-def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, idx_rate=0., return_enc=False):
+def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, idx_rate=0., return_enc=False, stats=None):
     """Every rank passes the same `frames`; returns the full bitstream on rank 0 (None elsewhere); with return_enc also
-    this rank's encode_video record (its units' reconstructions, None for the others')."""
+    this rank's encode_video record (its units' reconstructions, None for the others').
+    stats (aivc_amd.quality.QualityStats): every rank scores the frames of ITS units into its own collector
+    (FrameCodec.encode_units); gather_quality_rows brings the rows together."""
     rank, world = rank_world()
+    extra = {} if stats is None else {'stats': stats}  # (any object with FrameCodec's encode_video will do without a log)
     enc = frame_codec.encode_video(frames, gop_name, idx_starting_frame, idx_rate=idx_rate,
-                                   unit_filter=lambda u: unit_owner(u, world) == rank)
+                                   unit_filter=lambda u: unit_owner(u, world) == rank, **extra)
     dev = getattr(frames[0]['y'], 'device', None)
     dev = dev if isinstance(dev, torch.device) else None
     gops = gather_gops(enc['gops'], device=dev)
@@ -167,6 +170,19 @@ def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, id
         return (None, enc) if return_enc else None
     blob = frame_codec.assemble_video(dict(enc, gops=gops, data_dim=data_dim))
     return (blob, enc) if return_enc else blob
+
+
+def gather_quality_rows(rows, keys, device=None):
+    """rows: {key: float64 array of QualityStats.ROW_LEN numbers} of the frames THIS rank scored; keys: every frame's key, in
+    the same order on all ranks -> the complete {key: row} on every rank (two tensor collectives, gather_bytes_all)."""
+    import numpy as np
+    _, world = rank_world()
+    if world == 1:
+        return dict(rows)
+    index = {k: i for i, k in enumerate(keys)}
+    got = gather_bytes_all({index[k]: np.ascontiguousarray(v, np.float64).tobytes() for k, v in rows.items()},
+                           list(range(len(keys))), None, world, device)
+    return {keys[i]: np.frombuffer(b, np.float64).copy() for i, b in got.items()}
 
 
 def decode_video_sharded(frame_codec, blob, device=None):

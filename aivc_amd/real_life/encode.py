@@ -60,14 +60,21 @@ def read_png_folder(path, first=0, last=-1, device=None):
 
 
 def encode(param):
+    """working_dir: '' (the default) -- no log; a directory -- the reference's per-frame table <working_dir>/detailed.txt
+    (func_util/result_logging.py) is written from statistics scored on the device while the frames are coded
+    (aivc_amd/quality.py), the PSNR line comes from the exact integer squared error, an `Estimated MS-SSIM` line follows it
+    and the returned dictionary gains ms_ssim_db, h, w and nb_coded_frames.  The bitstream is the same either way."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
-               'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1}
+               'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
+               'working_dir': ''}
     model = get_value('model', param, default)
     seq = get_value('sequence_path', param, default)
     gop_name = get_value('GOP_struct_name', param, default)
     final_file = get_value('final_file', param, default)
     first = get_value('idx_starting_frame', param, default)
     last = get_value('idx_end_frame', param, default)
+    working_dir = get_value('working_dir', param, default)
+    idx_rate = get_value('idx_rate', param, default)
     dev = next(model.parameters()).device
     if first > last and last != -1:
         print('ERROR: First frame index bigger than last frame index')
@@ -80,13 +87,15 @@ def encode(param):
     from .. import parallel
     fc.estimated_bits, fc.coded_payload_bytes = 0.0, 0
     rank, world = parallel.rank_world()
+    stats = None
+    if working_dir:
+        from ..quality import QualityStats
+        stats = QualityStats()
     with torch.no_grad(), bitstream.estimating_rate():  # the reference's in-band rate check (RESULT lines)
         if world > 1:  # one process per GPU: intra-period units over the ranks, the container on rank 0
-            blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=get_value('idx_rate', param, default),
-                                                      return_enc=True)
+            blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=idx_rate, return_enc=True, stats=stats)
         else:
-            enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last,
-                                  idx_rate=get_value('idx_rate', param, default))
+            enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last, idx_rate=idx_rate, stats=stats)
             blob = fc.assemble_video(enc)
         torch.cuda.synchronize()
     dt = time.time() - t0
@@ -102,6 +111,8 @@ def encode(param):
             idx = u * len(g) + i
             if idx < n:
                 mine.append((first + idx, r))
+                if stats is not None:  # (scored on the device already)
+                    continue
                 se += sum(float(((r[k].float() - frames[idx][k].float()) ** 2).sum()) for k in 'yuv')
                 cnt += sum(frames[idx][k].numel() for k in 'yuv')
     if world > 1:
@@ -109,6 +120,17 @@ def encode(param):
         t = torch.tensor([se, cnt, est_bits, payload], dtype=torch.float64, device=parallel._comm_device(None, dev))
         dist.all_reduce(t)
         se, cnt, est_bits, payload = (float(v) for v in t)
+    seq_res = None
+    if stats is not None:  # every rank scored the frames of its units: the rows travel to rank 0 (to all, in fact)
+        from ..model_mngt.model_management import lambda_tradeoff_of, sequence_result_from_rows, write_detailed_log
+        from ..func_util.GOP_structure import generate_gop_struct
+        unit = len(generate_gop_struct(gop_name))
+        keys = [(u, i) for u in range(enc['nb_gop']) for i in range(unit)]
+        rows = parallel.gather_quality_rows(stats.rows(), keys, dev)
+        if rank == 0:
+            seq_res = sequence_result_from_rows(rows, enc['nb_gop'], unit, first, n, lambda_tradeoff_of(model, idx_rate))
+            name = os.path.basename(os.path.normpath(seq))
+            write_detailed_log(working_dir, seq_res, name[:-4] if name.endswith('.yuv') else name)
     if get_value('flag_bitstream_debug', param, default):
         from .decode import debug_dir, write_debug_md5
         for idx, r in mine:  # every rank writes the digests of its own frames
@@ -123,13 +145,18 @@ def encode(param):
         dist.barrier()  # the file exists before any rank goes on (to decode it)
     if rank != 0:
         return None
-    psnr = 10 * np.log10(255.0 ** 2 / max(se / cnt, 1e-12))
+    if seq_res is None:
+        psnr = 10 * np.log10(255.0 ** 2 / max(se / cnt, 1e-12))
+    else:
+        psnr = seq_res['sequence']['psnr']
     print_log_msg('INFO', 'Encoding done', '', '')
     print_log_msg('INFO', 'Bitstream path', '', final_file)
     print_log_msg('RESULT', 'Number of frames', '[frame]', int(n))
     print_log_msg('RESULT', 'Encoding/decoding time', '[s]', '%.1f' % dt)
     print_log_msg('RESULT', 'Encoding/decoding FPS', '[frame/s]', '%.1f' % (n / dt))
     print_log_msg('RESULT', 'Estimated PSNR', '[dB]', '%.4f' % psnr)
+    if seq_res is not None:
+        print_log_msg('RESULT', 'Estimated MS-SSIM', '[dB]', '%.4f' % seq_res['sequence']['ms_ssim_db'])
     # The reference's in-band rate check (src/real_life/encode.py:140-170): the rate its entropy model ESTIMATES against
     # the bytes written.  Here the estimate is what the 16-bit CDF bounds price the coded symbols at (aivc_bounds_rate:
     # sum of -log2((c_hi - c_lo) / 2^16), what an ideal arithmetic coder would write for the same CDFs); the real rate
@@ -140,5 +167,9 @@ def encode(param):
     print_log_msg('RESULT', 'Estimated rate', '[byte]', '%.1f' % est_byte)
     print_log_msg('RESULT', 'Real rate', '[byte]', len(blob))
     print_log_msg('RESULT', 'Estimated rate overhead', '[%]', '%.2f' % overhead)
-    return {'real_rate_byte': len(blob), 'psnr': psnr, 'nb_frames_to_code': n, 'estimated_rate_byte': est_byte,
-            'rate_overhead_percent': overhead, 'range_coder_payload_byte': int(payload)}
+    out = {'real_rate_byte': len(blob), 'psnr': psnr, 'nb_frames_to_code': n, 'estimated_rate_byte': est_byte,
+           'rate_overhead_percent': overhead, 'range_coder_payload_byte': int(payload)}
+    if seq_res is not None:
+        avg = seq_res['sequence']
+        out.update(ms_ssim_db=avg['ms_ssim_db'], h=avg['h'], w=avg['w'], nb_coded_frames=len(seq_res) - 1)
+    return out

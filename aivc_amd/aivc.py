@@ -25,7 +25,7 @@ def gop_name(cfg, gop_size, intra_period):
     sys.exit('[ERROR]: unknown coding configuration. Should be either RA, AI or LDP.')
 
 
-def main(argv=None):
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--coding_config', default='RA', type=str)
     p.add_argument('--gop_size', default=32, type=int)
@@ -39,7 +39,14 @@ def main(argv=None):
     p.add_argument('--rng_seed', default=666, type=int)
     p.add_argument('--cpu', action='store_true')
     p.add_argument('--log_dir', default='', type=str, help="the encoder's per-frame table goes to <log_dir>/detailed.txt (encode.py)")
+    enc_cli.add_rate_flags(p)
     a = p.parse_args(argv)
+    enc_cli.check_rate_flags(p, a)
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     gop = gop_name(a.coding_config, a.gop_size, a.intra_period)
     common = ['--model', a.model] + (['--cpu'] if a.cpu else [])
     import os
@@ -47,7 +54,10 @@ def main(argv=None):
     banner(('*' * 80).center(120))
     banner('Starting encoding'.center(120))
     enc_cli.main(['-i', a.i, '--gop', gop, '--start_frame', str(a.start_frame), '--end_frame', str(a.end_frame),
-                  '-o', a.bitstream_out] + common + (['--log_dir', a.log_dir] if a.log_dir else []))
+                  '-o', a.bitstream_out, '--rate_step', str(a.rate_step)] + common
+                 + (['--log_dir', a.log_dir] if a.log_dir else [])
+                 + (['--idx_rate', str(a.idx_rate)] if a.idx_rate is not None else [])
+                 + (['--target_bpp', str(a.target_bpp)] if a.target_bpp > 0 else []))
     banner(('*' * 80).center(120))
     banner('Starting decoding'.center(120))
     status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common)

@@ -11,7 +11,7 @@ import os as _os
 
 import torch
 
-from . import abi, ops
+from . import abi, ops, rate_control
 from .func_util.GOP_structure import FRAME_B, FRAME_I, FRAME_P, coding_levels, generate_gop_struct
 from .real_life import cat_binary_files as container
 from .real_life import header as hdr
@@ -120,6 +120,8 @@ class FrameCodec:
     def encode_batch(self, cur, prev, nxt, frame_type, idx_rate=0., want_aux=False, on_sections=None, want_rec=True):
         """Encode n frames of the same type together.  cur/prev/nxt: lists of uint8 plane dicts
         (prev/nxt ignored where the frame type has no such reference).
+        idx_rate: a scalar, or one rate per frame of the batch (frames of units coded at different rates: the latent stages
+        then use one gain row per image, include/aivc_hip_rates.h; the same rate n times is the scalar path).
         -> list of {'bytes', 'rec', 'data_dim'[, 'aux']}
         on_sections(sections): called once every latent of the batch is quantised -- BEFORE the CodecNet synthesis is
         queued -- so that the caller can send the non-zero-map flags on their way to the host (prepare_finalize)
@@ -293,6 +295,7 @@ class FrameCodec:
         y streams -> y_hat.  It depends on the bitstream only (never on reconstructed frames), so the
         caller may run it for every frame of a video up front, all streams concurrently.
         -> {'mof': y_hat [n,h_y,w_y,C] or None, 'cod': y_hat}
+        idx_rate: a scalar, or one rate per frame (as in encode_batch).
         streams: optional list of HIP streams; the two networks' chains (z streams -> h_s -> y streams) are
         independent and go to streams[0] / streams[1]; then -> (dict, [event per chain])."""
         device = device or torch.device('cuda')
@@ -428,6 +431,10 @@ class FrameCodec:
     def encode_units(self, units, gop_name, idx_rate=0., shard=None, recon='all', stats=None, stats_units=None):
         """units: list of frame lists (display order, each len == len(GOP struct)).
         -> ([gop bytes per unit], [reconstructions per unit], data_dim)
+        idx_rate: a scalar for all units, or one rate per unit: frame (u, f) of a level batch is then coded at idx_rate[u]
+        (one batch may mix rates) and unit u's GOP header carries idx_rate[u].  A list is checked
+        (rate_control.check_unit_rates: multiples of 1/16 inside the gain matrix, ValueError naming the unit); a scalar is
+        taken as it is.  Each unit comes out with the bytes it has when coded alone at its rate.
         recon: 'all' -- every frame is reconstructed, as the reference's encoder does (its forward pass returns x_hat
         for every frame and the command line prints a PSNR from them); 'refs' -- a bitstream-only encoder: frames that
         no other frame of the GOP structure references (the last dependency level of a random-access GOP: 16 of the 33
@@ -462,6 +469,14 @@ class FrameCodec:
         if stats is not None and shard is not None:
             raise ValueError('stats= is an option of unit-wise coding (the level-sharded paths spread a unit over ranks)')
         stats_units = list(range(len(units))) if stats_units is None else list(stats_units)
+        unit_rates = None  # one rate per unit, or None: idx_rate serves them all
+        if rate_control.is_rate_list(idx_rate):
+            if len(idx_rate) != len(units):
+                raise ValueError('%d rate indices for %d units' % (len(idx_rate), len(units)))
+            unit_rates = rate_control.check_unit_rates(idx_rate, rate_control.nb_rates_of(self))
+
+        def rate_of(chunk):
+            return idx_rate if unit_rates is None else [unit_rates[u] for u, _ in chunk]
         referenced = {gop[f][k] for f in gop for k in ('prev_ref', 'next_ref') if gop[f].get(k) is not None}
 
         def flush(li):
@@ -491,12 +506,12 @@ class FrameCodec:
                                   [rec[u].get(gop[f]['next_ref']) for u, f in chunk])
                 on_secs = (lambda secs: preps.append(prepare_finalize(secs))) if keep else None
                 if bands is None:
-                    out = self.encode_batch(cur, prev, nxt, ftype, idx_rate, want_aux=stats is not None, on_sections=on_secs,
+                    out = self.encode_batch(cur, prev, nxt, ftype, rate_of(chunk), want_aux=stats is not None, on_sections=on_secs,
                                             want_rec=recon == 'all' or any(f in referenced for _, f in chunk))
                     if stats is not None:
                         stats.score_batch([(stats_units[u], frame_index(f)) for u, f in chunk], out.pop('aux'))
                 else:
-                    out = self.encode_banded(cur[0], prev[0], nxt[0], ftype, idx_rate, bands, on_sections=on_secs)
+                    out = self.encode_banded(cur[0], prev[0], nxt[0], ftype, rate_of(chunk), bands, on_sections=on_secs)
                 data_dim = out['data_dim']
                 for (u, f), r in zip(chunk, out['rec']):
                     rec[u][f] = r
@@ -527,8 +542,8 @@ class FrameCodec:
             for (u, f), b in allb.items():
                 fbytes[u][f] = b
             data_dim = shard.agree(data_dim)
-        head = hdr.gop_header_bytes(gop_name, idx_rate)
-        blobs = [container.pack_gop(head, [fbytes[u][f] for f in names]) for u in range(len(units))]
+        heads = [hdr.gop_header_bytes(gop_name, idx_rate if unit_rates is None else unit_rates[u]) for u in range(len(units))]
+        blobs = [container.pack_gop(heads[u], [fbytes[u][f] for f in names]) for u in range(len(units))]
         return blobs, [[rec[u][f] for f in names] for u in range(len(units))], data_dim
 
     def decode_units(self, gop_blobs, data_dim, device=None, shard=None):
@@ -563,7 +578,9 @@ class FrameCodec:
 
     def _decode_units_gen(self, gop_blobs, data_dim, device=None, shard=None):
         """-> [reconstructions (display order) per unit] (a generator: yields once per coding-structure group, right
-        after that group's entropy stage has been issued up front; decode_units runs it through).  shard: as in encode_units (the entropy stage only runs
+        after that group's entropy stage has been issued up front; decode_units runs it through).  Units are grouped by
+        their coding structure; each carries the rate index of its own GOP header, so a video whose units were coded at
+        different rates decodes in the same level batches as a single-rate one.  shard: as in encode_units (the entropy stage only runs
         for this rank's frames; one exchange of the new reconstructions per level).
         Stage 1 entropy-decodes EVERY frame of every unit (entropy_chunk frames at a time: that many
         range-coder streams run concurrently, one wavefront each; the serial coder is off the
@@ -571,10 +588,10 @@ class FrameCodec:
         parsed = [container.unpack_gop(g) for g in gop_blobs]
         self.check_sections(parsed)
         out = [None] * len(gop_blobs)
-        groups = {}
-        for i, (name, idx_rate, _) in enumerate(parsed):
-            groups.setdefault((name, idx_rate), []).append(i)
-        for (gop_name, idx_rate), members in groups.items():
+        groups = {}  # by coding structure alone: the members keep their own rate index, a level batch may mix them
+        for i, (name, _, _) in enumerate(parsed):
+            groups.setdefault(name, []).append(i)
+        for gop_name, members in groups.items():
             gop = generate_gop_struct(gop_name)
             names = sorted(gop, key=frame_index)
             # entropy stage on the (high priority) side stream, one dependency level ahead of the
@@ -612,7 +629,7 @@ class FrameCodec:
                     pair = [sides[(rr[0] + k) % len(sides)] for k in range(2)]
                     rr[0] += 2
                     yh, evs = self.entropy_decode([parsed[i][2][frame_index(f)] for i, f in chunk], ftype,
-                                                  data_dim, idx_rate, device, streams=pair)
+                                                  data_dim, [parsed[i][1] for i, _ in chunk], device, streams=pair)
                     for v in yh.values():
                         if v is not None:
                             v.record_stream(main)
@@ -679,7 +696,9 @@ class FrameCodec:
         unit is padded by repeating the last frame (src/model_mngt/model_management.py:142-153).
         unit_filter(u) -> bool selects the units this process codes (multi-GPU sharding); skipped
         units come back as None in the returned list of GOP blobs.
-        stats: see encode_units; the rows are recorded under (unit number in the video, display index in the unit)."""
+        stats: see encode_units; the rows are recorded under (unit number in the video, display index in the unit).
+        idx_rate: a scalar, or one rate per unit of the VIDEO (indexed by the unit's number whatever unit_filter selects;
+        the entries of units filtered out are not looked at)."""
         n = len(frames)
         idx_end_frame = idx_starting_frame + n - 1 if idx_end_frame is None else idx_end_frame
         unit = len(generate_gop_struct(gop_name))
@@ -688,6 +707,10 @@ class FrameCodec:
         gops, recs, data_dim = [None] * nb_gop, [None] * nb_gop, None
         if mine:
             units = [[frames[min(u * unit + i, n - 1)] for i in range(unit)] for u in mine]
+            if rate_control.is_rate_list(idx_rate):
+                if len(idx_rate) != nb_gop:
+                    raise ValueError('%d rate indices for the %d units of the video' % (len(idx_rate), nb_gop))
+                idx_rate = rate_control.check_unit_rates([idx_rate[u] for u in mine], rate_control.nb_rates_of(self), mine)
             blobs, rr, data_dim = self.encode_units(units, gop_name, idx_rate, recon=recon, stats=stats, stats_units=mine)
             for u, b, r in zip(mine, blobs, rr):
                 gops[u], recs[u] = b, r

@@ -8,7 +8,31 @@ from aivc_amd.func_util.GOP_structure import generate_gop_struct
 from aivc_amd.real_life.encode import encode
 
 
-def main(argv=None):
+def add_rate_flags(p):
+    """--idx_rate / --target_bpp / --rate_step (shared with aivc.py)"""
+    p.add_argument('--idx_rate', default=None, type=float,
+                   help='rate index of the whole clip: a multiple of 1/16 in [0, rate indices of the model - 1]; default 0')
+    p.add_argument('--target_bpp', default=0., type=float,
+                   help='bit per pixel: every intra-period unit is coded at the richest rate index whose GOP record fits '
+                        'target_bpp x w x h x frames / 8 bytes (a few bitstream-only encodes per unit); 0: off')
+    p.add_argument('--rate_step', default=0.0625, type=float, help='grid step of the --target_bpp search (a multiple of 1/16)')
+
+
+def check_rate_flags(p, a):
+    """-> the idx_rate to encode with; an argparse error for --idx_rate together with --target_bpp or off the 1/16 grid"""
+    from aivc_amd import rate_control
+    if a.target_bpp < 0:
+        p.error('--target_bpp must be positive (0: off)')
+    if a.idx_rate is not None and a.target_bpp > 0:
+        p.error('--idx_rate and --target_bpp are mutually exclusive: a byte budget chooses the rate index itself')
+    if a.idx_rate is not None and (a.idx_rate < 0 or not rate_control.on_sixteenths(a.idx_rate)):
+        p.error('--idx_rate %r: expected a non-negative multiple of 1/16 (the GOP header stores sixteenths)' % a.idx_rate)
+    if a.rate_step <= 0 or not rate_control.on_sixteenths(a.rate_step):
+        p.error('--rate_step %r: expected a positive multiple of 1/16' % a.rate_step)
+    return 0 if a.idx_rate is None else a.idx_rate
+
+
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--gop', default='1_GOP_32', type=str)
     p.add_argument('--model', default='ms_ssim-2021cc-6', type=str)
@@ -21,12 +45,22 @@ def main(argv=None):
     p.add_argument('--log_dir', default='', type=str,
                    help='write the per-frame table <log_dir>/detailed.txt (PSNR, rates, alpha, beta, loss, MS-SSIM) and print '
                         'the Estimated MS-SSIM line; off by default')
+    add_rate_flags(p)
     a = p.parse_args(argv)
+    a.idx_rate = check_rate_flags(p, a)
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     dev = resolve_device(a.cpu)
     model = get_model(a.model, dev)
+    nb_rates = len(model.codec_net.codec_net.gain_I.enc_gain_list) if a.idx_rate else 1
+    if a.idx_rate > nb_rates - 1:
+        raise SystemExit('[ERROR] --idx_rate %s: model %s has %d rate indices (0 ... %d)' % (a.idx_rate, a.model, nb_rates, nb_rates - 1))
     return encode({'model': model, 'sequence_path': a.i, 'GOP_struct': generate_gop_struct(a.gop),
-                   'GOP_struct_name': a.gop, 'idx_rate': 0, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
-                   'idx_end_frame': a.end_frame, 'working_dir': a.log_dir})
+                   'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
+                   'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp, 'rate_step': a.rate_step})
 
 
 if __name__ == '__main__':

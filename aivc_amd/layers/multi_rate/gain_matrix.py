@@ -50,6 +50,21 @@ class GainMatrix(Module):
             return self.interpolate_gain_vector(idx_rate, mode).detach().reshape(-1)  # API use on CPU params
         return ops.gain_interp(lst[prev_i], lst[next_i], lam)
 
+    def gain_rows(self, rates, mode, c=None):
+        """[n][C] gain table of a batch whose image i is coded at rates[i] (ops.channel_gain_rows / quantize_center_rows /
+        dequantize_rows): row i is gain_vector(rates[i], mode) -- evaluated once per DISTINCT rate, so a fractional rate has
+        the bits of the single-rate path -- the rows stacked on the parameters' device.  c: the channels of the batch, needed
+        only to expand a scalar-gain matrix (default: the vector's own length)."""
+        vecs = {}
+        for r in rates:
+            r = float(r)
+            if r not in vecs:
+                g = self.gain_vector(r, mode)
+                if c is not None and g.numel() == 1 and c != 1:
+                    g = g.expand(c)
+                vecs[r] = g
+        return torch.stack([vecs[float(r)] for r in rates]).contiguous()
+
     def forward(self, param):
         default = {'x': None, 'idx_rate': 0., 'mode': None}
         x = get_value('x', param, default)

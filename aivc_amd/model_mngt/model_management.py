@@ -103,12 +103,16 @@ def lambda_tradeoff_of(model, idx_rate):
 def sequence_result_from_rows(rows, nb_gop, unit, idx_starting_frame, nb_frames, lambda_tradeoff=0.0):
     """rows: {(unit number, display index): row of aivc_amd.quality} of all nb_gop x unit coded frames -> the reference's
     sequence_result: {'frame_<index in the video>': result dictionary, ..., 'sequence': their average}, the frames in display
-    order; the frames past nb_frames are the padding of the last unit (rate counts, distortion does not)."""
+    order; the frames past nb_frames are the padding of the last unit (rate counts, distortion does not).
+    lambda_tradeoff: one number, or one per unit (units coded at different rate indices: the loss column of a frame uses its
+    unit's; the sequence row averages the frames' columns, so its loss weighs every frame's rate with that frame's lambda)."""
     from ..func_util.result_logging import average_N_frame, frame_result
+    per_unit = isinstance(lambda_tradeoff, (list, tuple))
     seq = {}
     for u in range(nb_gop):
         for i in range(unit):
-            seq['frame_%d' % (u * unit + i + idx_starting_frame)] = frame_result(rows[(u, i)], lambda_tradeoff)
+            seq['frame_%d' % (u * unit + i + idx_starting_frame)] = frame_result(rows[(u, i)],
+                                                                                lambda_tradeoff[u] if per_unit else lambda_tradeoff)
     seq['sequence'] = average_N_frame(seq, nb_pad_frame=nb_gop * unit - nb_frames)
     return seq
 

@@ -616,6 +616,53 @@ def dequantize(q, mu=None, gain_dec=None):
     return out
 
 
+# ... with one gain row per image of the batch (include/aivc_hip_rates.h): x [n, ..., c], gains [n, c]
+def _gain_rows(gains, n, c):
+    if gains is None:
+        return None
+    gains = _dev(gains.detach(), torch.float32, 'gains')
+    if tuple(gains.shape) != (n, c):
+        raise AivcNativeError('gain rows: expected [%d, %d] (one row per image), got %s' % (n, c, list(gains.shape)))
+    return gains
+
+
+def _rows_dims(t):
+    if t.dim() < 2:
+        raise AivcNativeError('a batch with gain rows is [n, ..., c], got %s' % list(t.shape))
+    n, c = t.shape[0], t.shape[-1]
+    return n, (t.numel() // (n * c) if n * c else 0), c
+
+
+def channel_gain_rows(x, gains):
+    x = _dev(x, torch.float32, 'x')
+    n, npix, c = _rows_dims(x)
+    gains = _gain_rows(gains, n, c)
+    out = torch.empty_like(x)
+    call('aivc_channel_gain_rows', _p(x), _p(gains), n, npix, c, _p(out), _stream())
+    return out
+
+
+def quantize_center_rows(y, mu, gains_dec, want_yhat=True, want_q=True):
+    y = _dev(y, torch.float32, 'y')
+    mu = _dev(mu, torch.float32, 'mu')
+    n, npix, c = _rows_dims(y)
+    gains_dec = _gain_rows(gains_dec, n, c)
+    q = torch.empty(y.shape, dtype=torch.int16, device=y.device) if want_q else None
+    y_hat = torch.empty_like(y) if want_yhat else None
+    call('aivc_quantize_center_rows', _p(y), _p(mu), _p(gains_dec), n, npix, c, _p(q), _p(y_hat), _stream())
+    return q, y_hat
+
+
+def dequantize_rows(q, mu, gains_dec):
+    q = _dev(q, torch.int16, 'q')
+    mu = _dev(mu, torch.float32, 'mu')
+    n, npix, c = _rows_dims(q)
+    gains_dec = _gain_rows(gains_dec, n, c)
+    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    call('aivc_dequantize_rows', _p(q), _p(mu), _p(gains_dec), n, npix, c, _p(out), _stream())
+    return out
+
+
 # entropy model ---------------------------------------------------------------------------------
 def balle_cdf_table(params, want_float=False):
     params = _dev(params, torch.float32, 'params')

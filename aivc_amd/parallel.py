@@ -149,6 +149,7 @@ def gather_gops(local_gops, dst=0, device=None):
 def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, idx_rate=0., return_enc=False, stats=None):
     """Every rank passes the same `frames`; returns the full bitstream on rank 0 (None elsewhere); with return_enc also
     this rank's encode_video record (its units' reconstructions, None for the others').
+    idx_rate: a scalar, or one rate per unit of the video (FrameCodec.encode_video); every rank passes the same list.
     stats (aivc_amd.quality.QualityStats): every rank scores the frames of ITS units into its own collector
     (FrameCodec.encode_units); gather_quality_rows brings the rows together."""
     rank, world = rank_world()
@@ -157,6 +158,14 @@ def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, id
                                    unit_filter=lambda u: unit_owner(u, world) == rank, **extra)
     dev = getattr(frames[0]['y'], 'device', None)
     dev = dev if isinstance(dev, torch.device) else None
+    blob = assemble_video_sharded(frame_codec, enc, dev)
+    return (blob, enc) if return_enc else blob
+
+
+def assemble_video_sharded(frame_codec, enc, dev=None):
+    """enc: this rank's encode_video record (None for the units its peers coded) -> the full bitstream on rank 0, None
+    elsewhere.  A collective."""
+    _, world = rank_world()
     gops = gather_gops(enc['gops'], device=dev)
     data_dim = enc['data_dim']
     if world > 1:  # ranks without a unit do not know the latent sizes: element-wise max of six int64
@@ -167,9 +176,8 @@ def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, id
         with _host_wait('latent sizes to the host'):
             data_dim = _dd_from_ints([int(x) for x in t.cpu()])
     if gops is None:
-        return (None, enc) if return_enc else None
-    blob = frame_codec.assemble_video(dict(enc, gops=gops, data_dim=data_dim))
-    return (blob, enc) if return_enc else blob
+        return None
+    return frame_codec.assemble_video(dict(enc, gops=gops, data_dim=data_dim))
 
 
 def gather_quality_rows(rows, keys, device=None):
@@ -430,6 +438,8 @@ def encode_clip(frame_codec, units, gop_name, idx_rate=0., shard=None):
     mine = {}
     data_dim = None
     if shard.units:
+        if isinstance(idx_rate, (list, tuple)):  # one rate per unit of the clip: this group's
+            idx_rate = [idx_rate[u] for u in shard.units]
         blobs, _, data_dim = frame_codec.encode_units([units[u] for u in shard.units], gop_name, idx_rate, shard=shard)
         mine = dict(zip(shard.units, blobs))
     return shard.gather_units(mine, data_dim)

@@ -63,10 +63,15 @@ def encode(param):
     """working_dir: '' (the default) -- no log; a directory -- the reference's per-frame table <working_dir>/detailed.txt
     (func_util/result_logging.py) is written from statistics scored on the device while the frames are coded
     (aivc_amd/quality.py), the PSNR line comes from the exact integer squared error, an `Estimated MS-SSIM` line follows it
-    and the returned dictionary gains ms_ssim_db, h, w and nb_coded_frames.  The bitstream is the same either way."""
+    and the returned dictionary gains ms_ssim_db, h, w and nb_coded_frames.  The bitstream is the same either way.
+    idx_rate: the rate index of the whole clip, or a list with one per intra-period unit.  target_bpp > 0 (instead of an
+    idx_rate): every unit gets the richest rate index of the grid 0, rate_step, ..., nb_rates - 1 whose GOP record fits
+    target_bpp x w x h x (frames of the unit) / 8 bytes (aivc_amd/rate_control.py: a few bitstream-only encodes, then the
+    final one); one `[RATE]` line per unit, a `[WARN]` line for a unit that does not fit at any rate; the returned dictionary
+    gains 'rates'.  Under torch.distributed.run every rank searches the units it codes."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
-               'working_dir': ''}
+               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16}
     model = get_value('model', param, default)
     seq = get_value('sequence_path', param, default)
     gop_name = get_value('GOP_struct_name', param, default)
@@ -75,6 +80,8 @@ def encode(param):
     last = get_value('idx_end_frame', param, default)
     working_dir = get_value('working_dir', param, default)
     idx_rate = get_value('idx_rate', param, default)
+    target_bpp = get_value('target_bpp', param, default)
+    rate_step = get_value('rate_step', param, default)
     dev = next(model.parameters()).device
     if first > last and last != -1:
         print('ERROR: First frame index bigger than last frame index')
@@ -91,8 +98,12 @@ def encode(param):
     if working_dir:
         from ..quality import QualityStats
         stats = QualityStats()
+    budgeted = None
     with torch.no_grad(), bitstream.estimating_rate():  # the reference's in-band rate check (RESULT lines)
-        if world > 1:  # one process per GPU: intra-period units over the ranks, the container on rank 0
+        if target_bpp and target_bpp > 0:
+            budgeted = _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev)
+            blob, enc, idx_rate = budgeted
+        elif world > 1:  # one process per GPU: intra-period units over the ranks, the container on rank 0
             blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=idx_rate, return_enc=True, stats=stats)
         else:
             enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last, idx_rate=idx_rate, stats=stats)
@@ -128,7 +139,9 @@ def encode(param):
         keys = [(u, i) for u in range(enc['nb_gop']) for i in range(unit)]
         rows = parallel.gather_quality_rows(stats.rows(), keys, dev)
         if rank == 0:
-            seq_res = sequence_result_from_rows(rows, enc['nb_gop'], unit, first, n, lambda_tradeoff_of(model, idx_rate))
+            lambdas = [lambda_tradeoff_of(model, r) for r in idx_rate] if isinstance(idx_rate, (list, tuple)) \
+                else lambda_tradeoff_of(model, idx_rate)
+            seq_res = sequence_result_from_rows(rows, enc['nb_gop'], unit, first, n, lambdas)
             name = os.path.basename(os.path.normpath(seq))
             write_detailed_log(working_dir, seq_res, name[:-4] if name.endswith('.yuv') else name)
     if get_value('flag_bitstream_debug', param, default):
@@ -172,4 +185,31 @@ def encode(param):
     if seq_res is not None:
         avg = seq_res['sequence']
         out.update(ms_ssim_db=avg['ms_ssim_db'], h=avg['h'], w=avg['w'], nb_coded_frames=len(seq_res) - 1)
+    if budgeted is not None:
+        out['rates'] = list(idx_rate)
     return out
+
+
+def _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev):
+    """encode() under a byte budget per unit: every rank searches and codes the units it owns (a unit's choice depends on
+    that unit alone), rank 0 gets the container; the [RATE] / [WARN] lines come from rank 0, for all units.
+    -> (bitstream or None, this rank's encode_video record, [rate per unit of the video])"""
+    from .. import parallel, rate_control
+    mine = (lambda u: parallel.unit_owner(u, world) == rank) if world > 1 else None
+    enc = rate_control.encode_video_budgeted(fc, frames, gop_name, target_bpp, step=rate_step, idx_starting_frame=first,
+                                             stats=stats, unit_filter=mine)
+    report = {u: (ch.rate, ch.nbytes, int(ch.over_budget)) for u, ch in enumerate(enc['choices']) if ch is not None}
+    if world > 1:
+        import struct
+        keys = list(range(enc['nb_gop']))
+        got = parallel.gather_bytes_all({u: struct.pack('>dqq', *v) for u, v in report.items()}, keys, None, world, dev)
+        report = {u: struct.unpack('>dqq', b) for u, b in got.items()}
+    blob = parallel.assemble_video_sharded(fc, enc, dev)
+    rates = [report[u][0] for u in range(enc['nb_gop'])]
+    if rank == 0:
+        for u in range(enc['nb_gop']):
+            r, nbytes, over = report[u]
+            print('[RATE] unit %d: idx_rate %s %d B / %d B' % (u, ('%.4f' % r).rstrip('0').rstrip('.'), nbytes, enc['budgets'][u]))
+            if over:
+                print('[WARN] unit %d: %d B at its leanest rate index, over its budget of %d B' % (u, nbytes, enc['budgets'][u]))
+    return blob, enc, rates

@@ -21,8 +21,16 @@
 //                  tiles x 8, by a cooperative transform: 8 ds_read_b128 + 32 v_fma + 4 ds_write_b128 per thread).
 //                  Everything double-buffered (158 KB of LDS, one workgroup per CU) and ONE barrier per chunk: in chunk c a
 //                  wave issues the DMAs of raw(c + 2) and U(c + 1), transforms raw(c + 1) into the other V buffer and
-//                  multiplies chunk c -- the two waves of a SIMD in opposite order, so that one's transform runs under the
-//                  other's MFMAs.
+//                  multiplies chunk c: one instruction stream in which the transform's steps follow the MFMAs of a position pair.
+//   phase offset   the two waves of a SIMD (w and w + 4, the position halves) run that stream in the same order.  In the
+//                  stride-1 kernel they are kept one window of non-matrix work apart: behind the chunk's barrier the upper
+//                  half issues its 5-6 DMA instructions first, the lower half goes straight to its first pair and issues them
+//                  behind that pair's MFMAs -- with both heads at the same place the matrix pipe stood idle for their length;
+//                  the barrier re-aligns the waves, so the offset is made again in every chunk.  There the raw pixels of a
+//                  transform step are also read BEFORE the pair's MFMAs and combined behind them (4 float4 in flight), and the
+//                  transform has no run-time flag.  3x3 128 -> 128: 6-10 % per launch (experiments/wino_phases.md).  The 5x5
+//                  forms keep both heads at the barrier: the second copy of their issue code (phase / class address
+//                  arithmetic) costs registers they do not have, measured 0 ... +5 % slower at either offset and either half.
 #include <stdlib.h>
 
 #include "mfma_util.h"
@@ -294,19 +302,22 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   const int a_rd = (8 * ph) * WINO_V_POS + hh * WINO_V_QUAD + (32 * wm + l31) * 16;
   const int b_rd = (8 * ph) * 2048 + hh * 1024 + (32 * wn + l31) * 16;
   // chunk c multiplied (8 positions x 4 MFMAs) with the transform of chunk c + 1 dealt out between the positions: one
-  // instruction stream per wave in which matrix and vector / LDS work alternate, so that the two waves of a SIMD fill each
-  // other's gaps without any phase arrangement
+  // instruction stream per wave in which matrix and vector / LDS work alternate.  dma(): the chunk's LDS-DMA issues, which the
+  // stride-1 kernel places by position half (the file header's phase offset); the 5x5 forms have issued them already
   // FIRST: the block's first chunk starts its accumulators from the inline constant 0 (no clearing pass after the fold)
   // pm: bit q set = position q of this wave's half is issued (polyphase form: positions whose U is zero by construction are not)
-  // tm: bit s set = step s of the NEXT chunk's transform is run (0: no transform rides along)
-  auto multiply = [&](auto STAGE, auto FIRST, uint32_t tm, uint32_t pm) {
+  // tm (5x5 forms): bit s set = step s of the NEXT chunk's transform is run: the masks skip rows and columns that are zero by
+  // construction.  The stride-1 kernel runs every step in every chunk: behind the last chunk of a workgroup's last block that
+  // transform reads the stale raw stage 0 and writes V stage 0, which nobody reads again (the pair exchange uses V stage 1)
+  auto multiply = [&](auto STAGE, auto FIRST, uint32_t tm, uint32_t pm, auto &&dma) {
     constexpr int stage = decltype(STAGE)::value;
     constexpr bool first = decltype(FIRST)::value;
     using NEXT = std::integral_constant<int, 1 - stage>;
     const char *va = Vs + stage * WINO_V_STAGE + a_rd, *ub = Us + stage * WINO_U_STAGE + b_rd;
     // positions in pairs: the MFMAs of two accumulators alternate (a dependent MFMA waits for its predecessor's last pass),
     // the fragments of the next pair are read while this pair multiplies, the transform steps follow the pair's MFMAs (the
-    // first MFMAs behind the chunk's barrier then wait for two LDS round trips only)
+    // first MFMAs behind the chunk's barrier then wait for two LDS round trips only); stride-1 kernel: the raw pixels of the
+    // pair's read steps are asked for in front of its MFMAs, so that the combination behind them does not wait for LDS
     float4 af[2][2], bf[2][2];
     auto rd = [&](int set, int q) {
       af[set][0] = *reinterpret_cast<const float4 *>(va + q * WINO_V_POS);
@@ -314,6 +325,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       af[set][1] = *reinterpret_cast<const float4 *>(va + (q + 1) * WINO_V_POS);
       bf[set][1] = *reinterpret_cast<const float4 *>(ub + (q + 1) * 2048);
     };
+    if constexpr (MODE == 0) {
+      if (ph) dma();  // (the lower half issues them behind its first pair)
+    }
     rd(0, 0);
     auto pair = [&](auto Q) {
       constexpr int q = decltype(Q)::value, set = (q >> 1) & 1;
@@ -321,6 +335,26 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       if constexpr (q + 2 < 8) {
         if (MODE == 0 || (first && !TC) || (pm & (0xCu << q))) rd(1 - set, q + 2);
       }
+      float4 ta[2], tb[2];  // the raw pixels of two read steps of the transform, in flight under the pair's MFMAs
+      auto reads = [&](auto S) {
+        constexpr int st = decltype(S)::value;
+        const char *rs = raw + (1 - stage) * WINO_RAW_STAGE;
+        ta[0] = *reinterpret_cast<const float4 *>(rs + t_oa[st]);
+        tb[0] = *reinterpret_cast<const float4 *>(rs + t_ob[st]);
+        ta[1] = *reinterpret_cast<const float4 *>(rs + t_oa[st + 1]);
+        tb[1] = *reinterpret_cast<const float4 *>(rs + t_ob[st + 1]);
+      };
+      auto finish = [&](auto S) {
+        constexpr int st = decltype(S)::value;
+        if constexpr (st < 4) {
+          R[st] = comb(ta[0], tb[0], t_si);
+          R[st + 1] = comb(ta[1], tb[1], t_si);
+        } else {
+          transform_step(NEXT{}, integral_constant<int, st>{});
+          transform_step(NEXT{}, integral_constant<int, st + 1>{});
+        }
+      };
+      if constexpr (MODE == 0 && q < 4) reads(Q);
       __builtin_amdgcn_sched_barrier(0);
       const float4 x0 = af[set][0], y0 = bf[set][0], x1 = af[set][1], y1 = bf[set][1];
       if constexpr (first && TC) {
@@ -369,8 +403,15 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      if ((tm >> q) & 1u) transform_step(NEXT{}, integral_constant<int, q>{});
-      if ((tm >> (q + 1)) & 1u) transform_step(NEXT{}, integral_constant<int, q + 1>{});
+      if constexpr (MODE == 0) {
+        if constexpr (q == 0) {
+          if (!ph) dma();
+        }
+        finish(Q);
+      } else {
+        if ((tm >> q) & 1u) transform_step(NEXT{}, integral_constant<int, q>{});
+        if ((tm >> (q + 1)) & 1u) transform_step(NEXT{}, integral_constant<int, q + 1>{});
+      }
       __builtin_amdgcn_sched_barrier(0);
     };
     using std::integral_constant;
@@ -403,11 +444,15 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     // two chunks per trip (stage parities 0, 1: compile-time LDS offsets); the block's first chunk starts the accumulators
     auto chunk = [&](auto STAGE, auto FIRST, int c) {
       // here: V(c) complete, U(c) and raw(c + 1) in LDS; raw stage c & 1, U stage (c + 1) & 1 and V stage (c + 1) & 1 are free
-      // (chunks beyond this block's are the first ones of the next block).  The transform of chunk c + 1 rides along (always,
-      // except behind the last chunk of the workgroup's last block: a run-time flag -- as a third instantiation of the chunk
+      // (chunks beyond this block's are the first ones of the next block): the DMA targets are free from here to the closing
+      // s_waitcnt + barrier, wherever in the chunk a wave issues them.  The transform of chunk c + 1 rides along (5x5 forms:
+      // except behind the last chunk of the workgroup's last block, a run-time flag -- as a third instantiation of the chunk
       // the register allocator spilled 213 registers)
-      issue_raw_at(kb, c + 2);
-      issue_u_at(kb, c + 1);
+      auto dma = [&]() {
+        issue_raw_at(kb, c + 2);
+        issue_u_at(kb, c + 1);
+      };
+      if constexpr (MODE != 0) dma();
       uint32_t pm = 0xFFu;
       if constexpr (POLY) {  // phase 2 py + px of this chunk: j == 3 (q = 3, 7) is zero for px = 1, i == 3 (the upper half's q = 4 .. 7) for py = 1
         const int ph2 = c >> cpp_shift;
@@ -420,13 +465,14 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       }
       // the transform of chunk c + 1 (the next block's chunk 0 behind this block's last): this thread computes the positions
       // (i = t_i, j = 0 .. 3) -- nothing if row i is zero by construction in that chunk's phase / class, not V_j if column j is
-      uint32_t tm = (c + 1 < nch || kb + 1u < n_mine) ? 0xFFu : 0u;
+      uint32_t tm = 0xFFu;
       if constexpr (MODE != 0) {
+        if (!(c + 1 < nch || kb + 1u < n_mine)) tm = 0u;
         const int pcn = c + 1 < nch ? phase_or_class(cur, c + 1) : phase_or_class(nxt, 0);
         if (zero_pos(pcn, t_i, 1)) tm = 0u;  // (j = 1 is never zero by construction: the row is)
         else if (zero_pos(pcn, 1, POLY ? 3 : 0)) tm &= POLY ? ~0x80u : ~0x10u;
       }
-      multiply(STAGE, FIRST, tm, pm);
+      multiply(STAGE, FIRST, tm, pm, dma);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     };

@@ -76,7 +76,7 @@ static int conv_route(const aivc_conv_params *p) {
   if (p->gdn) return direct || !aivc::conv2d_mfma_supported(*p) ? AIVC_ERR_UNSUPPORTED : ROUTE_MFMA;
   if (p->tail_c_out) return direct || !aivc::conv2d_mfma_tail_supported(*p) ? AIVC_ERR_UNSUPPORTED : ROUTE_MFMA;
   if (direct) return ROUTE_DIRECT;
-  if (p->algo == AIVC_ALGO_MFMA) return ROUTE_MFMA;
+  if (p->algo == AIVC_ALGO_MFMA) return aivc::conv2d_mfma_addressable(*p) ? ROUTE_MFMA : AIVC_ERR_UNSUPPORTED;
   if (auto_ && aivc::gdn_resident_supported(*p)) return ROUTE_GDN_RESIDENT;  // stand-alone (I)GDN: same bits as the MFMA GDN mode
   if (auto_ && aivc::conv2d_thin_supported(*p)) return ROUTE_THIN;
   return aivc::conv2d_mfma_supported(*p) ? ROUTE_MFMA : ROUTE_DIRECT;

@@ -31,6 +31,11 @@ struct LdsOptIn {
   }
 };
 
+// The LDS-DMA loaders of the conv family form per-lane BYTE offsets in 32 bits: this is what one launch can address of
+// a tensor.  (Tensors of the family are multiples of 16 bytes, c_in % 4 == 0: the largest such size below 4 GiB.)
+constexpr uint64_t LOADER_MAX_BYTES = 0xFFFFFFF0ull;
+static inline bool loader_addressable(uint64_t bytes) { return bytes <= LOADER_MAX_BYTES; }
+
 static inline hipStream_t to_stream(aivc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
@@ -124,7 +129,8 @@ struct Epilogue {
 
 int conv2d_direct(const aivc_conv_params &p, hipStream_t s);
 int conv2d_mfma(const aivc_conv_params &p, hipStream_t s);  // AIVC_ERR_UNSUPPORTED if shape not covered
-bool conv2d_mfma_supported(const aivc_conv_params &p);
+bool conv2d_mfma_addressable(const aivc_conv_params &p);  // what the kernels can index: the limit of AIVC_ALGO_MFMA
+bool conv2d_mfma_supported(const aivc_conv_params &p);    // ... and what AUTO sends there
 bool conv2d_mfma_tail_supported(const aivc_conv_params &p);
 int conv2d_mfma_variant(const aivc_conv_params &p);
 bool conv2d_bf16x3_supported(const aivc_conv_params &p);  // conv_bf16x3.hip: the precision mode (aivc_conv_params.precision = 1)

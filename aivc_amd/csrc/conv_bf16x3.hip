@@ -19,18 +19,17 @@ bool conv2d_bf16x3_supported(const aivc_conv_params &p) {
   // on the fp32 kernels' small tiles (measured: 109-121 TFLOP/s fp32-equivalent against 125-133 there)
   const int taps = p.mode == AIVC_MODE_TCONV ? (p.ksize * p.ksize + 3) / 4 : p.ksize * p.ksize;
   if (taps * p.c_in < 512) return false;
-  if ((uint64_t)p.c_out * p.ksize * p.ksize * p.c_in * 4ull >= 0xFFFFFFFFull || (uint64_t)p.ksize * p.ksize * p.c_in >= 65536ull) return false;
-  return (uint64_t)p.h_in * p.w_in * p.c_in * 4ull < 0xFFFFFFF0ull;  // one image inside the loader's 32-bit byte offsets
+  if ((uint64_t)p.ksize * p.ksize * p.c_in >= 65536ull) return false;
+  // one image and the weights inside the loader's 32-bit byte offsets
+  return loader_addressable((uint64_t)p.h_in * p.w_in * p.c_in * 4ull) && loader_addressable((uint64_t)p.c_out * p.ksize * p.ksize * p.c_in * 4ull);
 }
 
-template <int MODE, int PREC>
-static int launch_bf16x3_prec(const aivc_conv_params &p, hipStream_t s) {
-  if (p.c_out == 64) return p.gdn ? launch_cfg2<MODE, 4, 1, 2, 2, true, true, false, true, PREC>(p, s)
-                                  : launch_cfg2<MODE, 4, 1, 2, 2, false, true, false, true, PREC>(p, s);
-  return p.gdn ? launch_cfg2<MODE, 2, 2, 2, 2, true, true, false, true, PREC>(p, s)
-               : launch_cfg2<MODE, 2, 2, 2, 2, false, true, false, true, PREC>(p, s);
+// weights split ahead of the launch (aivc_split_weights_bf16x3) or by the K loop: the same terms, the same bits
+static bool split_ahead(const aivc_conv_params &p) {
+  return p.w_bf16x3 != nullptr && loader_addressable((uint64_t)p.c_out * p.ksize * p.ksize * p.c_in * 6ull);
 }
-// Tile of a launch of the mode (the ids of aivc_conv2d_variant: 0 = 128x128, 2 = 256x64, 5 = 64x128, 6 = 128x64).  Weights
+
+// Tile of a launch of the mode (ids of TILE_MENU).  Weights
 // split in the K loop: wave tile 64x64 (the split is 44 vector instructions per fragment: smaller wave tiles are bound
 // by it).  Weights split ahead (w_bf16x3): measured per layer class on the bench's shapes (tools/bf16x3_probe.py,
 // TFLOP/s fp32-equivalent, in-loop | 64x64 wave tile | 32x64 wave tile): conv to 128 channels 163-181 | 174-204 | 161-182,
@@ -38,29 +37,40 @@ static int launch_bf16x3_prec(const aivc_conv_params &p, hipStream_t s) {
 // grows to 88 KB with the three weight planes: one workgroup per CU).
 int conv2d_bf16x3_tile(const aivc_conv_params &p) {
   static const int force = getenv("AIVC_BF16X3_TILE") ? atoi(getenv("AIVC_BF16X3_TILE")) : 0;  // tuning aid: 1 = wave tile 64x64 everywhere
-  const bool ahead = p.w_bf16x3 != nullptr && (uint64_t)p.c_out * p.ksize * p.ksize * p.c_in * 6ull < 0xFFFFFFFFull;
   if (p.tail_c_out) return 6;  // fused tail: 128x64 either way (64 rows of 128 tail channels per wave would not fit the registers)
-  if (!ahead || force == 1) return p.c_out == 64 ? 2 : 0;
+  if (!split_ahead(p) || force == 1) return p.c_out == 64 ? 2 : 0;
   if (p.c_out == 64) return 6;
   return p.mode == AIVC_MODE_TCONV ? 5 : 0;
 }
 
+// The mode's tiles are those of TILE_MENU, except that its 128x64 stacks the four waves along M (wave tile 32x64).
+constexpr ConvTile bf16x3_tile(int id) { return id == 6 ? ConvTile{6, 4, 1, 1, 2, false} : TILE_MENU[tile_index(id)]; }
+
+// one tile of the mode, with or without fused (I)GDN
+template <int MODE, int PREC, int ID>
+static int launch_bf16x3_tile(const aivc_conv_params &p, hipStream_t s) {
+  constexpr ConvTile t = bf16x3_tile(ID);
+  return p.gdn ? launch_cfg2<MODE, t.wm, t.wn, t.tm, t.tn, true, true, false, PREC>(p, s)
+               : launch_cfg2<MODE, t.wm, t.wn, t.tm, t.tn, false, true, false, PREC>(p, s);
+}
+
+template <int MODE, int PREC>
+static int launch_bf16x3_prec(const aivc_conv_params &p, hipStream_t s) {
+  if constexpr (MODE == AIVC_MODE_CONV) {
+    constexpr ConvTile t = bf16x3_tile(6);
+    if (p.tail_c_out) return launch_cfg2<MODE, t.wm, t.wn, t.tm, t.tn, false, true, true, PREC>(p, s);
+  }
+  const int tile = conv2d_bf16x3_tile(p);
+  if constexpr (PREC == 2) {  // the 32x64 wave tiles: instantiated for weights split ahead only
+    if (tile == 6) return launch_bf16x3_tile<MODE, 2, 6>(p, s);
+    if (tile == 5) return launch_bf16x3_tile<MODE, 2, 5>(p, s);
+  }
+  return tile == 2 ? launch_bf16x3_tile<MODE, PREC, 2>(p, s) : launch_bf16x3_tile<MODE, PREC, 0>(p, s);
+}
+
 template <int MODE>
 static int launch_bf16x3(const aivc_conv_params &p, hipStream_t s) {
-  // weights split ahead of the launch (aivc_split_weights_bf16x3) or by the K loop: the same terms, the same bits
-  const bool ahead = p.w_bf16x3 != nullptr && (uint64_t)p.c_out * p.ksize * p.ksize * p.c_in * 6ull < 0xFFFFFFFFull;
-  if constexpr (MODE == AIVC_MODE_CONV) {
-    if (p.tail_c_out) return ahead ? launch_cfg2<MODE, 4, 1, 1, 2, false, true, true, true, 2>(p, s)
-                                   : launch_cfg2<MODE, 4, 1, 1, 2, false, true, true, true, 1>(p, s);
-  }
-  if (!ahead) return launch_bf16x3_prec<MODE, 1>(p, s);
-  switch (conv2d_bf16x3_tile(p)) {
-    case 6: return p.gdn ? launch_cfg2<MODE, 4, 1, 1, 2, true, true, false, true, 2>(p, s)
-                         : launch_cfg2<MODE, 4, 1, 1, 2, false, true, false, true, 2>(p, s);
-    case 5: return p.gdn ? launch_cfg2<MODE, 2, 2, 1, 2, true, true, false, true, 2>(p, s)
-                         : launch_cfg2<MODE, 2, 2, 1, 2, false, true, false, true, 2>(p, s);
-    default: return launch_bf16x3_prec<MODE, 2>(p, s);
-  }
+  return split_ahead(p) ? launch_bf16x3_prec<MODE, 2>(p, s) : launch_bf16x3_prec<MODE, 1>(p, s);
 }
 
 __global__ __launch_bounds__(256) void split_weights_kernel(const float *__restrict__ w, size_t pairs, int k_total, uint32_t *__restrict__ out) {
@@ -85,22 +95,9 @@ int split_weights_bf16x3(const float *w, int c_out, int k_total, void *out, hipS
 
 int conv2d_bf16x3(const aivc_conv_params &p, hipStream_t s) {
   if (!conv2d_bf16x3_supported(p)) return AIVC_ERR_UNSUPPORTED;
-  // a batch beyond the 4 GB the loader addresses goes out as sub-batches (images are independent)
-  const uint64_t per_image = (uint64_t)p.h_in * p.w_in * p.c_in * 4ull;
-  const int chunk = (int)(0xFFFFFFF0ull / per_image);
-  for (int n0 = 0; n0 < p.n; n0 += chunk) {
-    aivc_conv_params q = p;
-    q.n = p.n - n0 < chunk ? p.n - n0 : chunk;
-    const size_t in_off = (size_t)n0 * p.h_in * p.w_in * p.c_in;
-    const size_t out_off = (size_t)n0 * p.h_out * p.w_out * (p.tail_c_out ? p.tail_c_out : p.c_out);  // (fused tail: y and res are the tail's)
-    q.x = p.x + in_off;
-    q.y = p.y + out_off;
-    if (p.res) q.res = p.res + out_off;
-    if (p.mul) q.mul = p.mul + out_off;
-    const int rc = p.mode == AIVC_MODE_CONV ? launch_bf16x3<AIVC_MODE_CONV>(q, s) : launch_bf16x3<AIVC_MODE_TCONV>(q, s);
-    if (rc) return rc;
-  }
-  return AIVC_OK;
+  return for_sub_batches(p, [&](const aivc_conv_params &q) {
+    return p.mode == AIVC_MODE_CONV ? launch_bf16x3<AIVC_MODE_CONV>(q, s) : launch_bf16x3<AIVC_MODE_TCONV>(q, s);
+  });
 }
 
 }  // namespace aivc

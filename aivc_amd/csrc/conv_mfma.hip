@@ -1,40 +1,26 @@
-// conv_mfma.hip -- fp32 dispatch of the implicit-GEMM convolution family (kernel: conv_mfma_kernel.h): the tile menu,
-// the choice between the LDS-DMA and the register-staged K loop, sub-batching beyond 4 GB.
+// conv_mfma.hip -- fp32 dispatch of the implicit-GEMM convolution family (kernel: conv_mfma_kernel.h): the tile rules,
+// what the kernels can address, sub-batching beyond 4 GB.
+#include <utility>
+
 #include "conv_mfma_kernel.h"
 
 namespace aivc {
 
-// LDS-DMA K loop: conv with c_in % 32 == 0 on the tiles it is instantiated for; per-lane BYTE offsets are 32 bits
-static bool use_glds(const aivc_conv_params &p) {
-  if (p.mode != AIVC_MODE_CONV && p.mode != AIVC_MODE_TCONV) return false;
-  if (p.c_in % BK != 0 && p.mode != AIVC_MODE_CONV) return false;  // generic K: conv only
-  return (uint64_t)p.n * p.h_in * p.w_in * p.c_in * 4ull < 0xFFFFFFFFull && (uint64_t)p.c_out * p.ksize * p.ksize * p.c_in * 4ull < 0xFFFFFFFFull;
-}
-
-template <int MODE, int WM, int WN, int TM, int TN, bool FUSE>
+// one tile of the menu: the reduction is a run of whole K tiles (c_in % 32 == 0) or generic
+template <int MODE, int T, bool FUSE>
 static int launch_cfg(const aivc_conv_params &p, hipStream_t s) {
-  // every tile of the menu except 256x128 (96 KB of ring: one workgroup per CU)
-  if constexpr ((MODE == AIVC_MODE_CONV || MODE == AIVC_MODE_TCONV) && 32 * WM * TM + 32 * WN * TN <= 320) {
-    if (use_glds(p)) {
-      if (p.c_in % BK == 0) return launch_cfg2<MODE, WM, WN, TM, TN, FUSE, true, false, true>(p, s);
-      if constexpr (MODE == AIVC_MODE_CONV && !(WM == 4 && TM == 2)) return launch_cfg2<MODE, WM, WN, TM, TN, FUSE, false, false, true>(p, s);
-    }
-  }
-  if (p.c_in % BK == 0) return launch_cfg2<MODE, WM, WN, TM, TN, FUSE, true>(p, s);
-  if constexpr (WM == 4 && TM == 2) return AIVC_ERR_UNSUPPORTED;  // pick_tile never sends a generic reduction here
-  else return launch_cfg2<MODE, WM, WN, TM, TN, FUSE, false>(p, s);
+  constexpr ConvTile t = TILE_MENU[T];
+  if (p.c_in % BK == 0) return launch_cfg2<MODE, t.wm, t.wn, t.tm, t.tn, FUSE, true>(p, s);
+  if constexpr (!t.generic_k) return AIVC_ERR_UNSUPPORTED;  // pick_tile never sends a generic reduction here
+  else return launch_cfg2<MODE, t.wm, t.wn, t.tm, t.tn, FUSE, false>(p, s);
 }
 
-// tile menu {BM x BN}: id 0 = 128x128, 1 = 64x64, 2 = 256x64, 3 = 128x32, (4 = 256x128: retired), 5 = 64x128, 6 = 128x64
 static int pick_tile_auto(const aivc_conv_params &p);
 static int pick_tile(const aivc_conv_params &p) {
-  // tuning aid: AIVC_FORCE_TILE=<id> overrides the choice when that tile can run the shape
+  // tuning aid: AIVC_FORCE_TILE=<id of TILE_MENU> overrides the choice when that tile can run the shape
   if (const char *e = getenv("AIVC_FORCE_TILE")) {
-    const int t = atoi(e);
-    const int bn = t == 0 || t == 5 ? 128 : (t == 3 ? 32 : 64);
-    // (id 4 = 256x128 left the menu in round 3: never chosen since round 2, and it spilled; the 256-row tile is
-    // instantiated for c_in % 32 == 0 only -- its generic loader spilled 700 bytes)
-    if (t >= 0 && t <= 6 && t != 4 && (t != 2 || p.c_in % BK == 0) && (!p.gdn || bn == p.c_out)) return t;
+    const int i = tile_index(atoi(e));
+    if (i >= 0 && (TILE_MENU[i].generic_k || p.c_in % BK == 0) && (!p.gdn || TILE_MENU[i].bn() == p.c_out)) return TILE_MENU[i].id;
   }
   return pick_tile_auto(p);
 }
@@ -109,29 +95,20 @@ static int pick_tile_auto(const aivc_conv_params &p) {
   return tile;
 }
 
+// the ladder over TILE_MENU: every tile, with and without fused (I)GDN (the GDN mode itself has nothing to fuse)
+template <int MODE, bool FUSE, int... T>
+static int launch_tile(int tile, const aivc_conv_params &p, hipStream_t s, std::integer_sequence<int, T...>) {
+  int rc = AIVC_ERR_UNSUPPORTED;
+  (void)((TILE_MENU[T].id == tile && ((rc = launch_cfg<MODE, T, FUSE>(p, s)), true)) || ...);
+  return rc;
+}
 template <int MODE>
 static int launch_mode(const aivc_conv_params &p, hipStream_t s) {
-  const int tile = pick_tile(p);
+  constexpr auto menu = std::make_integer_sequence<int, N_TILES>();
   if constexpr (MODE != AIVC_MODE_GDN) {
-    if (p.gdn) {
-      switch (tile) {
-        case 0: return launch_cfg<MODE, 2, 2, 2, 2, true>(p, s);
-        case 1: return launch_cfg<MODE, 2, 2, 1, 1, true>(p, s);
-        case 2: return launch_cfg<MODE, 4, 1, 2, 2, true>(p, s);
-        case 5: return launch_cfg<MODE, 2, 2, 1, 2, true>(p, s);
-        case 6: return launch_cfg<MODE, 2, 2, 2, 1, true>(p, s);
-        default: return launch_cfg<MODE, 4, 1, 1, 1, true>(p, s);
-      }
-    }
+    if (p.gdn) return launch_tile<MODE, true>(pick_tile(p), p, s, menu);
   }
-  switch (tile) {
-    case 0: return launch_cfg<MODE, 2, 2, 2, 2, false>(p, s);
-    case 1: return launch_cfg<MODE, 2, 2, 1, 1, false>(p, s);
-    case 2: return launch_cfg<MODE, 4, 1, 2, 2, false>(p, s);
-    case 5: return launch_cfg<MODE, 2, 2, 1, 2, false>(p, s);
-    case 6: return launch_cfg<MODE, 2, 2, 2, 1, false>(p, s);
-    default: return launch_cfg<MODE, 4, 1, 1, 1, false>(p, s);
-  }
+  return launch_tile<MODE, false>(pick_tile(p), p, s, menu);
 }
 
 // fused 1x1 tail: a conv with c_out = 64 (one 128x64 tile owns every channel of its pixels), TAIL_N tail channels,
@@ -148,49 +125,35 @@ int conv2d_mfma_variant(const aivc_conv_params &p) {
   return 100 + 10 * mode + pick_tile(p) + (p.gdn ? 50 : 0);
 }
 
-bool conv2d_mfma_supported(const aivc_conv_params &p) {
-  if (p.gdn && p.c_out != 32 && p.c_out != 64 && p.c_out != 128) return false;
-  // thin outputs (c_out of 3 / 6): N is padded to 32, still ~6x faster than the scalar kernel once
-  // the reduction is long; tiny reductions stay scalar
-  if (p.c_out < 16 && p.c_in * p.ksize * p.ksize < 256) return false;
+// what the kernels can index and address (ALGO_MFMA is held to this too)
+bool conv2d_mfma_addressable(const aivc_conv_params &p) {
   // 32-bit element offsets inside the kernel
   const uint64_t in_elems = (uint64_t)p.n * p.h_in * p.w_in * p.c_in;
   const uint64_t w_elems = (uint64_t)p.c_out * p.ksize * p.ksize * p.c_in;
   if (in_elems >= 0xFFFFFFFFull || w_elems >= 0xFFFFFFFFull) return false;
   if ((uint64_t)p.ksize * p.ksize * p.c_in >= 65536ull) return false;
+  // the LDS-DMA loop's 32-bit BYTE offsets: ONE image's input (a larger batch goes out as sub-batches) and the weights.
+  // These modes have no other MFMA loop: the router sends a larger tensor to the scalar kernel.  No codec tensor comes
+  // near (an 8K frame's half-resolution 64-channel map is 2.1 GB).
+  if (lds_dma_loop(p.mode, p.c_in % BK == 0) &&
+      !(loader_addressable((uint64_t)p.h_in * p.w_in * p.c_in * 4ull) && loader_addressable(w_elems * 4ull)))
+    return false;
   return true;
 }
 
-// byte size of the input tensor / of the weights as the LDS-DMA loader addresses them (32-bit byte offsets)
-static bool glds_sizes_ok(const aivc_conv_params &p) {
-  return (uint64_t)p.n * p.h_in * p.w_in * p.c_in * 4ull < 0xFFFFFFFFull;
+bool conv2d_mfma_supported(const aivc_conv_params &p) {
+  if (p.gdn && p.c_out != 32 && p.c_out != 64 && p.c_out != 128) return false;
+  // thin outputs (c_out of 3 / 6): N is padded to 32, still ~6x faster than the scalar kernel once
+  // the reduction is long; tiny reductions stay scalar
+  if (p.c_out < 16 && p.c_in * p.ksize * p.ksize < 256) return false;
+  return conv2d_mfma_addressable(p);
 }
 
-int conv2d_mfma(const aivc_conv_params &p, hipStream_t s) {
-  // a batch whose input exceeds the 4 GB the LDS-DMA loader can address goes out as several launches over
-  // sub-batches (images are independent; same kernels, same results)
-  if ((p.mode == AIVC_MODE_CONV || (p.mode == AIVC_MODE_TCONV && p.c_in % BK == 0)) && p.n > 1 && !glds_sizes_ok(p)) {
-    const uint64_t per_image = (uint64_t)p.h_in * p.w_in * p.c_in * 4ull;
-    int chunk = (int)(0xFFFFFFF0ull / per_image);
-    if (chunk >= 1) {
-      const int c_y = p.tail_c_out ? p.tail_c_out : p.c_out;
-      for (int n0 = 0; n0 < p.n; n0 += chunk) {
-        aivc_conv_params q = p;
-        q.n = p.n - n0 < chunk ? p.n - n0 : chunk;
-        const size_t in_off = (size_t)n0 * p.h_in * p.w_in * p.c_in, out_off = (size_t)n0 * p.h_out * p.w_out * c_y;
-        q.x = p.x + in_off;
-        q.y = p.y + out_off;
-        if (p.res) q.res = p.res + out_off;
-        if (p.mul) q.mul = p.mul + out_off;
-        if (const int rc = conv2d_mfma(q, s)) return rc;
-      }
-      return AIVC_OK;
-    }
-  }
+static int launch_one(const aivc_conv_params &p, hipStream_t s) {
   if (p.tail_c_out) {
     if (!conv2d_mfma_tail_supported(p)) return AIVC_ERR_UNSUPPORTED;
-    if (use_glds(p)) return launch_cfg2<AIVC_MODE_CONV, 2, 2, 2, 1, false, true, true, true>(p, s);
-    return launch_cfg2<AIVC_MODE_CONV, 2, 2, 2, 1, false, true, true>(p, s);
+    constexpr ConvTile t = TILE_MENU[tile_index(6)];
+    return launch_cfg2<AIVC_MODE_CONV, t.wm, t.wn, t.tm, t.tn, false, true, true>(p, s);
   }
   switch (p.mode) {
     case AIVC_MODE_CONV: return launch_mode<AIVC_MODE_CONV>(p, s);
@@ -199,6 +162,11 @@ int conv2d_mfma(const aivc_conv_params &p, hipStream_t s) {
     case AIVC_MODE_IGDN: return launch_mode<AIVC_MODE_GDN>(p, s);
     default: return AIVC_ERR_UNSUPPORTED;
   }
+}
+
+int conv2d_mfma(const aivc_conv_params &p, hipStream_t s) {
+  if (!lds_dma_loop(p.mode, p.c_in % BK == 0)) return launch_one(p, s);  // register-staged: 32-bit ELEMENT offsets, one launch
+  return for_sub_batches(p, [&](const aivc_conv_params &q) { return launch_one(q, s); });
 }
 
 }  // namespace aivc

@@ -73,6 +73,10 @@ __device__ __forceinline__ void bf16x3_split2(float x0, float x1, uint32_t &h, u
   l = pk(q0, q1);
 }
 
+// The K loop of an instantiation follows from its mode and reduction: conv stages its operands by LDS-DMA (any c_in % 4 == 0),
+// transposed conv does with c_in % 32 == 0 (FASTK), and is register-staged otherwise, as the (I)GDN mode always is.
+constexpr bool lds_dma_loop(int mode, bool fastk) { return mode == AIVC_MODE_CONV || (mode == AIVC_MODE_TCONV && fastk); }
+
 // PREC: 0 = the fp32 arithmetic contract (v_mfma_f32_32x32x2_f32, fixed-order fmaf chains); 1 = "bf16x3" (round 5, a
 // precision MODE, never the default): every fp32 operand is split exactly into three bf16 terms x = h + m + l and a
 // product a * b is the six bf16 MFMA products h h', h m', m h', m m', h l', l h' with fp32 accumulation
@@ -82,11 +86,12 @@ __device__ __forceinline__ void bf16x3_split2(float x0, float x1, uint32_t &h, u
 // PREC 2 = PREC 1 with the weights split ahead of the launch (aivc_conv_params.w_bf16x3): the B side of a stage is three
 // bf16 planes of [BN rows][32 k] (64 bytes per row and plane), fetched by the same LDS-DMA, and a fragment is one
 // ds_read_b128 per term; the same terms in the same products as PREC 1, so the same bits.
-template <int MODE, int WM, int WN, int TM, int TN, bool FUSE, bool FASTK, bool TAIL = false, bool GLDS = false, int PREC = 0>
+template <int MODE, int WM, int WN, int TM, int TN, bool FUSE, bool FASTK, bool TAIL = false, int PREC = 0>
 __global__ __launch_bounds__(256, (PREC ? 1 : (TAIL ? AIVC_TAIL_WAVES : (TM * TN >= 8 ? 2 : (FUSE && TM * TN == 2 && WN == 2 && TM == 2 ? 3 : 1))))) void conv_mfma_kernel(MfmaArgs a) {
   constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
   static_assert(!TAIL || (MODE == AIVC_MODE_CONV && !FUSE && FASTK && BN == 64 && BN % BK == 0), "fused tail: conv, c_out 64");
-  static_assert(PREC == 0 || (GLDS && FASTK), "bf16x3: the LDS-DMA loop with c_in % 32 == 0");
+  constexpr bool GLDS = lds_dma_loop(MODE, FASTK);
+  static_assert(PREC == 0 || (MODE != AIVC_MODE_GDN && FASTK), "bf16x3: the LDS-DMA loop with c_in % 32 == 0");
   constexpr int UA = BM * OCT / 256;          // (row, octet) units per thread for A
   constexpr int UB = (BN * OCT + 255) / 256;  // ... for B
   constexpr bool B_FULL = (BN * OCT) % 256 == 0;  // every thread stages a B unit: no exec masking
@@ -1243,9 +1248,10 @@ extern "C" __attribute__((visibility("default"))) int aivc_dbg_dump(unsigned lon
 }
 #endif
 
-template <int MODE, int WM, int WN, int TM, int TN, bool FUSE, bool FASTK, bool TAIL = false, bool GLDS = false, int PREC = 0>
+template <int MODE, int WM, int WN, int TM, int TN, bool FUSE, bool FASTK, bool TAIL = false, int PREC = 0>
 static int launch_cfg2(const aivc_conv_params &p, hipStream_t s) {
   constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
+  constexpr bool GLDS = lds_dma_loop(MODE, FASTK);
   MfmaArgs a;
   a.p = p;
   a.M = MODE == AIVC_MODE_TCONV ? p.n * p.h_in * p.w_in : p.n * p.h_out * p.w_out;
@@ -1262,11 +1268,58 @@ static int launch_cfg2(const aivc_conv_params &p, hipStream_t s) {
   if (PREC == 2 && lds < (size_t)2 * (BM * BK * 4 + BN * 192)) lds = (size_t)2 * (BM * BK * 4 + BN * 192);
   if (lds > 64 * 1024) {
     static LdsOptIn opt_in;  // per instantiation, per device
-    if (!opt_in.raise(reinterpret_cast<const void *>(&conv_mfma_kernel<MODE, WM, WN, TM, TN, FUSE, FASTK, TAIL, GLDS, PREC>), lds))
+    if (!opt_in.raise(reinterpret_cast<const void *>(&conv_mfma_kernel<MODE, WM, WN, TM, TN, FUSE, FASTK, TAIL, PREC>), lds))
       return check_launch("conv_mfma lds attribute");
   }
-  hipLaunchKernelGGL((conv_mfma_kernel<MODE, WM, WN, TM, TN, FUSE, FASTK, TAIL, GLDS, PREC>), grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((conv_mfma_kernel<MODE, WM, WN, TM, TN, FUSE, FASTK, TAIL, PREC>), grid, dim3(256), lds, s, a);
   return check_launch("conv_mfma");
+}
+
+// The tile menu: id (the last digit of aivc_conv2d_variant's codes, AIVC_FORCE_TILE) -> WM x WN waves of TM x TN
+// accumulators of 32x32 each, a workgroup tile of BM x BN = 32 WM TM x 32 WN TN.  generic_k: also instantiated for
+// c_in % 32 != 0 (the 256-row tile's generic loader spilled 700 bytes).  Id 4 (256x128) left the menu in round 3: never
+// chosen since round 2, and it spilled.  The dispatch ladders and the AIVC_FORCE_TILE rule are derived from this table.
+struct ConvTile {
+  int id, wm, wn, tm, tn;
+  bool generic_k;
+  constexpr int bm() const { return 32 * wm * tm; }
+  constexpr int bn() const { return 32 * wn * tn; }
+};
+constexpr ConvTile TILE_MENU[] = {
+    {0, 2, 2, 2, 2, true},   // 128x128
+    {1, 2, 2, 1, 1, true},   // 64x64
+    {2, 4, 1, 2, 2, false},  // 256x64
+    {3, 4, 1, 1, 1, true},   // 128x32
+    {5, 2, 2, 1, 2, true},   // 64x128
+    {6, 2, 2, 2, 1, true},   // 128x64
+};
+constexpr int N_TILES = sizeof(TILE_MENU) / sizeof(TILE_MENU[0]);
+constexpr int tile_index(int id) {  // position in TILE_MENU, -1: no such tile
+  for (int i = 0; i < N_TILES; ++i)
+    if (TILE_MENU[i].id == id) return i;
+  return -1;
+}
+
+// A batch whose input exceeds what the LDS-DMA loader addresses (LOADER_MAX_BYTES) goes out as several launches over
+// sub-batches: images are independent, so the same kernels give the same results.  launch(q) runs one sub-batch; x, y,
+// res and mul move with it (fused tail: y and res are the tail's).
+template <class Launch>
+static int for_sub_batches(const aivc_conv_params &p, Launch launch) {
+  const uint64_t per_image = (uint64_t)p.h_in * p.w_in * p.c_in * 4ull;
+  const int chunk = (int)(LOADER_MAX_BYTES / per_image);
+  if (chunk < 1) return AIVC_ERR_UNSUPPORTED;  // (the router declines such an image: conv2d_mfma_supported)
+  const int c_y = p.tail_c_out ? p.tail_c_out : p.c_out;
+  for (int n0 = 0; n0 < p.n; n0 += chunk) {
+    aivc_conv_params q = p;
+    q.n = p.n - n0 < chunk ? p.n - n0 : chunk;
+    const size_t in_off = (size_t)n0 * p.h_in * p.w_in * p.c_in, out_off = (size_t)n0 * p.h_out * p.w_out * c_y;
+    q.x = p.x + in_off;
+    q.y = p.y + out_off;
+    if (p.res) q.res = p.res + out_off;
+    if (p.mul) q.mul = p.mul + out_off;
+    if (const int rc = launch(q)) return rc;
+  }
+  return AIVC_OK;
 }
 
 }  // namespace aivc

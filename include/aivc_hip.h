@@ -198,7 +198,13 @@ static inline int aivc_winograd_covers(const aivc_conv_params *p) {
  *                  v = act1(v);  if (mul) v = mul * v;  if (res) v = v + res;  v = act2(v).
  * A fused-gdn or fused-tail request the kernels cannot honour (all output channels of a pixel must sit in one
  * workgroup tile: c_out of 64 or 128 on the MFMA path; tail: c_out 64 -> tail_c_out 128, c_in % 32 == 0) returns
- * AIVC_ERR_UNSUPPORTED; callers then issue the two launches (aivc_conv2d_variant tells in advance). */
+ * AIVC_ERR_UNSUPPORTED; callers then issue the two launches (aivc_conv2d_variant tells in advance).
+ * Size limit of the MFMA path: its conv and transposed-conv (c_in % 32 == 0) kernels address ONE image's input and the
+ * weights with 32-bit byte offsets (a batch beyond 4 GiB of smaller images is split into sub-batch launches inside the call).
+ * Where either reaches 4 GiB a plain launch takes the scalar kernel (64-bit indexing, the same bits; one thread per
+ * output value, so the runtime's own launch limits apply), a fused-gdn / fused-tail request and AIVC_ALGO_MFMA return
+ * AIVC_ERR_UNSUPPORTED.  The (I)GDN modes and transposed conv with c_in % 32 != 0 index ELEMENTS in 32 bits: below 2^32 - 1
+ * input elements over the batch. */
 int aivc_conv2d(const aivc_conv_params *p, aivc_stream_t stream);
 
 /* AIVC_PREC_FP32_WINO: U_p[co][ci], p = 4 i + j, = (G g G^T)[i][j] of the 3x3 kernel g[ky][kx] = w[co][ky][kx][ci], G = (1, 0, 0),
@@ -226,7 +232,7 @@ int aivc_split_weights_bf16x3(const float *w, int32_t c_out, int32_t k_total, vo
 
 /* Which kernel aivc_conv2d would launch for these parameters (no launch): 0 = scalar kernel,
  * 1 = thin-output VALU kernel (transposed conv to 3 / 6 channels), otherwise 100 + 10 * template-mode (0 conv, 1 tconv, 2 gdn) + tile id (0: 128x128, 1: 64x64,
- * 2: 256x64, 3: 128x32, 4: 256x128, 5: 64x128, 6: 128x64) + 50 with a fused gdn; 190 = conv with a fused 1x1 tail (191: aivc_conv_images).
+ * 2: 256x64, 3: 128x32, 5: 64x128, 6: 128x64; the table is TILE_MENU of csrc/conv_mfma_kernel.h) + 50 with a fused gdn; 190 = conv with a fused 1x1 tail (191: aivc_conv_images).
  * 1000 + that code: the launch the precision mode takes (AIVC_PREC_BF16X3; the tile depends on whether w_bf16x3 is given).
  * Negative = error code.  Used by bench.py to attribute launch times and by callers to ask whether a fusion is available. */
 int aivc_conv2d_variant(const aivc_conv_params *p);

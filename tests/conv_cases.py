@@ -56,6 +56,26 @@ CONV_CASES = [
     (abi.MODE_CONV, 5, 2, 2, 96, 160, 13, 9, 0, 0, False, False),
 ]
 
+# The register-staged K loop's own users, on every tile each is instantiated for (AIVC_FORCE_TILE ids; 2 = 256x64 exists for
+# c_in % 32 == 0 only): the (I)GDN mode with and without whole K tiles, transposed conv with c_in % 32 != 0.  Two images of
+# 9 x 13: M = 234 rows, a partial last tile for every BM.
+STAGED_CASES = [
+    # row as in CONV_CASES, tiles
+    ((abi.MODE_GDN, 1, 1, 0, 64, 64, 9, 13, 0, 0, False, False), (0, 1, 2, 3, 5, 6)),
+    ((abi.MODE_IGDN, 1, 1, 0, 64, 64, 9, 13, 0, 0, False, True), (0, 1, 2, 3, 5, 6)),
+    ((abi.MODE_GDN, 1, 1, 0, 36, 36, 9, 13, 0, 0, False, True), (0, 1, 3, 5, 6)),
+    ((abi.MODE_IGDN, 1, 1, 0, 36, 36, 9, 13, 0, 0, False, False), (0, 1, 3, 5, 6)),
+    ((abi.MODE_TCONV, 3, 2, 0, 8, 64, 9, 13, abi.ACT_LEAKY, 0, False, True), (0, 1, 3, 5, 6)),
+    ((abi.MODE_TCONV, 5, 2, 0, 8, 64, 9, 13, 0, 0, False, False), (0, 1, 3, 5, 6)),
+    ((abi.MODE_TCONV, 3, 2, 0, 12, 128, 9, 13, 0, 0, False, False), (0, 1, 3, 5, 6)),
+    ((abi.MODE_TCONV, 5, 2, 0, 12, 128, 9, 13, 0, abi.ACT_RELU, False, True), (0, 1, 3, 5, 6)),
+]
+# ... and with a fused (I)GDN (rows as in FUSED_GDN_CASES): the tiles whose BN is c_out
+STAGED_FUSED_GDN_CASES = [
+    ((abi.MODE_TCONV, 5, 2, 0, 8, 64, 9, 13, True, False), (1, 6)),
+    ((abi.MODE_TCONV, 3, 2, 0, 12, 128, 9, 13, False, True), (0, 5)),
+]
+
 THIN_WALK_GRIDS = [1, 3, 7]
 THIN_WALK_CASES = [(3, 5, 64, 21, 100), (6, 5, 64, 9, 70), (3, 3, 16, 13, 65)]  # co, k, ci, h, w
 

@@ -4,8 +4,8 @@ import pytest
 import torch
 
 from aivc_amd import abi
-from conv_cases import (CONV_CASES, CONV_IMAGES_CASES, FUSED_GDN_CASES, FUSED_TAIL_CASES, THIN_WALK_CASES, THIN_WALK_GRIDS, conv_case,
-                        conv_images_cases, fused_gdn_case, fused_tail_case, pack_images_cases, thin_walk_case)
+from conv_cases import (CONV_CASES, CONV_IMAGES_CASES, FUSED_GDN_CASES, FUSED_TAIL_CASES, STAGED_CASES, STAGED_FUSED_GDN_CASES, THIN_WALK_CASES,
+                        THIN_WALK_GRIDS, conv_case, conv_images_cases, fused_gdn_case, fused_tail_case, pack_images_cases, thin_walk_case)
 from op_cases import (FORCED, FRAME_BATCH_CASES, FRAME_SIZES, RANGE_CODER_CASES, WARP_SHAPES, T, cdf_case, eq, frame_batch_case, forced_case, frame_sources,
                       frame_to_yuv420_case, latent_ops_case, on, profiled, range_coder_case, range_coder_pmf_case, range_encode_case,
                       straddle_stream, warp_blend_case, warp_blend_sources, warp_case, yuv420_to_444_case, yuv_planes)
@@ -21,6 +21,22 @@ def test_conv_family_bit_exact(case, algo, oracle, cuda):
     from aivc_amd import ops
     c = conv_case(oracle, case, hash(case) % (2 ** 31))
     c.check(c.run(ops, on(cuda), algo=algo))
+
+
+@pytest.mark.parametrize('row,tiles', STAGED_CASES + STAGED_FUSED_GDN_CASES)
+def test_register_staged_k_loop_on_every_tile(row, tiles, oracle, cuda, monkeypatch):
+    """The register-staged K loop is what the (I)GDN mode and transposed conv with c_in % 32 != 0 run on (conv and transposed
+    conv with whole K tiles have the LDS-DMA loop only): each of them through ALGO_MFMA on every tile it is instantiated for,
+    the launch's variant code asserted, bit exact against the oracle (computed once per row)."""
+    from aivc_amd import ops
+    fused = len(row) == 10
+    c = (fused_gdn_case if fused else conv_case)(oracle, row, abs(hash(row)) % (2 ** 31))
+    digit = {abi.MODE_CONV: 0, abi.MODE_TCONV: 1, abi.MODE_GDN: 2, abi.MODE_IGDN: 2}[row[0]]
+    for tile in tiles:
+        monkeypatch.setenv('AIVC_FORCE_TILE', str(tile))
+        got, codes = profiled(lambda: c.run(ops, on(cuda), algo=abi.ALGO_MFMA))
+        assert codes == [100 + 10 * digit + tile + (50 if fused else 0)], (tile, codes)
+        c.check(got)
 
 
 @pytest.mark.parametrize('grid', THIN_WALK_GRIDS)

@@ -86,6 +86,50 @@ def test_conv_dispatch_of_the_default_model_at_1080p():
         assert got == r[16:], (r[:16], got, r[16:])
 
 
+def _variant(mode, k, s, pad, n, h, w, ci, co, gdn=0, tail=0, algo=None):
+    """aivc_conv2d_variant of one fp32 launch with stand-in pointers (nothing is allocated, nothing launched)"""
+    from aivc_amd import _lib, abi
+    a = 1 << 20
+    ho, wo = abi.conv_out_size(mode, h, w, k, s, pad)
+    p = abi.ConvParams(mode, k, s, pad, n, h, w, ci, ho, wo, co, 0, 0, abi.ALGO_AUTO if algo is None else algo, gdn, 0, a, 2 * a, 3 * a,
+                       None, None, 6 * a, 7 * a if gdn else None, 8 * a if gdn else None)
+    if tail:
+        p.tail_w, p.tail_bias, p.tail_c_out = 9 * a, 10 * a, tail
+    p.precision = abi.PREC_FP32
+    return _lib.load()['aivc_conv2d_variant'](ctypes.byref(p))
+
+
+def test_conv_dispatch_at_the_loaders_4_gib_limit():
+    """The LDS-DMA K loop (conv; transposed conv with c_in % 32 == 0) addresses ONE image's input and the weights with 32-bit
+    byte offsets, and no other MFMA kernel is built for these modes: at 4 GiB per image a plain launch takes the scalar kernel
+    (64-bit indexing, same bits) and a fused request is declined (the caller issues two launches).  A batch beyond 4 GiB
+    of smaller images is sub-batched as before, and the register-staged families keep their 2^32-ELEMENT limit."""
+    from aivc_amd import abi
+    conv = (abi.MODE_CONV, 3, 1, 1)
+    at = conv + (1, 4096, 4096, 64, 64)  # 4096 * 4096 * 64 * 4 bytes = 4 GiB exactly
+    assert 4096 * 4096 * 64 * 4 == 1 << 32
+    assert _variant(*at) == 0
+    assert _variant(*at, gdn=1) == abi.ERR_UNSUPPORTED
+    assert _variant(*at, tail=128) == abi.ERR_UNSUPPORTED
+    assert _variant(*at, algo=abi.ALGO_MFMA) == abi.ERR_UNSUPPORTED
+    below = conv + (1, 4095, 4096, 64, 64)
+    assert 100 <= _variant(*below) <= 109
+    assert 150 <= _variant(*below, gdn=1) <= 159
+    assert _variant(*below, tail=128) == 190
+    # two images of 2.5 GiB: sub-batches of one image each, the same kernel as ever
+    assert _variant(*conv, 2, 2560, 4096, 64, 64) == 102
+    # transposed conv, c_in % 32 == 0: the same limit
+    tconv = (abi.MODE_TCONV, 5, 2, 0)
+    assert _variant(*tconv, 1, 4095, 4096, 64, 64) == 111
+    assert _variant(*tconv, 1, 4096, 4096, 64, 64) == 0
+    assert _variant(*tconv, 1, 4096, 4096, 64, 64, gdn=2) == abi.ERR_UNSUPPORTED
+    # transposed conv with a generic reduction is register-staged: element offsets, no byte limit
+    assert _variant(*tconv, 1, 4096, 4096, 48, 64) == 111
+    assert 4096 * 8192 * 48 * 4 > 1 << 32 and 4096 * 8192 * 48 < (1 << 32) - 1
+    assert _variant(*tconv, 1, 4096, 8192, 48, 64) == 111
+    assert _variant(*tconv, 1, 4096, 8192, 48, 64, gdn=2) == 161
+
+
 def test_product_path_refuses_cpu_tensors():
     from aivc_amd import ops
     from aivc_amd._lib import AivcNativeError

@@ -29,8 +29,12 @@
 //                  the barrier re-aligns the waves, so the offset is made again in every chunk.  There the raw pixels of a
 //                  transform step are also read BEFORE the pair's MFMAs and combined behind them (4 float4 in flight), and the
 //                  transform has no run-time flag.  3x3 128 -> 128: 6-10 % per launch (experiments/wino_phases.md).  The 5x5
-//                  forms keep both heads at the barrier: the second copy of their issue code (phase / class address
-//                  arithmetic) costs registers they do not have, measured 0 ... +5 % slower at either offset and either half.
+//                  forms (experiments/wino5_issue.md) run the same transform: every step in every chunk, read early -- a V
+//                  position whose U is zero by construction is computed and never read (4-6 % per launch: the eight flag tests
+//                  per chunk and wave and all scratch gone).  The polyphase form is offset as well: its issue is split into
+//                  prepare() (every wave at the chunk head: all address arithmetic) and fire() (the DMA instructions alone,
+//                  placed by position half), so that the offset costs no second copy of the arithmetic.  The transposed form
+//                  keeps both heads at the barrier: offset behind pair 0 it measured +8 %, behind pair 2 null.
 #include <stdlib.h>
 
 #include "mfma_util.h"
@@ -192,7 +196,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     if constexpr (TC) return ((pc >> 1) && i == 0) || ((pc & 1) && j == 0);
     return false;
   };
-  auto phase_or_class = [&](const Desc &d_, int c) -> int { return POLY ? c >> cpp_shift : (TC ? d_.cb / a.gy : 0); };
+  auto phase_or_class = [&](const Desc &d_, int c) -> int {
+    return POLY ? c >> cpp_shift : (TC ? d_.cb / a.gy : 0);
+  };
   auto issue_u = [&](const Desc &d_, int c) {  // chunk c of block d_ -> U stage c & 1: a straight copy of the chunk image
     const float *src = MODE != 0 ? uniform_ptr(d_.ubase + (size_t)c * (WINO_U_STAGE / 4)) : d_.ubase + (size_t)c * (WINO_U_STAGE / 4);
     const uint32_t d = MODE != 0 ? __builtin_amdgcn_readfirstlane(u_dst + (uint32_t)((c & 1) * WINO_U_STAGE)) : u_dst + (uint32_t)((c & 1) * WINO_U_STAGE);
@@ -222,6 +228,73 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
                    "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
                    "global_load_lds_dwordx4 %0, %1 offset:3072"
                    : : "v"(u_off), "s"(src), "s"(d) : "memory", "m0");
+    }
+  };
+
+  // polyphase form: the issue of a chunk in two parts.  prepare(kb, cr, cu), run by every wave at the chunk head, does everything
+  // of the issue of raw chunk cr and U chunk cu (of this workgroup's block kb, possibly beyond its chunks: the next block's first
+  // ones) that is no DMA instruction: cur or nxt, the per-lane patch offsets on phase entry, the wave-uniform sources, which
+  // pieces are issued.  fire_raw / fire_u hold the DMA instructions alone, under their guards (the LDS stage is the caller's
+  // compile-time constant), so that placing them by position half costs no second copy of the address arithmetic.
+  struct Prep {
+    const float *r_src, *u_src;  // wave-uniform sources: the raw chunk, the U chunk image
+    uint32_t flags;              // 1: the raw chunk is issued; 2 / 4: the lo / hi pieces of the U image are
+  };
+  auto prepare = [&](uint32_t kb, int cr, int cu) -> Prep {
+    Prep q;
+    const bool more = kb + 1u < n_mine;
+    uint32_t fl = 0u;
+    {
+      const bool own = cr < nch;
+      const int c = own ? cr : cr - nch;
+      const Desc &d_ = own ? cur : nxt;
+      if (own || more) {
+        fl |= 1u;
+        if ((c & cpp_mask) == 0) patch_offsets(d_, c >> cpp_shift);  // the issue stream enters a phase
+      }
+      q.r_src = uniform_ptr(d_.xbase + 8 * (c & cpp_mask));
+    }
+    {
+      const bool own = cu < nch;
+      const int c = own ? cu : cu - nch;
+      const Desc &d_ = own ? cur : nxt;
+      q.u_src = uniform_ptr(d_.ubase + (size_t)c * (WINO_U_STAGE / 4));
+      if (own || more) {  // this wave's pieces are positions 2 wave and 2 wave + 1: one that is zero by construction is not fetched
+        const int pc = c >> cpp_shift, i = wave >> 1, j = 2 * (wave & 1);
+        if (!zero_pos(pc, i, j)) fl |= 2u;
+        if (!zero_pos(pc, i, j + 1)) fl |= 4u;
+      }
+    }
+    q.flags = __builtin_amdgcn_readfirstlane(fl);
+    return q;
+  };
+  auto fire_raw = [&](auto STAGE, const Prep &q) {
+    const uint32_t d = r_dst + (uint32_t)(decltype(STAGE)::value * WINO_RAW_STAGE);
+    if (q.flags & 1u) {
+      glds16(q.r_src, iss_off[0], d);
+      if (wave < 3) glds16(q.r_src, iss_off[1], d + 8192u);
+    }
+  };
+  auto fire_u = [&](auto STAGE, const Prep &q) {
+    const uint32_t d = u_dst + (uint32_t)(decltype(STAGE)::value * WINO_U_STAGE);
+    const uint32_t both = q.flags & 6u;
+    if (both == 6u) {
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                   "global_load_lds_dwordx4 %0, %1\n\t"
+                   "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
+                   "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
+                   "global_load_lds_dwordx4 %0, %1 offset:3072"
+                   : : "v"(u_off), "s"(q.u_src), "s"(d) : "memory", "m0");
+    } else if (both == 2u) {
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                   "global_load_lds_dwordx4 %0, %1\n\t"
+                   "global_load_lds_dwordx4 %0, %1 offset:1024"
+                   : : "v"(u_off), "s"(q.u_src), "s"(d) : "memory", "m0");
+    } else if (both == 4u) {
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                   "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
+                   "global_load_lds_dwordx4 %0, %1 offset:3072"
+                   : : "v"(u_off), "s"(q.u_src), "s"(d) : "memory", "m0");
     }
   };
 
@@ -303,20 +376,22 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   const int b_rd = (8 * ph) * 2048 + hh * 1024 + (32 * wn + l31) * 16;
   // chunk c multiplied (8 positions x 4 MFMAs) with the transform of chunk c + 1 dealt out between the positions: one
   // instruction stream per wave in which matrix and vector / LDS work alternate.  dma(): the chunk's LDS-DMA issues, which the
-  // stride-1 kernel places by position half (the file header's phase offset); the 5x5 forms have issued them already
+  // stride-1 kernel and the polyphase form place by position half (the file header's phase offset); the transposed form has
+  // issued them already
   // FIRST: the block's first chunk starts its accumulators from the inline constant 0 (no clearing pass after the fold)
   // pm: bit q set = position q of this wave's half is issued (polyphase form: positions whose U is zero by construction are not)
-  // tm (5x5 forms): bit s set = step s of the NEXT chunk's transform is run: the masks skip rows and columns that are zero by
-  // construction.  The stride-1 kernel runs every step in every chunk: behind the last chunk of a workgroup's last block that
-  // transform reads the stale raw stage 0 and writes V stage 0, which nobody reads again (the pair exchange uses V stage 1)
-  auto multiply = [&](auto STAGE, auto FIRST, uint32_t tm, uint32_t pm, auto &&dma) {
+  // The transform of the NEXT chunk runs every step in every chunk, in all three forms.  Behind the last chunk of a workgroup's
+  // last block it reads the stale raw stage 0 and writes V stage 0, which nobody reads again (the pair exchange uses V stage 1);
+  // in the 5x5 forms it also computes the V positions whose U is zero by construction: rd() is guarded by pm and the transposed
+  // form's first chunk clears such an accumulator with an MFMA of zeros, so they are never read
+  auto multiply = [&](auto STAGE, auto FIRST, uint32_t pm, auto &&dma) {
     constexpr int stage = decltype(STAGE)::value;
     constexpr bool first = decltype(FIRST)::value;
     using NEXT = std::integral_constant<int, 1 - stage>;
     const char *va = Vs + stage * WINO_V_STAGE + a_rd, *ub = Us + stage * WINO_U_STAGE + b_rd;
     // positions in pairs: the MFMAs of two accumulators alternate (a dependent MFMA waits for its predecessor's last pass),
     // the fragments of the next pair are read while this pair multiplies, the transform steps follow the pair's MFMAs (the
-    // first MFMAs behind the chunk's barrier then wait for two LDS round trips only); stride-1 kernel: the raw pixels of the
+    // first MFMAs behind the chunk's barrier then wait for two LDS round trips only); the raw pixels of the
     // pair's read steps are asked for in front of its MFMAs, so that the combination behind them does not wait for LDS
     float4 af[2][2], bf[2][2];
     auto rd = [&](int set, int q) {
@@ -325,7 +400,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       af[set][1] = *reinterpret_cast<const float4 *>(va + (q + 1) * WINO_V_POS);
       bf[set][1] = *reinterpret_cast<const float4 *>(ub + (q + 1) * 2048);
     };
-    if constexpr (MODE == 0) {
+    if constexpr (!TC) {
       if (ph) dma();  // (the lower half issues them behind its first pair)
     }
     rd(0, 0);
@@ -354,7 +429,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
           transform_step(NEXT{}, integral_constant<int, st + 1>{});
         }
       };
-      if constexpr (MODE == 0 && q < 4) reads(Q);
+      if constexpr (q < 4) reads(Q);
       __builtin_amdgcn_sched_barrier(0);
       const float4 x0 = af[set][0], y0 = bf[set][0], x1 = af[set][1], y1 = bf[set][1];
       if constexpr (first && TC) {
@@ -403,15 +478,10 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (MODE == 0) {
-        if constexpr (q == 0) {
-          if (!ph) dma();
-        }
-        finish(Q);
-      } else {
-        if ((tm >> q) & 1u) transform_step(NEXT{}, integral_constant<int, q>{});
-        if ((tm >> (q + 1)) & 1u) transform_step(NEXT{}, integral_constant<int, q + 1>{});
+      if constexpr (!TC && q == 0) {
+        if (!ph) dma();
       }
+      finish(Q);
       __builtin_amdgcn_sched_barrier(0);
     };
     using std::integral_constant;
@@ -431,9 +501,16 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     if (c < nch) issue_u(cur, c);
     else if (kb + 1u < n_mine) issue_u(nxt, c - nch);
   };
-  issue_raw(cur, 0);
-  issue_u(cur, 0);
-  issue_raw_at(0u, 1);
+  if constexpr (POLY) {
+    const Prep q0 = prepare(0u, 0, 0);
+    fire_raw(std::integral_constant<int, 0>{}, q0);
+    fire_u(std::integral_constant<int, 0>{}, q0);
+    fire_raw(std::integral_constant<int, 1>{}, prepare(0u, 1, 0));
+  } else {
+    issue_raw(cur, 0);
+    issue_u(cur, 0);
+    issue_raw_at(0u, 1);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   transform0();
@@ -445,14 +522,18 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     auto chunk = [&](auto STAGE, auto FIRST, int c) {
       // here: V(c) complete, U(c) and raw(c + 1) in LDS; raw stage c & 1, U stage (c + 1) & 1 and V stage (c + 1) & 1 are free
       // (chunks beyond this block's are the first ones of the next block): the DMA targets are free from here to the closing
-      // s_waitcnt + barrier, wherever in the chunk a wave issues them.  The transform of chunk c + 1 rides along (5x5 forms:
-      // except behind the last chunk of the workgroup's last block, a run-time flag -- as a third instantiation of the chunk
-      // the register allocator spilled 213 registers)
+      // s_waitcnt + barrier, wherever in the chunk a wave issues them.  The transform of chunk c + 1 rides along
+      Prep q;
+      if constexpr (POLY) q = prepare(kb, c + 2, c + 1);  // every wave, here: fire() is placed by position half
       auto dma = [&]() {
-        issue_raw_at(kb, c + 2);
-        issue_u_at(kb, c + 1);
+        if constexpr (POLY) {
+          fire_raw(STAGE, q);  // raw(c + 2) -> raw stage c & 1, U(c + 1) -> the other U stage
+          fire_u(std::integral_constant<int, 1 - decltype(STAGE)::value>{}, q);
+        } else {
+          issue_raw_at(kb, c + 2);
+          issue_u_at(kb, c + 1);
+        }
       };
-      if constexpr (MODE != 0) dma();
       uint32_t pm = 0xFFu;
       if constexpr (POLY) {  // phase 2 py + px of this chunk: j == 3 (q = 3, 7) is zero for px = 1, i == 3 (the upper half's q = 4 .. 7) for py = 1
         const int ph2 = c >> cpp_shift;
@@ -463,16 +544,8 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
         const int cls = cur.cb / a.gy;
         pm = 0xFFu & ~((cls & 1) ? 0x11u : 0u) & ~(((cls >> 1) && !ph) ? 0x0Fu : 0u);
       }
-      // the transform of chunk c + 1 (the next block's chunk 0 behind this block's last): this thread computes the positions
-      // (i = t_i, j = 0 .. 3) -- nothing if row i is zero by construction in that chunk's phase / class, not V_j if column j is
-      uint32_t tm = 0xFFu;
-      if constexpr (MODE != 0) {
-        if (!(c + 1 < nch || kb + 1u < n_mine)) tm = 0u;
-        const int pcn = c + 1 < nch ? phase_or_class(cur, c + 1) : phase_or_class(nxt, 0);
-        if (zero_pos(pcn, t_i, 1)) tm = 0u;  // (j = 1 is never zero by construction: the row is)
-        else if (zero_pos(pcn, 1, POLY ? 3 : 0)) tm &= POLY ? ~0x80u : ~0x10u;
-      }
-      multiply(STAGE, FIRST, tm, pm, dma);
+      if constexpr (TC) dma();  // (transposed form: both heads at the barrier)
+      multiply(STAGE, FIRST, pm, dma);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     };

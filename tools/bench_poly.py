@@ -1,5 +1,7 @@
 """5x5 stride-2 64 -> 128 (+ GDN) at 540x960: version 1 (tap chain, fused GDN) against the polyphase Winograd form + GDN launch.
-BATCH=n (default 16)"""
+BATCH=n (default 16)
+`bench_poly.py layers`: the two 5x5 Winograd launches alone under fp32w on the shapes the 1080p step runs most (A/B of kernel
+variants: select the library with AIVC_HIP_LIB) -- 3 warm-up launches, 3 x 10 launches between events, best of the three means."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import torch
@@ -60,7 +62,38 @@ def tconv():
               % (ci, co, h, w, nb, out['fp32'][0], out['fp32w'][0], out['fp32'][0] / out['fp32w'][0], out['fp32'][1], direct / out['fp32'][1] / 1e9,
                  out['fp32w'][1], out['fp32'][1] / out['fp32w'][1], ex / out['fp32w'][1] / 1e9, ex / out['fp32w'][1] / 1e9 / 157.3))
 
+LAYERS = [  # form, frames, h, w, c_in, c_out
+    ('poly5', 16, 540, 960, 64, 128), ('poly5', 64, 540, 960, 64, 128), ('poly5', 64, 270, 480, 64, 128),
+    ('tconv5', 16, 272, 480, 128, 64), ('tconv5', 64, 272, 480, 128, 64),
+]
+
+
+def layers():
+    from aivc_amd import abi
+    dev = torch.device('cuda:0')
+    prev = ops.set_precision('fp32w')
+    try:
+        for (form, nb, h, w, ci, co) in LAYERS:
+            g = torch.Generator(device=dev).manual_seed(7)
+            x = torch.randn(nb, h, w, ci, device=dev, generator=g)
+            wt = torch.randn(co, 5, 5, ci, device=dev, generator=g) * 0.02
+            b = torch.rand(co, device=dev, generator=g) * 0.1
+            if form == 'poly5':
+                fn = lambda: ops.conv2d(x, wt, b, stride=2, pad=2)
+            else:
+                fn = lambda: ops.conv2d(x, wt, b, mode=abi.MODE_TCONV, stride=2)
+            for _ in range(3):
+                y = fn()
+            best = min(timeit(fn, reps=10) for _ in range(3))
+            print('layer %s %d->%d %dx%d n%d: %.4f ms  sum %.9e' % (form, ci, co, h, w, nb, best, float(y.double().sum())), flush=True)
+            del x, y
+    finally:
+        ops.set_precision(prev)
+
 
 if __name__ == '__main__':
-    main()
-    tconv()
+    if sys.argv[1:] == ['layers']:
+        layers()
+    else:
+        main()
+        tconv()

@@ -1,46 +1,47 @@
 // conv_wino.hip -- version 2 of the fp32 arithmetic contract (AIVC_PREC_FP32_WINO, include/aivc_hip.h): the stride-1 3x3
-// convolutions with c_in % 32 == 0 and c_out % 64 == 0 as Winograd F(2x2, 3x3) on the gfx950 matrix cores.
+// convolutions with c_in % 32 == 0 and c_out % 64 == 0 as Winograd F(2x2, 3x3) on the gfx950 matrix cores -- 16 multiplications
+// per 2x2 output pixels and channel pair instead of 36 on the scarce fp32 matrix pipe -- and, on the same kernel, the 5x5
+// stride-2 convolutions (polyphase form) and transposed convolutions (class by class).  What was tried on the way and what it
+// measured: experiments/r06.md (designs), experiments/wino_phases.md (phase offset), experiments/wino5_issue.md (5x5 forms).
 //
-//   why            the fp32 matrix pipe is the scarce unit of this part (157 TFLOP/s, 1/16 of the bf16 rate) and the codec's
-//                  step is 0.75 of it end to end: what is left under the tap chain is ~10 %.  F(2x2, 3x3) issues 16
-//                  multiplications per 2x2 output pixels and channel pair instead of 36.
-//   first version  (round 6, experiments/r06.md): position-outer K loop, the four input pixels of a position fetched per
-//                  position and K-tile -- 12 KB of L2 -> LDS traffic per output pixel at 2.25x the tap kernel's pace
-//                  (~11 TB/s asked of the L2): 0.56 of the matrix peak, 1.2x the tap kernel.  This version fetches every
-//                  input pixel of a block ONCE per channel chunk.
 //   work split     a workgroup = a block of 8 x 8 output tiles (16 x 16 pixels) x 64 output channels, 8 waves: (4 x 8 tiles)
 //                  x 32 channels x 8 of the 16 positions each -- 8 accumulator blocks (128 registers) per wave, two waves per
 //                  SIMD.  The reduction runs over chunks of 8 input channels (one octet of AIVC_K_ORDER = four
 //                  v_mfma_f32_32x32x2_f32 steps per position); M_p = a fixed-order fmaf chain over ci per position, as the
 //                  contract says.  After the last chunk a wave folds its 8 positions into the partial sums S0 / S1 of the
 //                  four outputs of every tile, the two waves of a pair exchange halves through LDS and each finishes one
-//                  output row (a = 0 / a = 1) of the tiles.
+//                  output row (a = 0 / a = 1) of the tiles.  Persistent workgroups, one per CU, walk the block list.
 //   per chunk      raw patch (18 x 18 pixels x 8 channels, 10 KB: replicate-clamped on the global side of the LDS-DMA, stored
-//                  as four parity planes so that the transform's reads are contiguous), U image (16 positions x 64 channels x
-//                  8, 32 KB: aivc_winograd_weights lays it out as it is staged, one contiguous copy), V (16 positions x 64
-//                  tiles x 8, by a cooperative transform: 8 ds_read_b128 + 32 v_fma + 4 ds_write_b128 per thread).
-//                  Everything double-buffered (158 KB of LDS, one workgroup per CU) and ONE barrier per chunk: in chunk c a
+//                  as four parity planes so that the transform's reads are contiguous), fetched ONCE per block and chunk; U
+//                  image (16 positions x 64 channels x 8, 32 KB: aivc_winograd_weights lays it out as it is staged, one
+//                  contiguous copy); V (16 positions x 64 tiles x 8, by a cooperative transform: 8 ds_read_b128 + 32 v_fma +
+//                  4 ds_write_b128 per thread).
+//   pipeline       everything double-buffered (158 KB of LDS, one workgroup per CU) and ONE barrier per chunk: in chunk c a
 //                  wave issues the DMAs of raw(c + 2) and U(c + 1), transforms raw(c + 1) into the other V buffer and
-//                  multiplies chunk c: one instruction stream in which the transform's steps follow the MFMAs of a position pair.
-//   phase offset   the two waves of a SIMD (w and w + 4, the position halves) run that stream in the same order.  In the
-//                  stride-1 kernel they are kept one window of non-matrix work apart: behind the chunk's barrier the upper
-//                  half issues its 5-6 DMA instructions first, the lower half goes straight to its first pair and issues them
-//                  behind that pair's MFMAs -- with both heads at the same place the matrix pipe stood idle for their length;
-//                  the barrier re-aligns the waves, so the offset is made again in every chunk.  There the raw pixels of a
-//                  transform step are also read BEFORE the pair's MFMAs and combined behind them (4 float4 in flight), and the
-//                  transform has no run-time flag.  3x3 128 -> 128: 6-10 % per launch (experiments/wino_phases.md).  The 5x5
-//                  forms (experiments/wino5_issue.md) run the same transform: every step in every chunk, read early -- a V
-//                  position whose U is zero by construction is computed and never read (4-6 % per launch: the eight flag tests
-//                  per chunk and wave and all scratch gone).  The polyphase form is offset as well: its issue is split into
-//                  prepare() (every wave at the chunk head: all address arithmetic) and fire() (the DMA instructions alone,
-//                  placed by position half), so that the offset costs no second copy of the arithmetic.  The transposed form
-//                  keeps both heads at the barrier: offset behind pair 0 it measured +8 %, behind pair 2 null.
+//                  multiplies chunk c: one instruction stream in which the transform's steps follow the MFMAs of a position
+//                  pair.  The raw pixels of a transform step are read BEFORE the pair's MFMAs and combined behind them (4
+//                  float4 in flight); the transform runs every step in every chunk and has no run-time flag.  Chunk indices
+//                  run on through the workgroup's blocks, so the pipeline is filled once per workgroup.
+//   phase offset   the two waves of a SIMD (w and w + 4, the position halves) run that stream in the same order and are kept
+//                  one window of non-matrix work apart: behind the chunk's barrier the upper half issues its 5-6 DMA
+//                  instructions first, the lower half goes straight to its first pair and issues them behind that pair's
+//                  MFMAs -- with both heads at the same place the matrix pipe stands idle for their length.  The barrier
+//                  re-aligns the waves, so the offset is made again in every chunk.
+//   three forms    MODE 0, stride-1 3x3: issue_raw / issue_u (address arithmetic and DMA instructions together), offset.
+//                  MODE 1, polyphase 5x5 stride 2: 4 phases x c_in channels; the per-lane patch offsets change on phase entry,
+//                  so the issue is split into prepare() (every wave at the chunk head: all address arithmetic) and fire_*()
+//                  (the DMA instructions alone, placed by position half): the offset costs no second copy of the arithmetic.
+//                  MODE 2, transposed 5x5 stride 2: 4 classes in the block list, zero extension through 64-bit per-lane
+//                  addresses, issue_raw / issue_u with both heads at the barrier (no offset), 2 x 2 output stride in the
+//                  epilogue.  In the 5x5 forms a position whose U is zero by construction (wino_zero_pos) is neither
+//                  fetched nor multiplied; its V is computed and never read.
 #include <stdlib.h>
 
 #include "mfma_util.h"
 
 namespace aivc {
 
+// TH, TW, poly: read by no kernel; dropping them moves the polyphase kernel's code, so they stay (EXPERIMENTS.md, "Conv kernel sources", reverted pieces)
 struct WinoArgs {
   aivc_conv_params p;
   int TH, TW;    // output tiles per image column / row
@@ -61,10 +62,47 @@ constexpr int WINO_LDS = 2 * (WINO_RAW_STAGE + WINO_U_STAGE + WINO_V_STAGE);
 // 4 KB of zeros: the source of the patch pixels outside the image in the transposed form (zero extension; an LDS-DMA cannot fill)
 __device__ __attribute__((aligned(4096))) float wino_zeros[1024];
 
+// Zero-by-construction positions, the one statement of the rule.  Both 5x5 forms run 3x3 kernels that are 5 taps padded with
+// zeros to 6: a row or column of zeros in g makes a row or column of U = G g G^T zero.  MODE 1, phase pc = 2 py + px: the taps
+// 2 r + py / 2 l + px reach 5 for r = 2 (py = 1) / l = 2 (px = 1), so positions with i == 3 / j == 3 are zero (49 instead of 64 of
+// the 4 x 16 position products).  MODE 2, class pc = 2 pyc + pxc: the taps pyc + 4 - 2 r / pxc + 4 - 2 l reach 5 for r = 0 (pyc = 1)
+// / l = 0 (pxc = 1), so positions with i == 0 / j == 0 are zero.  Such a position is neither fetched nor multiplied.
+template <int MODE>
+__host__ __device__ constexpr bool wino_zero_pos(int pc, int i, int j) {
+  if constexpr (MODE == 1) return ((pc >> 1) && i == 3) || ((pc & 1) && j == 3);
+  if constexpr (MODE == 2) return ((pc >> 1) && i == 0) || ((pc & 1) && j == 0);
+  return false;
+}
+// the positions q of position half `half` (i = 2 half + (q >> 2), j = q & 3) that phase / class pc issues, bit q set = issued
+template <int MODE>
+__host__ __device__ constexpr uint32_t wino_pos_mask(int pc, int half) {
+  uint32_t m = 0u;
+  for (int q = 0; q < 8; ++q) m |= wino_zero_pos<MODE>(pc, 2 * half + (q >> 2), q & 3) ? 0u : 1u << q;
+  return m;
+}
+
+// The block walk of a persistent workgroup.  The dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (each with
+// a private L2): workgroup b sits on XCD b & 7 and takes blocks of that XCD's contiguous eighth of the block list, interleaved with
+// the other workgroups of the XCD -- they advance through one region together; the channel blocks of a pixel block are neighbours
+// in the list (same raw patch).
+struct WinoWalk {
+  uint32_t x_lo, x_hi, slot, wg_per_xcd;  // this XCD's part of the list, this workgroup's place among the XCD's workgroups
+  __device__ __forceinline__ WinoWalk(uint32_t total, uint32_t nwg, uint32_t wg) {
+    const uint32_t xcd = wg & 7u;
+    slot = wg >> 3;
+    const uint32_t per_xcd = (total + 7u) >> 3;
+    wg_per_xcd = (nwg + 7u - xcd) >> 3;  // workgroups on this XCD
+    x_lo = xcd * per_xcd;
+    x_hi = min(x_lo + per_xcd, total);
+  }
+  __device__ __forceinline__ uint32_t block_of(uint32_t k) const { return x_lo + slot + k * wg_per_xcd; }  // k-th block of this workgroup
+  __device__ __forceinline__ uint32_t count() const { return x_lo + slot < x_hi ? (x_hi - x_lo - slot + wg_per_xcd - 1u) / wg_per_xcd : 0u; }
+};
+
 // MODE 0: stride-1 3x3.  MODE 1 (POLY): the polyphase form of the 5x5 stride-2 convolutions.  MODE 2 (TC): the 5x5 stride-2
 // TRANSPOSED convolutions: each of the four output parity classes is a stride-1 3x3 correlation of the (zero-extended) input with
 // the class's taps padded with zeros -- a block of the list is (pixel block, class, 64 output channels), the outputs of class
-// (pyc, pxc) land on pixels (2 y + pyc, 2 x + pxc); positions with i == 0 (pyc = 1) or j == 0 (pxc = 1) have U = 0 and are not issued.
+// (pyc, pxc) land on pixels (2 y + pyc, 2 x + pxc).
 // Separate instantiations: the stride-1 3x3 kernel pays nothing for the others.
 template <int MODE>
 __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
@@ -80,21 +118,14 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   // H x W: the pixel grid the blocks walk = the OUTPUT's (stride 1: also the input's); Hi x Wi: the input's.  Polyphase form
   // (MODE 1, 5x5 stride 2, include/aivc_hip.h): the reduction runs over 4 phases x c_in channels, chunk c belongs to phase
   // c >> cpp_shift = 2 py + px, whose patch pixel (y, x) is input pixel (clamp(2 y + py), clamp(2 x + px)) -- the replicate
-  // padding of the ORIGINAL image -- and whose 3x3 kernel is the phase's taps padded with zeros: positions with i == 3 (py = 1)
-  // or j == 3 (px = 1) have U = 0 and are not issued (49 instead of 64 of the 4 x 16 position products).
+  // padding of the ORIGINAL image -- and whose 3x3 kernel is the phase's taps padded with zeros (wino_zero_pos).
   const int H = TC ? p.h_in : p.h_out, W = TC ? p.w_in : p.w_out, Hi = p.h_in, Wi = p.w_in, Cin = p.c_in, Cout = p.c_out;
   const int gyc = TC ? 4 * a.gy : a.gy;  // entries of the block list per pixel block: channel blocks (x 4 classes)
   const int cpp_shift = a.cpp_shift, cpp_mask = (1 << a.cpp_shift) - 1;
 
-  // Persistent workgroups (one per CU: a.nwg of them) walk the blocks.  The dispatcher deals consecutive workgroup ids
-  // round-robin to the 8 XCDs (each with a private L2): workgroup b sits on XCD b & 7 and takes blocks of that XCD's
-  // contiguous eighth of the block list, interleaved with the other workgroups of the XCD -- they advance through one region
-  // together; the channel blocks of a pixel block are neighbours in the list (same raw patch).
-  const uint32_t total = (uint32_t)a.total, nwg = gridDim.x, xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-  const uint32_t per_xcd = (total + 7u) >> 3, wg_per_xcd = (nwg + 7u - xcd) >> 3;  // workgroups on this XCD
-  const uint32_t x_lo = xcd * per_xcd, x_hi = min(x_lo + per_xcd, total);
-  auto block_of = [&](uint32_t k) -> uint32_t { return x_lo + slot + k * wg_per_xcd; };  // k-th block of this workgroup
-  const uint32_t n_mine = x_lo + slot < x_hi ? (x_hi - x_lo - slot + wg_per_xcd - 1u) / wg_per_xcd : 0u;
+  // ---- block walk: persistent workgroups (gridDim.x of them: one per CU, or one per block of a short list) ------------------
+  const WinoWalk walk((uint32_t)a.total, gridDim.x, blockIdx.x);
+  const uint32_t n_mine = walk.count();
   if (n_mine == 0u) return;
   // descriptor of a block: what the loader needs (image base, chunk images of its channel block, per-lane patch offsets) and
   // what the epilogue needs (coordinates)
@@ -135,8 +166,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     }
     return d;
   };
-  // per-lane byte offsets of the raw patch of block d_ in phase ph2 = 2 py + px (stride 1: phase 0, step 1): recomputed when the
-  // issue stream enters a phase (every c_in / 8 chunks), kept in two registers in between
+  // ---- load: the LDS-DMA issue of a chunk's raw patch and U image -------------------------------------------------------------
+  // polyphase form: per-lane byte offsets of the raw patch of block d_ in phase ph2 = 2 py + px, recomputed when the issue stream
+  // enters a phase (every c_in / 8 chunks), kept in two registers in between
   uint32_t iss_off[2];
   auto patch_offsets = [&](const Desc &d_, int ph2) {
     const int st = POLY ? 2 : 1, py = ph2 >> 1, px = ph2 & 1;
@@ -159,7 +191,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       iss_addr[k] = in ? a_in : a_z;
     }
   };
-  Desc cur = make_desc(block_of(0)), nxt = n_mine > 1u ? make_desc(block_of(1)) : cur;
+  Desc cur = make_desc(walk.block_of(0)), nxt = n_mine > 1u ? make_desc(walk.block_of(1)) : cur;
 
   const uint32_t r_dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)wave * 1024u);
   const uint32_t u_dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(2 * WINO_RAW_STAGE) + (uint32_t)wave * 4096u);
@@ -169,6 +201,8 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
     return reinterpret_cast<const float *>((uintptr_t)(((uint64_t)hi << 32) | lo));
   };
+  // stride-1 and transposed forms: issue_raw / issue_u hold the address arithmetic and the DMA instructions of a chunk together
+  // (the polyphase form issues through prepare / fire_* below)
   auto issue_raw = [&](const Desc &d_, int c) {  // chunk c of block d_ -> raw stage c & 1 (chunks are issued in order)
     const uint32_t d = r_dst + (uint32_t)((c & 1) * WINO_RAW_STAGE);
     if constexpr (TC) {
@@ -178,57 +212,25 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       if (wave < 3) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(iss_addr[1]), "s"(du + 8192u) : "memory", "m0");
       iss_addr[0] += 32u;
       iss_addr[1] += 32u;
-    } else if constexpr (POLY) {
-      if ((c & cpp_mask) == 0) patch_offsets(d_, c >> cpp_shift);  // the issue stream enters a phase
-      const float *src = uniform_ptr(d_.xbase + 8 * (c & cpp_mask));
-      const uint32_t du = __builtin_amdgcn_readfirstlane(d);  // (under register pressure the compiler parks the uniform in a VGPR)
-      glds16(src, iss_off[0], du);
-      if (wave < 3) glds16(src, iss_off[1], du + 8192u);
     } else {
       const float *src = d_.xbase + 8 * c;
       glds16(src, d_.r_off[0], d);
       if (wave < 3) glds16(src, d_.r_off[1], d + 8192u);
     }
   };
-  // zero-by-construction positions (polyphase / transposed forms): is position (i, j) of phase / class `pc` zero?
-  auto zero_pos = [&](int pc, int i, int j) -> bool {
-    if constexpr (POLY) return ((pc >> 1) && i == 3) || ((pc & 1) && j == 3);
-    if constexpr (TC) return ((pc >> 1) && i == 0) || ((pc & 1) && j == 0);
-    return false;
-  };
-  auto phase_or_class = [&](const Desc &d_, int c) -> int {
-    return POLY ? c >> cpp_shift : (TC ? d_.cb / a.gy : 0);
-  };
-  auto issue_u = [&](const Desc &d_, int c) {  // chunk c of block d_ -> U stage c & 1: a straight copy of the chunk image
-    const float *src = MODE != 0 ? uniform_ptr(d_.ubase + (size_t)c * (WINO_U_STAGE / 4)) : d_.ubase + (size_t)c * (WINO_U_STAGE / 4);
-    const uint32_t d = MODE != 0 ? __builtin_amdgcn_readfirstlane(u_dst + (uint32_t)((c & 1) * WINO_U_STAGE)) : u_dst + (uint32_t)((c & 1) * WINO_U_STAGE);
-    // four instructions off ONE M0: the instruction offset advances the global and the LDS address alike (the chunk image is
-    // contiguous on both sides).  This wave's four pieces are positions 2 wave (two channel quads) and 2 wave + 1: a position whose
-    // U is zero by construction is neither multiplied nor fetched
+  // U chunk images are straight copies; this wave's 4 KB piece holds positions 2 wave and 2 wave + 1 = (i, j) and (i, j + 1)
+  auto issue_u = [&](const Desc &d_, int c) {  // chunk c of block d_ -> U stage c & 1
+    const float *src = TC ? uniform_ptr(d_.ubase + (size_t)c * (WINO_U_STAGE / 4)) : d_.ubase + (size_t)c * (WINO_U_STAGE / 4);
+    const uint32_t d = TC ? __builtin_amdgcn_readfirstlane(u_dst + (uint32_t)((c & 1) * WINO_U_STAGE)) : u_dst + (uint32_t)((c & 1) * WINO_U_STAGE);
     bool lo = true, hi = true;
-    if constexpr (MODE != 0) {
-      const int pc = phase_or_class(d_, c), i = wave >> 1, j = 2 * (wave & 1);
-      lo = !zero_pos(pc, i, j);
-      hi = !zero_pos(pc, i, j + 1);
+    if constexpr (TC) {
+      const int cls = d_.cb / a.gy, i = wave >> 1, j = 2 * (wave & 1);
+      lo = !wino_zero_pos<MODE>(cls, i, j);
+      hi = !wino_zero_pos<MODE>(cls, i, j + 1);
     }
-    if (lo && hi) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %0, %1\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:3072"
-                   : : "v"(u_off), "s"(src), "s"(d) : "memory", "m0");
-    } else if (lo) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %0, %1\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:1024"
-                   : : "v"(u_off), "s"(src), "s"(d) : "memory", "m0");
-    } else if (hi) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:3072"
-                   : : "v"(u_off), "s"(src), "s"(d) : "memory", "m0");
-    }
+    if (lo && hi) glds_piece<GLDS_BOTH>(src, u_off, d);
+    else if (lo) glds_piece<GLDS_LO>(src, u_off, d);
+    else if (hi) glds_piece<GLDS_HI>(src, u_off, d);
   };
 
   // polyphase form: the issue of a chunk in two parts.  prepare(kb, cr, cu), run by every wave at the chunk head, does everything
@@ -259,10 +261,10 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       const int c = own ? cu : cu - nch;
       const Desc &d_ = own ? cur : nxt;
       q.u_src = uniform_ptr(d_.ubase + (size_t)c * (WINO_U_STAGE / 4));
-      if (own || more) {  // this wave's pieces are positions 2 wave and 2 wave + 1: one that is zero by construction is not fetched
+      if (own || more) {
         const int pc = c >> cpp_shift, i = wave >> 1, j = 2 * (wave & 1);
-        if (!zero_pos(pc, i, j)) fl |= 2u;
-        if (!zero_pos(pc, i, j + 1)) fl |= 4u;
+        if (!wino_zero_pos<MODE>(pc, i, j)) fl |= 2u;
+        if (!wino_zero_pos<MODE>(pc, i, j + 1)) fl |= 4u;
       }
     }
     q.flags = __builtin_amdgcn_readfirstlane(fl);
@@ -278,24 +280,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   auto fire_u = [&](auto STAGE, const Prep &q) {
     const uint32_t d = u_dst + (uint32_t)(decltype(STAGE)::value * WINO_U_STAGE);
     const uint32_t both = q.flags & 6u;
-    if (both == 6u) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %0, %1\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:3072"
-                   : : "v"(u_off), "s"(q.u_src), "s"(d) : "memory", "m0");
-    } else if (both == 2u) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %0, %1\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:1024"
-                   : : "v"(u_off), "s"(q.u_src), "s"(d) : "memory", "m0");
-    } else if (both == 4u) {
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:3072"
-                   : : "v"(u_off), "s"(q.u_src), "s"(d) : "memory", "m0");
-    }
+    if (both == 6u) glds_piece<GLDS_BOTH>(q.u_src, u_off, d);
+    else if (both == 2u) glds_piece<GLDS_LO>(q.u_src, u_off, d);
+    else if (both == 4u) glds_piece<GLDS_HI>(q.u_src, u_off, d);
   };
 
   // ---- transform plan: thread = (tile, channel quad, row i of the 4 x 4 positions) -----------------------------------------
@@ -379,7 +366,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   // stride-1 kernel and the polyphase form place by position half (the file header's phase offset); the transposed form has
   // issued them already
   // FIRST: the block's first chunk starts its accumulators from the inline constant 0 (no clearing pass after the fold)
-  // pm: bit q set = position q of this wave's half is issued (polyphase form: positions whose U is zero by construction are not)
+  // pm: bit q set = position q of this wave's half is issued (chunk() derives it from wino_zero_pos)
   // The transform of the NEXT chunk runs every step in every chunk, in all three forms.  Behind the last chunk of a workgroup's
   // last block it reads the stale raw stage 0 and writes V stage 0, which nobody reads again (the pair exchange uses V stage 1);
   // in the 5x5 forms it also computes the V positions whose U is zero by construction: rd() is guarded by pm and the transposed
@@ -436,22 +423,10 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
         // the block's first chunk: a position the class does not issue gets a cleared accumulator (one MFMA of zeros), the others
         // start from the inline zero
         const floatx16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if ((pm >> q) & 1u) {
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, y0.x, zero, 0, 0, 0);
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, y0.y, acc[q], 0, 0, 0);
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, y0.z, acc[q], 0, 0, 0);
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, y0.w, acc[q], 0, 0, 0);
-        } else {
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(0.0f, 0.0f, zero, 0, 0, 0);
-        }
-        if ((pm >> (q + 1)) & 1u) {
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, y1.x, zero, 0, 0, 0);
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, y1.y, acc[q + 1], 0, 0, 0);
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, y1.z, acc[q + 1], 0, 0, 0);
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, y1.w, acc[q + 1], 0, 0, 0);
-        } else {
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(0.0f, 0.0f, zero, 0, 0, 0);
-        }
+        if ((pm >> q) & 1u) acc[q] = mfma_oct1(x0, y0, zero);
+        else acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(0.0f, 0.0f, zero, 0, 0, 0);
+        if ((pm >> (q + 1)) & 1u) acc[q + 1] = mfma_oct1(x1, y1, zero);
+        else acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(0.0f, 0.0f, zero, 0, 0, 0);
       } else if constexpr (first) {
         const floatx16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, y0.x, zero, 0, 0, 0);
@@ -464,18 +439,8 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
         acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, y1.w, acc[q + 1], 0, 0, 0);
       } else {
         // (wave-uniform tests; the four MFMAs of a position in a row: alternating two accumulators measured the same, experiments/r06.md 2)
-        if (MODE == 0 || ((pm >> q) & 1u)) {
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, y0.x, acc[q], 0, 0, 0);
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, y0.y, acc[q], 0, 0, 0);
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, y0.z, acc[q], 0, 0, 0);
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, y0.w, acc[q], 0, 0, 0);
-        }
-        if (MODE == 0 || ((pm >> (q + 1)) & 1u)) {
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, y1.x, acc[q + 1], 0, 0, 0);
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, y1.y, acc[q + 1], 0, 0, 0);
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, y1.z, acc[q + 1], 0, 0, 0);
-          acc[q + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, y1.w, acc[q + 1], 0, 0, 0);
-        }
+        if (MODE == 0 || ((pm >> q) & 1u)) acc[q] = mfma_oct1(x0, y0, acc[q]);
+        if (MODE == 0 || ((pm >> (q + 1)) & 1u)) acc[q + 1] = mfma_oct1(x1, y1, acc[q + 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (!TC && q == 0) {
@@ -493,6 +458,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
 
   // ---- the reduction, pipelined ACROSS blocks: chunk indices run on through the workgroup's blocks (c_in / 8 is even, so
   // the stage parity of a chunk is its index inside its block) -------------------------------------------------------------
+  // (stride-1 and transposed forms; the polyphase form's prepare() does the same choice of cur / nxt)
   auto issue_raw_at = [&](uint32_t kb, int c) {  // chunk c of this workgroup's block kb, c possibly beyond the block's chunks
     if (c < nch) issue_raw(cur, c);
     else if (kb + 1u < n_mine) issue_raw(nxt, c - nch);
@@ -534,15 +500,16 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
           issue_u_at(kb, c + 1);
         }
       };
+      // pm: the positions of this wave's half that the chunk's phase / the block's class issues (wino_zero_pos).  Bit 0 of pc
+      // takes a column j away in both halves, bit 1 a row i, i.e. one half's q = 0 .. 3 or q = 4 .. 7.  (Transposed form: the
+      // block's FIRST chunk multiplies the others by zeros to clear their accumulators)
       uint32_t pm = 0xFFu;
-      if constexpr (POLY) {  // phase 2 py + px of this chunk: j == 3 (q = 3, 7) is zero for px = 1, i == 3 (the upper half's q = 4 .. 7) for py = 1
-        const int ph2 = c >> cpp_shift;
-        pm = 0xFFu & ~((ph2 & 1) ? 0x88u : 0u) & ~(((ph2 >> 1) && ph) ? 0xF0u : 0u);
-      }
-      if constexpr (TC) {  // class 2 pyc + pxc of this block: i == 0 (the lower half's q = 0 .. 3) is zero for pyc = 1, j == 0 (q = 0, 4) for pxc = 1
-        // (the block's FIRST chunk issues every position: those multiply by U = 0 and clear their accumulators)
-        const int cls = cur.cb / a.gy;
-        pm = 0xFFu & ~((cls & 1) ? 0x11u : 0u) & ~(((cls >> 1) && !ph) ? 0x0Fu : 0u);
+      if constexpr (MODE != 0) {
+        constexpr uint32_t ZCOL = 0xFFu ^ wino_pos_mask<MODE>(1, 0), ZROW = 0xFFu ^ wino_pos_mask<MODE>(2, POLY ? 1 : 0);
+        static_assert(wino_pos_mask<MODE>(1, 1) == (0xFFu ^ ZCOL) && wino_pos_mask<MODE>(2, POLY ? 0 : 1) == 0xFFu &&
+                      wino_pos_mask<MODE>(3, POLY ? 1 : 0) == (0xFFu ^ (ZCOL | ZROW)), "pm's two terms are the whole rule");
+        const int pc = POLY ? c >> cpp_shift : cur.cb / a.gy;
+        pm = 0xFFu & ~((pc & 1) ? ZCOL : 0u) & ~(((pc >> 1) && (POLY ? ph : !ph)) ? ZROW : 0u);
       }
       if constexpr (TC) dma();  // (transposed form: both heads at the barrier)
       multiply(STAGE, FIRST, pm, dma);
@@ -732,7 +699,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     epilogue_done:;
     }
     cur = nxt;
-    if (kb + 2u < n_mine) nxt = make_desc(block_of(kb + 2u));
+    if (kb + 2u < n_mine) nxt = make_desc(walk.block_of(kb + 2u));
   }
 }
 
@@ -815,15 +782,24 @@ int winograd_weights_tconv5(const float *w, int c_out, int c_in, float *u, hipSt
   return winograd_weights_launch<WinoFormTconv5>("winograd_weights_tconv5", w, c_out, c_in, u, s);
 }
 
-// what the kernel can address: 32-bit byte offsets inside one image
+// The block list of a launch: the pixel grid the blocks walk (the output's; transposed form: the input's) in blocks of 16 x 16
+// pixels, times the blocks of 64 output channels (transposed form: times the 4 classes)
+struct WinoGrid {
+  int gh, gw, nby, nbx;  // pixel grid; blocks per image column / row
+  uint64_t blocks;       // entries of the block list
+};
+static WinoGrid wino_grid(const aivc_conv_params &p) {
+  const bool tc = p.mode == AIVC_MODE_TCONV;
+  const int gh = tc ? p.h_in : p.h_out, gw = tc ? p.w_in : p.w_out, nby = (gh + 15) / 16, nbx = (gw + 15) / 16;
+  return {gh, gw, nby, nbx, (uint64_t)p.n * nby * nbx * ((uint64_t)p.c_out / 64) * (tc ? 4 : 1)};
+}
+
+// what the kernel can address: 32-bit byte offsets inside one image, a block list that an int counts
 bool conv2d_wino_supported(const aivc_conv_params &p) {
   if (!aivc_winograd_covers(&p) || p.gdn) return false;
   if ((uint64_t)p.h_in * p.w_in * p.c_in * 4u >= 0xFFFF0000ull) return false;
-  const bool tc = p.mode == AIVC_MODE_TCONV;
-  if (tc && p.c_in > 960) return false;  // (a pixel outside the image reads c_in floats of the 4 KB zero page, one chunk after the other)
-  const uint64_t gh = tc ? p.h_in : p.h_out, gw = tc ? p.w_in : p.w_out;  // the pixel grid the blocks walk
-  const uint64_t blocks = (uint64_t)p.n * ((gh + 15) / 16) * ((gw + 15) / 16) * ((uint64_t)p.c_out / 64) * (tc ? 4 : 1);
-  return blocks < 0x7FFFFFFFull;
+  if (p.mode == AIVC_MODE_TCONV && p.c_in > 960) return false;  // (a pixel outside the image reads c_in floats of the 4 KB zero page, one chunk after the other)
+  return wino_grid(p).blocks < 0x7FFFFFFFull;
 }
 
 int conv2d_wino_variant(const aivc_conv_params &p) { return p.mode == AIVC_MODE_TCONV ? 303 : (p.ksize == 5 ? 302 : 301); }
@@ -844,18 +820,19 @@ int conv2d_wino(const aivc_conv_params &p, hipStream_t s) {
   a.poly = !tc && p.ksize == 5 ? 1 : 0;
   a.cpp_shift = 0;
   while ((8 << a.cpp_shift) < p.c_in) ++a.cpp_shift;  // (polyphase form: c_in / 8 is a power of two, aivc_winograd_covers)
-  a.TH = ((tc ? p.h_in : p.h_out) + 1) / 2;
-  a.TW = ((tc ? p.w_in : p.w_out) + 1) / 2;
-  a.nby = (a.TH + 7) / 8;
-  a.nbx = (a.TW + 7) / 8;
+  const WinoGrid g = wino_grid(p);
+  a.TH = (g.gh + 1) / 2;
+  a.TW = (g.gw + 1) / 2;
+  a.nby = g.nby;
+  a.nbx = g.nbx;
   a.gy = p.c_out / 64;
-  a.total = (int)((size_t)p.n * a.nby * a.nbx * a.gy * (tc ? 4 : 1));
+  a.total = (int)g.blocks;
   static std::atomic<int> n_cu{0};
   if (n_cu.load(std::memory_order_relaxed) == 0) {
     int dev = 0, cus = 0;
     n_cu = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 ? cus : 256;
   }
-  // persistent workgroups, one per CU (158 KB of LDS each); a multiple of 8 so that every XCD gets its share of the list
+  // persistent workgroups: min(CUs, blocks) -- one per CU (158 KB of LDS each), or one per block of a list shorter than that
   unsigned grid = (unsigned)n_cu.load(std::memory_order_relaxed);
   if ((unsigned)a.total < grid) grid = (unsigned)a.total;
   if (tc) return wino_launch<2>(a, grid, s);

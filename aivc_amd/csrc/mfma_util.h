@@ -15,6 +15,30 @@ __device__ __forceinline__ void glds16(const float *base, uint32_t voff, uint32_
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(base), "s"(lds_dst) : "memory", "m0");
 }
 
+// LDS-DMA of a contiguous 4 KB piece (256 slots of 16 bytes, slot s of instruction k = 64 k + lane), or of its lower / upper
+// half: up to four instructions off ONE M0 -- the instruction offset advances the global and the LDS address alike.
+enum GldsPiece { GLDS_BOTH, GLDS_LO, GLDS_HI };
+template <GldsPiece PIECE>
+__device__ __forceinline__ void glds_piece(const float *base, uint32_t voff, uint32_t lds_dst) {
+  if constexpr (PIECE == GLDS_BOTH)
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %0, %1\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:3072"
+                 : : "v"(voff), "s"(base), "s"(lds_dst) : "memory", "m0");
+  else if constexpr (PIECE == GLDS_LO)
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %0, %1\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:1024"
+                 : : "v"(voff), "s"(base), "s"(lds_dst) : "memory", "m0");
+  else
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:3072"
+                 : : "v"(voff), "s"(base), "s"(lds_dst) : "memory", "m0");
+}
+
 // NONE / LEAKY / RELU of act_apply() without branches
 __device__ __forceinline__ float act_cheap(int act, float v) {
   const float neg = act == AIVC_ACT_LEAKY ? v * 0.01f : (act == AIVC_ACT_RELU ? 0.0f : v);
@@ -36,6 +60,13 @@ __device__ __forceinline__ void mfma_oct_step(const float4 (&af)[TM], const floa
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) c[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4_at<S>(af[i]), f4_at<S>(bf[j]), c[i][j], 0, 0, 0);
+}
+// the four steps on ONE accumulator block, in a row
+__device__ __forceinline__ floatx16 mfma_oct1(const float4 &a, const float4 &b, floatx16 c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, c, 0, 0, 0);
 }
 // the four steps; skip3 (wave-uniform) leaves out step 3 where k % 4 == 3 multiplies a zero (AIVC_CONV_SPARSE4)
 template <int TM, int TN>

@@ -1,10 +1,11 @@
 """The conv family's part of tests/op_cases.py (read its docstring first): the case tables of tests/test_gpu_ops.py,
-test_gpu_winograd.py, test_gpu_gdn_resident.py and tests/test_gpu_memory_discipline.py and one builder per kind of launch.  Every
+test_gpu_winograd*.py (with their shared fixture and helpers), test_gpu_gdn_resident.py and tests/test_gpu_memory_discipline.py and one builder per kind of launch.  Every
 builder's call passes keyword arguments on to ops.conv2d / ops.gdn (algo=...).  Not a test module."""
 import numpy as np
+import pytest
 
 from aivc_amd import abi
-from op_cases import Case
+from op_cases import Case, on, profiled
 
 CONV_CASES = [
     # mode, k, stride, pad, cin, cout, h, w, act1, act2, mul, res
@@ -284,6 +285,37 @@ def wino_case(oracle, variant, row, seed):
     fixed = dict(mode=mode, stride=s, pad=pad, act1=a1, act2=a2)
     return Case({'x': x, 'w': wt, 'bias': b, 'mul': m, 'res': r}, _conv_call(('mul', 'res'), **fixed),
                 oracle.conv2d(x, wt, b, mul=m, res=r, **fixed))
+
+
+@pytest.fixture()
+def fp32w(oracle):
+    """version 2 of the contract with the size rule lifted, on the device side and in the oracle (a test module imports it)"""
+    from aivc_amd import ops
+    prev_h, prev_o = ops.set_precision('fp32w'), oracle.set_precision('fp32w')
+    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = True  # the kernel on shapes the oracle checks in seconds
+    yield
+    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = False
+    ops.set_precision(prev_h)
+    oracle.set_precision(prev_o)
+
+
+def wino_blocks(variant, row, n=None):
+    """length of the kernel's block list (conv2d_wino) for n images (default: the row's): 16 x 16 grid pixels x 64 output channels
+    (x 4 classes, transposed form).  The grid is the output's; transposed form: the input's"""
+    h, w, co = row[1], row[2], row[4]
+    gh, gw = ((h + 1) // 2, (w + 1) // 2) if variant == 302 else (h, w)
+    return (row[0] if n is None else n) * ((gh + 15) // 16) * ((gw + 15) // 16) * (co // 64) * (4 if variant == 303 else 1)
+
+
+def wino_three_launches(variant, c, cuda):
+    """three launches in a row on the same buffers: the variant code and the oracle's bits, every time"""
+    from aivc_amd import ops
+    d = c.place(on(cuda))
+    for launch in range(3):
+        got, variants = profiled(lambda: c.call(ops, d))
+        assert variants == [variant], (launch, variants)
+        g = got.cpu().numpy()
+        assert np.array_equal(g, c.want), (launch, float(np.abs(g - c.want).max()))
 
 
 def wino_weights_case(oracle, form, c_in):

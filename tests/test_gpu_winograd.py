@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from aivc_amd import abi
-from conv_cases import POLY_CASES, TC_CASES, WINO_CASES, wino_case, wino_weights_case
+from conv_cases import POLY_CASES, TC_CASES, WINO_CASES, fp32w, wino_case, wino_weights_case  # noqa: F401 (fp32w: a fixture)
 from op_cases import T, on, profiled
 
 pytestmark = pytest.mark.gpu
@@ -30,17 +30,6 @@ def _runs_on(variant, c, cuda, next_to_version_1=True):
         finally:
             ops.set_precision(prev)
         assert np.abs(g - v1).max() <= 2e-5 * max(1.0, float(np.abs(v1).max()))
-
-
-@pytest.fixture()
-def fp32w(oracle):
-    from aivc_amd import ops
-    prev_h, prev_o = ops.set_precision('fp32w'), oracle.set_precision('fp32w')
-    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = True  # the kernel on shapes the oracle checks in seconds
-    yield
-    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = False
-    ops.set_precision(prev_h)
-    oracle.set_precision(prev_o)
 
 
 @pytest.mark.parametrize('idx', range(len(WINO_CASES)))

@@ -6,32 +6,12 @@ chunk's LDS-DMAs take) at the places no other row reaches:
   * polyphase form with 8 and 16 chunks per phase, odd input sizes, block lists of 2 * CUs + 8 and 4 * CUs + 8;
   * one block per workgroup at c_in 128 (polyphase) and c_out 192 (transposed): the only block's last chunk.
 HIP == CPU oracle BIT FOR BIT, three launches in a row on the same buffers, the variant code asserted."""
-import numpy as np
 import pytest
 import torch
 
-from conv_cases import wino_case
-from op_cases import on, profiled
+from conv_cases import fp32w, wino_blocks, wino_case, wino_three_launches  # noqa: F401 (fp32w: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture()
-def fp32w(oracle):
-    from aivc_amd import ops
-    prev_h, prev_o = ops.set_precision('fp32w'), oracle.set_precision('fp32w')
-    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = True  # the kernel on shapes the oracle checks in seconds
-    yield
-    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = False
-    ops.set_precision(prev_h)
-    oracle.set_precision(prev_o)
-
-
-def _per_image(variant, row):
-    """list entries per image (conv2d_wino): 16 x 16 grid pixels x 64 output channels (x 4 classes, transposed form)"""
-    h, w, co = row[1], row[2], row[4]
-    gh, gw = ((h + 1) // 2, (w + 1) // 2) if variant == 302 else (h, w)
-    return ((gh + 15) // 16) * ((gw + 15) // 16) * (co // 64) * (4 if variant == 303 else 1)
 
 
 def _owned(total, cus):
@@ -48,19 +28,9 @@ def _owned(total, cus):
     return out
 
 
-def _three_launches(variant, c, cuda):
-    from aivc_amd import ops
-    d = c.place(on(cuda))
-    for launch in range(3):
-        got, variants = profiled(lambda: c.call(ops, d))
-        assert variants == [variant], (launch, variants)
-        g = got.cpu().numpy()
-        assert np.array_equal(g, c.want), (launch, float(np.abs(g - c.want).max()))
-
-
 def _sized(variant, row, blocks_wanted):
-    n = -(-blocks_wanted // _per_image(variant, row))
-    return (n,) + row[1:], n * _per_image(variant, row)
+    n = -(-blocks_wanted // wino_blocks(variant, row, n=1))
+    return (n,) + row[1:], wino_blocks(variant, row, n=n)
 
 
 def test_transposed_class_changes_between_a_workgroups_blocks(cuda, oracle, fp32w):
@@ -68,14 +38,14 @@ def test_transposed_class_changes_between_a_workgroups_blocks(cuda, oracle, fp32
     row, total = _sized(303, (None, 16, 16, 32, 192, 0, 0, True, False), 2 * cus + 8)  # 12 entries per pixel block: class = (entry % 12) // 3
     changes = sum(1 for mine in _owned(total, cus) for a, b in zip(mine, mine[1:]) if (a % 12) // 3 != (b % 12) // 3)
     assert changes > 0, (cus, total)  # the shape has to hand a workgroup two blocks of different classes
-    _three_launches(303, wino_case(oracle, 303, row, 1000), cuda)
+    wino_three_launches(303, wino_case(oracle, 303, row, 1000), cuda)
 
 
 def test_transposed_block_entry_across_image_borders(cuda, oracle, fp32w):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     row, total = _sized(303, (None, 17, 30, 64, 64, 0, 0, True, False), 2 * cus + 8)
     assert max(len(m) for m in _owned(total, cus)) >= 2
-    _three_launches(303, wino_case(oracle, 303, row, 1001), cuda)
+    wino_three_launches(303, wino_case(oracle, 303, row, 1001), cuda)
 
 
 # c_in, multiple of the CU count in the block list
@@ -89,7 +59,7 @@ def test_polyphase_many_chunks_per_phase(name, cuda, oracle, fp32w):
     # 30 x 62 inputs -> 15 x 31 outputs: the clamp into the other phase and the right-edge column
     row, total = _sized(302, (None, 30, 62, c_in, 128, 0, 0, True, False), mult * cus + 8)
     assert max(len(m) for m in _owned(total, cus)) >= mult + 1  # nxt is handed over `mult` times or more
-    _three_launches(302, wino_case(oracle, 302, row, 1010 + list(POLY).index(name)), cuda)
+    wino_three_launches(302, wino_case(oracle, 302, row, 1010 + list(POLY).index(name)), cuda)
 
 
 SINGLE = {
@@ -102,5 +72,5 @@ SINGLE = {
 def test_a_workgroup_with_one_block(name, cuda, oracle, fp32w):
     variant, row = SINGLE[name]
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    assert row[0] * _per_image(variant, row) <= cus
-    _three_launches(variant, wino_case(oracle, variant, row, 1020 + list(SINGLE).index(name)), cuda)
+    assert wino_blocks(variant, row) <= cus
+    wino_three_launches(variant, wino_case(oracle, variant, row, 1020 + list(SINGLE).index(name)), cuda)

@@ -4,32 +4,12 @@ whole images): workgroups own 2 and 3 blocks, unevenly over the XCDs, and the pa
 next block's patch, U image and first transform under this block's last chunk, the pair exchange through V stage 1 while V stage 0
 already holds the next block's chunk 0, and the descriptor hand-over (`nxt`).  Plus one launch per form in which every workgroup's
 only block is its first and its last.  HIP == CPU oracle BIT FOR BIT, three launches in a row on the same buffers."""
-import numpy as np
 import pytest
 import torch
 
-from conv_cases import wino_case
-from op_cases import on, profiled
+from conv_cases import fp32w, wino_blocks, wino_case, wino_three_launches  # noqa: F401 (fp32w: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture()
-def fp32w(oracle):
-    from aivc_amd import ops
-    prev_h, prev_o = ops.set_precision('fp32w'), oracle.set_precision('fp32w')
-    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = True  # the kernel on shapes the oracle checks in seconds
-    yield
-    ops.WINO_ANY_SIZE = oracle.WINO_ANY_SIZE = False
-    ops.set_precision(prev_h)
-    oracle.set_precision(prev_o)
-
-
-def _blocks(variant, row):
-    """length of the kernel's block list (conv2d_wino): 16 x 16 grid pixels x 64 output channels (x 4 classes, transposed form)"""
-    n, h, w, co = row[0], row[1], row[2], row[4]
-    gh, gw = ((h + 1) // 2, (w + 1) // 2) if variant == 302 else (h, w)  # the grid is the output's; transposed form: the input's
-    return n * ((gh + 15) // 16) * ((gw + 15) // 16) * (co // 64) * (4 if variant == 303 else 1)
 
 
 # variant, row of the form's table with n = None: the number of images comes from the device's CU count
@@ -47,31 +27,21 @@ SINGLE = {
 }
 
 
-def _three_launches(variant, c, cuda):
-    from aivc_amd import ops
-    d = c.place(on(cuda))
-    for launch in range(3):
-        got, variants = profiled(lambda: c.call(ops, d))
-        assert variants == [variant], (launch, variants)
-        g = got.cpu().numpy()
-        assert np.array_equal(g, c.want), (launch, float(np.abs(g - c.want).max()))
-
-
 @pytest.mark.parametrize('name', list(MANY))
 def test_workgroups_walk_two_and_three_blocks(name, cuda, oracle, fp32w):
     variant, row = MANY[name]
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    per_image = _blocks(variant, (1,) + row[1:])
+    per_image = wino_blocks(variant, row, n=1)
     n = -(-(2 * cus + 8) // per_image)
     row = (n,) + row[1:]
-    blocks = _blocks(variant, row)
+    blocks = wino_blocks(variant, row)
     assert 2 * cus + 8 <= blocks < 3 * cus, (cus, blocks)  # some workgroups own 2 blocks, some 3
-    _three_launches(variant, wino_case(oracle, variant, row, 900 + list(MANY).index(name)), cuda)
+    wino_three_launches(variant, wino_case(oracle, variant, row, 900 + list(MANY).index(name)), cuda)
 
 
 @pytest.mark.parametrize('name', list(SINGLE))
 def test_a_workgroup_with_one_block(name, cuda, oracle, fp32w):
     variant, row = SINGLE[name]
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    assert _blocks(variant, row) <= cus
-    _three_launches(variant, wino_case(oracle, variant, row, 950 + list(SINGLE).index(name)), cuda)
+    assert wino_blocks(variant, row) <= cus
+    wino_three_launches(variant, wino_case(oracle, variant, row, 950 + list(SINGLE).index(name)), cuda)

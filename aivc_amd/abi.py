@@ -7,7 +7,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -152,6 +152,28 @@ PROTOTYPES = {
     'aivc_table_prob': [_f, _f, _sz, _sz, _i32, _f],
 }
 
+# aivc_detmath_eval is a diagnostic like aivc_selfcheck_gdn_math and is bound like it: by declare() on the device library only.
+# PROTOTYPES is the list that declare() REQUIRES of an oracle library before it binds anything, and the oracle is test
+# infrastructure that is not always of this package's revision: the suite and oracle of an earlier revision, run against this
+# package to show that it still computes what it computed, have no twin of a newer diagnostic, and a name in PROTOTYPES would fail
+# every one of their oracle calls instead of none.  So oracle.detmath_eval binds `aivc_detmath_eval_ref` itself, and
+# tests/test_host_logic.py::test_oracle_exports_ref_twins asserts that twin by name.
+DETMATH_EVAL_ARGS = [_i32, _f, _f, _sz, _f]
+
+# aivc_detmath_eval's function ids (include/aivc_hip.h: AIVC_DETMATH_*)
+DETMATH_EXP, DETMATH_EXPM1, DETMATH_LOG, DETMATH_LOG1P = 0, 1, 2, 3  # fp64 cores
+DETMATH_EXPF, DETMATH_EXPM1F, DETMATH_SIGMOIDF, DETMATH_TANHF, DETMATH_SOFTPLUSF = 4, 5, 6, 7, 8  # fp32 wrappers
+DETMATH_POWF, DETMATH_LAPLACE_CDF = 9, 10  # fp32, two operands
+DETMATH_COUNT = 11
+
+
+def detmath_is_fp64(fn):
+    return DETMATH_EXP <= fn <= DETMATH_LOG1P
+
+
+def detmath_operands(fn):
+    return 2 if fn in (DETMATH_POWF, DETMATH_LAPLACE_CDF) else 1
+
 # include/aivc_hip_color.h: device only, like aivc_warp_modes (the CPU oracle has no `_ref` twin of these; their CPU statement is
 # Pillow itself, tests/test_color_tables.py)
 COLOR_PROTOTYPES = {
@@ -192,6 +214,10 @@ def declare(lib, suffix=''):
         chk.argtypes = [C.c_uint64, C.c_uint32, _f, C.c_void_p]
         chk.restype = C.c_int
         fns['aivc_selfcheck_gdn_math'] = chk
+        ev = lib.aivc_detmath_eval  # the deterministic transcendentals, element by element
+        ev.argtypes = list(DETMATH_EVAL_ARGS) + [C.c_void_p]
+        ev.restype = C.c_int
+        fns['aivc_detmath_eval'] = ev
         wm = lib.aivc_warp_modes  # include/aivc_hip_warp.h: the warp in every sampling mode, no host twin either
         wm.argtypes = [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, C.c_void_p]
         wm.restype = C.c_int

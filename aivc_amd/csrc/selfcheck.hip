@@ -1,5 +1,7 @@
 // selfcheck.hip -- device-side check of the lean square root / division of the fused GDN epilogues (common.h) against
-// the compiler's full IEEE sequences.  A diagnostic entry point: nothing on the coded path calls it.
+// the compiler's full IEEE sequences, and the element-by-element evaluator of the deterministic transcendentals
+// (include/aivc_detmath.h) whose device bits the tests compare with the host's.  Diagnostic entry points: nothing on the
+// coded path calls them.
 #include "common.h"
 
 namespace aivc {
@@ -49,4 +51,55 @@ AIVC_EXPORT int aivc_selfcheck_gdn_math(uint64_t n_div_pairs, uint32_t seed, uin
   if (n_div_pairs)
     hipLaunchKernelGGL(aivc::selfcheck_div_kernel, dim3(4096), dim3(256), 0, s, n_div_pairs, seed, reinterpret_cast<unsigned long long *>(mismatch) + 1);
   return aivc::check_launch("selfcheck_gdn_math");
+}
+
+namespace aivc {
+
+// out[i] = fn(a[i] [, b[i]]) for one function of include/aivc_detmath.h: nothing but the header's own functions
+template <typename T>
+__global__ __launch_bounds__(256) void detmath_eval_kernel(int fn, const T *__restrict__ a, const T *__restrict__ b, size_t n, T *__restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    if constexpr (sizeof(T) == 8) {
+      const double x = a[i];
+      double r;
+      switch (fn) {
+        case AIVC_DETMATH_EXP: r = aivc_det_exp(x); break;
+        case AIVC_DETMATH_EXPM1: r = aivc_det_expm1(x); break;
+        case AIVC_DETMATH_LOG: r = aivc_det_log(x); break;
+        default: r = aivc_det_log1p(x); break;
+      }
+      out[i] = r;
+    } else {
+      const float x = a[i];
+      float r;
+      switch (fn) {
+        case AIVC_DETMATH_EXPF: r = aivc_expf_det(x); break;
+        case AIVC_DETMATH_EXPM1F: r = aivc_expm1f_det(x); break;
+        case AIVC_DETMATH_SIGMOIDF: r = aivc_sigmoidf_det(x); break;
+        case AIVC_DETMATH_TANHF: r = aivc_tanhf_det(x); break;
+        case AIVC_DETMATH_SOFTPLUSF: r = aivc_softplusf_det(x); break;
+        case AIVC_DETMATH_POWF: r = aivc_powf_det(x, b[i]); break;
+        default: r = aivc_laplace_cdf(x, b[i]); break;
+      }
+      out[i] = r;
+    }
+  }
+}
+
+}  // namespace aivc
+
+AIVC_EXPORT int aivc_detmath_eval(int32_t fn, const void *a, const void *b, size_t n, void *out, aivc_stream_t stream) {
+  if (fn < 0 || fn >= AIVC_DETMATH_COUNT) return AIVC_ERR_ARG;
+  if (n == 0) return AIVC_OK;
+  const bool two = fn == AIVC_DETMATH_POWF || fn == AIVC_DETMATH_LAPLACE_CDF;
+  if (!a || !out || (two && !b)) return AIVC_ERR_ARG;
+  hipStream_t s = aivc::to_stream(stream);
+  const unsigned blocks = aivc::cdiv(n, 256) < 8192u ? aivc::cdiv(n, 256) : 8192u;
+  if (fn <= AIVC_DETMATH_LOG1P)
+    hipLaunchKernelGGL(aivc::detmath_eval_kernel<double>, dim3(blocks), dim3(256), 0, s, (int)fn, static_cast<const double *>(a),
+                       static_cast<const double *>(b), n, static_cast<double *>(out));
+  else
+    hipLaunchKernelGGL(aivc::detmath_eval_kernel<float>, dim3(blocks), dim3(256), 0, s, (int)fn, static_cast<const float *>(a),
+                       static_cast<const float *>(b), n, static_cast<float *>(out));
+  return aivc::check_launch("detmath_eval");
 }

@@ -329,6 +329,18 @@ def selfcheck_gdn_math(n_div_pairs=1 << 34, seed=1, device=None):
     return tuple(int(v) for v in out.cpu())
 
 
+def detmath_eval(fn, a, b=None):
+    """out[i] = fn(a[i]) or fn(a[i], b[i]) for one function of include/aivc_detmath.h on the device (aivc_detmath_eval, a
+    diagnostic): fn one of abi.DETMATH_*, a / b / out float64 for the fp64 cores and float32 for everything else"""
+    dt = torch.float64 if abi.detmath_is_fp64(fn) else torch.float32
+    a, b = _dev(a, dt, 'a'), _dev(b, dt, 'b')
+    if abi.detmath_operands(fn) == 2 and (b is None or b.shape != a.shape):
+        raise AivcNativeError('aivc_amd.ops.detmath_eval: function %d takes two operands of one shape' % fn)
+    out = torch.empty_like(a)
+    call('aivc_detmath_eval', int(fn), _p(a), _p(b), a.numel(), _p(out), _stream())
+    return out
+
+
 def gdn(x, beta_eff, gamma_eff, inverse=False, res=None, algo=abi.ALGO_AUTO, frame_h=None):
     c = x.shape[-1]
     mode = abi.MODE_IGDN if inverse else abi.MODE_GDN

@@ -62,7 +62,7 @@ enum {
  * Library identity
  * ---------------------------------------------------------------------------------------- */
 /* ABI version, bumped whenever a struct or signature changes (the library and the CPU oracle both return it). */
-#define AIVC_ABI_VERSION 21
+#define AIVC_ABI_VERSION 22
 int aivc_abi_version(void);
 /* Last HIP runtime error string seen by this thread's most recent failing call (host). */
 const char *aivc_last_error(void);
@@ -251,6 +251,28 @@ int aivc_gdn_reparam(const float *beta, const float *gamma, int32_t c, float bet
  * from the compiler's full ones: mismatch[0] over EVERY float s in the range for the square root, mismatch[1] over
  * n_div_pairs pseudo-random (numerator, denominator) pairs for the division.  Both must come back 0. */
 int aivc_selfcheck_gdn_math(uint64_t n_div_pairs, uint32_t seed, uint64_t *mismatch, aivc_stream_t stream);
+
+/* Diagnostic (nothing on the coded path calls it): out[i] = fn(a[i]) or fn(a[i], b[i]) for one function of
+ * include/aivc_detmath.h, i < n, evaluated on the device (the CPU oracle's twin: on the host), so that the header's claim
+ * "device bits == host bits" can be tested function by function, argument by argument (tests/test_gpu_detmath.py) and its
+ * accuracy on the host against a higher-precision libm (tests/test_detmath.py).
+ * a, b and out are double for the fp64 cores and float for everything else; b is read by the two-operand functions only.
+ * n == 0: nothing is done.  Null a / out, null b for a two-operand function, or an unknown fn: AIVC_ERR_ARG. */
+enum {
+  AIVC_DETMATH_EXP = 0,        /* fp64: aivc_det_exp(a) */
+  AIVC_DETMATH_EXPM1 = 1,      /* fp64: aivc_det_expm1(a) */
+  AIVC_DETMATH_LOG = 2,        /* fp64: aivc_det_log(a), finite a > 0 */
+  AIVC_DETMATH_LOG1P = 3,      /* fp64: aivc_det_log1p(a), a >= 0 */
+  AIVC_DETMATH_EXPF = 4,       /* fp32: aivc_expf_det(a) */
+  AIVC_DETMATH_EXPM1F = 5,     /* fp32: aivc_expm1f_det(a) */
+  AIVC_DETMATH_SIGMOIDF = 6,   /* fp32: aivc_sigmoidf_det(a) */
+  AIVC_DETMATH_TANHF = 7,      /* fp32: aivc_tanhf_det(a) */
+  AIVC_DETMATH_SOFTPLUSF = 8,  /* fp32: aivc_softplusf_det(a) */
+  AIVC_DETMATH_POWF = 9,       /* fp32, two operands: aivc_powf_det(a, b) */
+  AIVC_DETMATH_LAPLACE_CDF = 10, /* fp32, two operands: aivc_laplace_cdf(t = a, sigma = b) */
+  AIVC_DETMATH_COUNT = 11
+};
+int aivc_detmath_eval(int32_t fn, const void *a, const void *b, size_t n, void *out, aivc_stream_t stream);
 
 /* Zero-pad channels: in [npix][c_in] -> out [npix][c_out], c_out >= c_in, extra channels = 0. */
 int aivc_pad_channels(const float *in, size_t npix, int32_t c_in, float *out, int32_t c_out,

@@ -487,6 +487,23 @@ def laplace_prob(y, mu, sigma):
     return prob
 
 
+def detmath_eval(fn, a, b=None):
+    """out[i] = fn(a[i]) or fn(a[i], b[i]) for one function of include/aivc_detmath.h on the host: fn one of abi.DETMATH_*,
+    a / b / out float64 for the fp64 cores and float32 for everything else"""
+    dt = np.float64 if abi.detmath_is_fp64(fn) else np.float32
+    a = np.ascontiguousarray(a, dt)
+    b = None if b is None else np.ascontiguousarray(b, dt)
+    assert abi.detmath_operands(fn) == 1 or (b is not None and b.shape == a.shape)
+    out = np.empty_like(a)
+    fns = lib()
+    if 'aivc_detmath_eval' not in fns:  # (bound here, once, not by abi.declare: see abi.DETMATH_EVAL_ARGS)
+        ev = _lib.aivc_detmath_eval_ref
+        ev.argtypes, ev.restype = list(abi.DETMATH_EVAL_ARGS) + [C.c_void_p], C.c_int
+        fns['aivc_detmath_eval'] = ev
+    _chk(fns['aivc_detmath_eval'](int(fn), _p(a), _p(b), a.size, _p(out), None), 'aivc_detmath_eval')
+    return out
+
+
 def table_prob(x, cdf_f32):
     """x [b, c, h, w] integer-valued floats, cdf_f32 [c, 514] -> probabilities [b, c, h, w]"""
     x = np.ascontiguousarray(x, np.float32)

@@ -55,6 +55,10 @@ CONV_CASES = [
     (abi.MODE_TCONV, 3, 2, 0, 32, 64, 7, 9, 0, 0, False, False),
     (abi.MODE_TCONV, 5, 2, 0, 64, 128, 1, 3, abi.ACT_LEAKY, 0, False, False),
     (abi.MODE_CONV, 5, 2, 2, 96, 160, 13, 9, 0, 0, False, False),
+    # a 13th entry states the bias: sigmoid pre-activations (bias + a conv output of unit scale) on both sides of -103.97 / -88.72 /
+    # -87.34 and of their mirror images, where fp32 exp(-v) underflows, overflows or is subnormal and the quotient 1 / (1 + e) is
+    # subnormal or 0, instead of within +-5 (tests/test_gpu_detmath.py says why); conv_case asserts that they are reached
+    (abi.MODE_CONV, 1, 1, 0, 8, 8, 6, 10, abi.ACT_SIGMOID, 0, True, True, (-110.0, -104.0, -88.0, -40.0, 40.0, 88.0, 104.0, 110.0)),
 ]
 
 # The register-staged K loop's own users, on every tile each is instantiated for (AIVC_FORCE_TILE ids; 2 = 256x64 exists for
@@ -124,6 +128,22 @@ GDN_RESIDENT_CASES = [
     (128, 3, 136, 120, True, True),
 ]
 
+# the attention gate x + trunk * sigmoid(conv1x1(a)): whole 64-row tiles take the inlined-sigmoid epilogue, ragged ones the general
+# one; the last row scales the conv's weights (pre-activations far beyond +-5: see the last row of CONV_CASES)
+ATTENTION_GATE_CASES = [(2, 16, 32, 128, 1.0), (1, 9, 11, 128, 1.0), (2, 8, 8, 64, 1.0), (1, 9, 11, 128, 40.0)]  # n, h, w, c, weight scale
+
+
+def attention_gate_case(oracle, n, h, w, c, scale):
+    rng = np.random.default_rng(n * 100 + h)
+    a = rng.standard_normal((n, h, w, c), dtype=np.float32)
+    wt = (rng.standard_normal((c, 1, 1, c), dtype=np.float32) / np.sqrt(c)).astype(np.float32) * np.float32(scale)
+    b = rng.standard_normal(c, dtype=np.float32)
+    trunk = rng.standard_normal((n, h, w, c), dtype=np.float32)
+    x = rng.standard_normal((n, h, w, c), dtype=np.float32)
+    return Case({'x': a, 'w': wt, 'bias': b, 'mul': trunk, 'res': x}, _conv_call(('mul', 'res'), act1=abi.ACT_SIGMOID),
+                oracle.conv2d(a, wt, b, act1=abi.ACT_SIGMOID, mul=trunk, res=x), pre_activation=oracle.conv2d(a, wt, b))
+
+
 WINO_CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, mul, res
     (1, 8, 8, 32, 128, 0, 0, True, False, False),
     (2, 7, 9, 32, 128, 1, 0, True, False, False),      # odd sizes: half-filled last tile row / column
@@ -184,11 +204,14 @@ def _conv_call(names, **fixed):
 
 def conv_case(oracle, row, seed, n=2):
     """a row of CONV_CASES: bias, two activations, gate multiplicand, residual; the GDN modes with positive gamma and beta"""
-    mode, k, s, pad, ci, co, h, w, a1, a2, use_mul, use_res = row
+    mode, k, s, pad, ci, co, h, w, a1, a2, use_mul, use_res = row[:12]
     rng = np.random.default_rng(seed)
     x = rng.standard_normal((n, h, w, ci), dtype=np.float32)
     wt = (rng.standard_normal((co, k, k, ci), dtype=np.float32) / np.sqrt(k * k * ci)).astype(np.float32)
     bias = rng.standard_normal(co, dtype=np.float32)
+    if len(row) > 12:
+        bias = np.array(row[12], np.float32)
+        assert bias.shape == (co,)
     if mode in (abi.MODE_GDN, abi.MODE_IGDN):
         wt = np.abs(wt) * 0.1
         bias = np.abs(bias) + 0.1
@@ -196,8 +219,13 @@ def conv_case(oracle, row, seed, n=2):
     mul = rng.standard_normal((n, ho, wo, co), dtype=np.float32) if use_mul else None
     res = rng.standard_normal((n, ho, wo, co), dtype=np.float32) if use_res else None
     fixed = dict(mode=mode, stride=s, pad=pad, act1=a1, act2=a2)
+    facts = {}
+    if len(row) > 12:  # the range the row exists for, whatever the seed
+        pre = facts['pre_activation'] = oracle.conv2d(x, wt, bias, mode=mode, stride=s, pad=pad)
+        for lo, hi in ((-np.inf, -103.98), (-103.97, -88.73), (-88.72, -87.34), (87.34, 88.72), (88.73, 103.97), (103.98, np.inf)):
+            assert ((pre > lo) & (pre < hi)).any(), (lo, hi, float(pre.min()), float(pre.max()))
     return Case({'x': x, 'w': wt, 'bias': bias, 'mul': mul, 'res': res}, _conv_call(('mul', 'res'), **fixed),
-                oracle.conv2d(x, wt, bias, mul=mul, res=res, **fixed))
+                oracle.conv2d(x, wt, bias, mul=mul, res=res, **fixed), **facts)
 
 
 def thin_walk_case(oracle, row, seed, with_bias=True):

@@ -516,6 +516,80 @@ def rate_estimates_case(oracle, seed, shape):
     return Case({'y': y, 'mu': mu, 'sigma': sigma, 'cdf': cdf, 'p_zero': p_zero}, call, want, compare)
 
 
+# ---- deterministic transcendentals -----------------------------------------------------------------------------------------------
+def detmath_case(oracle, fn, a, b=None):
+    """aivc_detmath_eval of one function of include/aivc_detmath.h at the arguments a (and b): device bits == host bits, a NaN
+    matching any NaN (payload and sign of a NaN are not part of the contract)"""
+    from detmath_cases import same_bits
+    dt = np.float64 if abi.detmath_is_fp64(fn) else np.float32
+    a = np.ascontiguousarray(a, dt)
+    b = None if b is None else np.ascontiguousarray(b, dt)
+
+    def compare(got, want):
+        got = got.cpu().numpy()
+        ok = same_bits(got, want)
+        if not ok.all():
+            i = np.flatnonzero(~ok)
+            u = np.uint64 if dt == np.float64 else np.uint32
+            raise AssertionError('detmath fn %d: device != host at %d of %d arguments; first a = %r (bits 0x%X)%s: device %r (0x%X), host %r (0x%X)'
+                                 % (fn, i.size, a.size, a[i[0]], int(a.view(u)[i[0]]), '' if b is None else ', b = %r' % b[i[0]],
+                                    got[i[0]], int(got.view(u)[i[0]]), want[i[0]], int(want.view(u)[i[0]])))
+    return Case({'a': a, 'b': b}, lambda ops, d: ops.detmath_eval(fn, d['a'], d['b']), oracle.detmath_eval(fn, a, b), compare, n=a.size)
+
+
+WINDOW_CHUNK_TMIN = {0: 25.5, 1: 17.5, 2: 9.5, 3: 1.5, 5: 7.5, 6: 15.5, 7: 23.5}  # csrc/entropy.hip: |t| of a chunk's entry nearest to the centre
+
+
+def saturation_threshold_case(oracle, chunk):
+    """laplace_cdf_windows where the windows kernel decides, per wavefront and 8-entry chunk, whether every lane is saturated
+    (tmin / b > 17.5f for b = sigma / 1.41421354f: the entries are then k or 65023 + k without any fp64 work).  sigma takes the 9
+    floats around tmin * 1.41421354f / 17.5f of this chunk, on both sides of that test, over (1, 9, 13, 6) with maps [0, 2, 5]: 351
+    positions in stream order = 5 whole wavefronts and one of 31 valid lanes --
+      0: every lane just saturated            1: one lane just unsaturated, the others just saturated
+      2: the band in turn, both sides         3: every lane just unsaturated
+      4: the band at random                   5 (31 valid lanes): every valid lane just saturated
+    -> Case with the oracle's windows and sigma per position, which equal the slice of its full rows; q / payload: a stream coded
+    with these rows whose symbols leave the window too (the decoder's slow path rebuilds rows from sigma_pos).
+    What this proves: the shortcut writes the entries the long path writes, lane by lane, where lanes disagree about it.  What it
+    cannot: at the threshold both paths give the same entries by construction (expm1f is -1 from -17.33 on), so a predicate that
+    is slightly off (17.0f, or any lane instead of all) passes here as well."""
+    h, w, c, maps = 9, 13, 6, [0, 2, 5]
+    npix, tmin = h * w, np.float32(WINDOW_CHUNK_TMIN[chunk])
+    s0 = tmin * np.float32(1.41421354) / np.float32(17.5)
+    band = (s0.view(np.int32) + np.arange(-4, 5, dtype=np.int32)).view(np.float32)
+    sat = tmin / (band / np.float32(1.41421354)) > np.float32(17.5)  # the kernel's own test, in IEEE fp32
+    assert sat.any() and not sat.all() and np.all(sat[:-1] >= sat[1:]), (band, sat)  # (saturated below a threshold inside the band)
+    lo, hi = band[sat][-1], band[~sat][0]  # the last saturated sigma and the first unsaturated one: neighbours
+    rng = np.random.default_rng(chunk)
+    per_pos = np.empty(len(maps) * npix, np.float32)
+    per_pos[0:64] = lo
+    per_pos[64:128] = lo
+    per_pos[64 + 37] = hi
+    per_pos[128:192] = band[np.arange(64) % band.size]
+    per_pos[192:256] = hi
+    per_pos[256:320] = rng.choice(band, 64)
+    per_pos[320:] = band[sat][rng.integers(0, int(sat.sum()), per_pos.size - 320)]
+    sig = rng.uniform(0.5, 2.0, (1, h, w, c)).astype(np.float32)  # (the maps that are not coded)
+    sig.reshape(npix, c)[:, maps] = per_pos.reshape(len(maps), npix).T  # position = map * npix + pixel
+    q = np.clip(np.rint(rng.laplace(0, 1, sig.shape) * sig / np.sqrt(2)), -256, 255).astype(np.int16)
+    q.reshape(-1)[::7] = np.array([33, -33, 40, -34, 32, -32, 31], np.int16)[np.arange(q.size)[::7] % 7]
+    rows = oracle.laplace_cdf_rows(sig, maps)
+    win, sp = oracle.laplace_cdf_windows(sig, maps)
+    np.testing.assert_array_equal(sp, per_pos)
+    np.testing.assert_array_equal(win, rows[:, abi.CDF_WIN0:abi.CDF_WIN0 + abi.CDF_WIN])
+    payload = oracle.range_encode(oracle.laplace_bounds(sig, q, maps))
+    sym = oracle.range_decode(payload, rows, per_pos.size)
+    np.testing.assert_array_equal(sym, (q.reshape(npix, c)[:, maps].T.reshape(-1).astype(np.int32) + 256).astype(np.uint16))
+    assert (np.abs(sym.astype(np.int32) - 256) > 32).any()
+
+    def call(ops, d):
+        out = {}
+        out['win'], out['sp'] = ops.laplace_cdf_windows(d['sig'], maps)
+        (out['sym'],), _ = ops.range_decode([payload], out['win'], [0], [per_pos.size], [0], sigma_pos=out['sp'], want_bits=True)
+        return out
+    return Case({'sig': sig}, call, {'win': win, 'sp': sp, 'sym': sym}, eq_all, saturated=sat, band=band)
+
+
 # ---- metrics ---------------------------------------------------------------------------------------------------------------------
 def metrics_case(oracle, h, w, ws):
     """ssim_means, pool2x2 with both edges, sq_err on three fp64 planes and a noisy copy.  fp64 kernels: 1e-12 against the fp64

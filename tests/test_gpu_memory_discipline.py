@@ -23,7 +23,7 @@ from conv_cases import (BF16X3_CASES, CONV_CASES, CONV_IMAGES_CASES, FUSED_GDN_C
                         TC_CASES, THIN_WALK_CASES, THIN_WALK_GRIDS, WINO_CASES, bf16x3_case, conv_case, conv_images_cases, fused_gdn_case,
                         fused_tail_case, gdn_resident_case, mfma_tile_case, pack_images_cases, thin_walk_case, wino_case, wino_weights_case)
 from guarded import both_fills, guarded, guarded_empty
-from op_cases import (AUX, FRAME_BATCH_CASES, FRAME_SIZES, RANGE_DECODE_CASES, WARP_SHAPES, T, bounds_rate_case, cdf_case, downsample2x_cases,
+from op_cases import (AUX, FRAME_BATCH_CASES, FRAME_SIZES, RANGE_DECODE_CASES, WARP_SHAPES, T, bounds_rate_case, cdf_case, detmath_case, downsample2x_cases,
                       eq, frame_batch_case, frame_sources, frame_to_yuv420_case, gain_interp_case, latent_ops_case, metrics_case, on,
                       pad_channels_case, profiled, range_coder_case, range_coder_pmf_case, range_encode_case, rate_estimates_case,
                       stream_bytes, warp_blend_case, warp_blend_sources, warp_case, warp_modes_case, yuv420_to_444_case, yuv_planes)
@@ -433,6 +433,15 @@ def test_bounds_rate(n, oracle, cuda):
 def test_rate_estimates(shape, oracle, cuda):
     """laplace_prob with and without mu, table_prob, rate_bits"""
     run_guarded(rate_estimates_case(oracle, shape[-1], shape), cuda)
+
+
+# ---- deterministic transcendentals -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('n', [1, 63, 4097])
+def test_detmath_eval(n, oracle, cuda):
+    """every function id of aivc_detmath_eval: one element, less than a wavefront, more than a block's stride"""
+    from detmath_cases import sample
+    for fn in range(abi.DETMATH_COUNT):
+        run_guarded(detmath_case(oracle, fn, *sample(fn, n, 100 * fn + n)), cuda)
 
 
 # ---- metrics ---------------------------------------------------------------------------------------------------------------------

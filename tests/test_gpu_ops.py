@@ -4,8 +4,8 @@ import pytest
 import torch
 
 from aivc_amd import abi
-from conv_cases import (CONV_CASES, CONV_IMAGES_CASES, FUSED_GDN_CASES, FUSED_TAIL_CASES, STAGED_CASES, STAGED_FUSED_GDN_CASES, THIN_WALK_CASES,
-                        THIN_WALK_GRIDS, conv_case, conv_images_cases, fused_gdn_case, fused_tail_case, pack_images_cases, thin_walk_case)
+from conv_cases import (ATTENTION_GATE_CASES, CONV_CASES, CONV_IMAGES_CASES, FUSED_GDN_CASES, FUSED_TAIL_CASES, STAGED_CASES, STAGED_FUSED_GDN_CASES, THIN_WALK_CASES,
+                        THIN_WALK_GRIDS, attention_gate_case, conv_case, conv_images_cases, fused_gdn_case, fused_tail_case, pack_images_cases, thin_walk_case)
 from op_cases import (FORCED, FRAME_BATCH_CASES, FRAME_SIZES, RANGE_CODER_CASES, WARP_SHAPES, T, cdf_case, eq, frame_batch_case, forced_case, frame_sources,
                       frame_to_yuv420_case, latent_ops_case, on, profiled, range_coder_case, range_coder_pmf_case, range_encode_case,
                       straddle_stream, warp_blend_case, warp_blend_sources, warp_case, yuv420_to_444_case, yuv_planes)
@@ -386,20 +386,18 @@ def test_attention_res_block_256_bit_exact_in_version_2(oracle, cuda):
     eq(got, want)
 
 
-@pytest.mark.parametrize('n,h,w,c', [(2, 16, 32, 128), (1, 9, 11, 128), (2, 8, 8, 64)])
-def test_attention_gate_epilogue_bit_exact(n, h, w, c, oracle, cuda):
+@pytest.mark.parametrize('n,h,w,c,scale', [pytest.param(*r, id='-'.join(str(v) for v in r[:4]) + ('' if r[4] == 1.0 else '-x%g' % r[4]))
+                                           for r in ATTENTION_GATE_CASES])
+def test_attention_gate_epilogue_bit_exact(n, h, w, c, scale, oracle, cuda):
     """x + trunk * sigmoid(conv1x1(a)) in the conv epilogue (whole 64x64 tiles take the inlined-sigmoid path, ragged ones
-    the general one): both equal the oracle"""
+    the general one): both equal the oracle, through every algo; the scaled row's pre-activations reach beyond +-88, where
+    exp(-v) overflows fp32 or is subnormal"""
     from aivc_amd import ops
-    rng = np.random.default_rng(n * 100 + h)
-    a = rng.standard_normal((n, h, w, c), dtype=np.float32)
-    wt = (rng.standard_normal((c, 1, 1, c), dtype=np.float32) / np.sqrt(c)).astype(np.float32)
-    b = rng.standard_normal(c, dtype=np.float32)
-    trunk = rng.standard_normal((n, h, w, c), dtype=np.float32)
-    x = rng.standard_normal((n, h, w, c), dtype=np.float32)
-    want = oracle.conv2d(a, wt, b, act1=abi.ACT_SIGMOID, mul=trunk, res=x)
-    got = ops.conv2d(T(a, cuda), T(wt, cuda), T(b, cuda), act1=abi.ACT_SIGMOID, mul=T(trunk, cuda), res=T(x, cuda))
-    eq(got, want)
+    case = attention_gate_case(oracle, n, h, w, c, scale)
+    if scale != 1.0:
+        assert case.pre_activation.min() < -88 and case.pre_activation.max() > 88
+    for algo in ALGOS:
+        case.check(case.run(ops, on(cuda), algo=algo))
 
 
 def test_fused_tail_is_one_launch(cuda):

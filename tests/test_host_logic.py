@@ -33,7 +33,8 @@ def test_hip_library_exports_every_declared_symbol():
     from aivc_amd import abi
     assert lib.aivc_abi_version() == abi.ABI_VERSION
     # every prototype bound by abi.py is declared in the header and vice versa
-    assert set(abi.PROTOTYPES) | {'aivc_abi_version', 'aivc_last_error', 'aivc_conv2d_variant', 'aivc_selfcheck_gdn_math'} == set(names)
+    assert set(abi.PROTOTYPES) | {'aivc_abi_version', 'aivc_last_error', 'aivc_conv2d_variant', 'aivc_selfcheck_gdn_math',
+                                  'aivc_detmath_eval'} == set(names)
 
 
 def test_oracle_exports_ref_twins(oracle):
@@ -41,6 +42,7 @@ def test_oracle_exports_ref_twins(oracle):
     from aivc_amd import abi
     for n in abi.PROTOTYPES:
         assert hasattr(lib, n + '_ref')
+    assert hasattr(lib, 'aivc_detmath_eval_ref')  # (a diagnostic outside PROTOTYPES whose twin the accuracy tests run on)
 
 
 def test_argument_validation_without_gpu():
@@ -56,6 +58,15 @@ def test_argument_validation_without_gpu():
     assert fns['aivc_conv2d'](ctypes.byref(p), None) == -1  # wrong output size
     assert fns['aivc_conv2d_variant'](ctypes.byref(abi.ConvParams(
         abi.MODE_CONV, 3, 1, 1, 1, 270, 480, 128, 270, 480, 128, 0, 0, 0, 0, 0, 1, 1, None, None, None, 1, None, None))) == 105  # 64x128 (round-3 tile rules)
+    # aivc_detmath_eval: an unknown function, null a / out, null b of a two-operand function; n == 0 does nothing
+    ev = fns['aivc_detmath_eval']
+    assert ev(abi.DETMATH_COUNT, 1, 1, 4, 1, None) == -1 and ev(-1, 1, 1, 4, 1, None) == -1
+    assert ev(abi.DETMATH_COUNT, None, None, 0, None, None) == -1
+    for fn in range(abi.DETMATH_COUNT):
+        assert ev(fn, None, 1, 4, 1, None) == -1 and ev(fn, 1, 1, 4, None, None) == -1
+        if abi.detmath_operands(fn) == 2:  # (a one-operand function would take this call: never made with stand-in pointers)
+            assert ev(fn, 1, None, 4, 1, None) == -1
+        assert ev(fn, None, None, 0, None, None) == 0
 
 
 def test_conv_dispatch_of_the_default_model_at_1080p():

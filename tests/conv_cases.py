@@ -1,5 +1,6 @@
 """The conv family's part of tests/op_cases.py (read its docstring first): the case tables of tests/test_gpu_ops.py,
-test_gpu_winograd*.py (with their shared fixture and helpers), test_gpu_gdn_resident.py and tests/test_gpu_memory_discipline.py and one builder per kind of launch.  Every
+test_gpu_winograd*.py (with their shared fixture and helpers), test_gpu_gdn_resident.py, test_gpu_large_batches.py and tests/test_gpu_memory_discipline.py and one builder
+per kind of launch; the fp64 layer evaluation with torch that several modules compare against.  Every
 builder's call passes keyword arguments on to ops.conv2d / ops.gdn (algo=...).  Not a test module."""
 import numpy as np
 import pytest
@@ -435,3 +436,192 @@ def pack_images_cases(oracle, h, w, n, part_lists):
         first = next(t for t in d['parts'] if t is not None)
         return ops.pack_images(d['parts'], h, w, (first['y'] if isinstance(first, dict) else first).device)
     return [Case({'parts': parts}, call, oracle.pack_images(parts, h, w)) for parts in ([src[nm] for nm in pl] for pl in part_lists)]
+
+
+# ---- fp64 evaluations with torch (tests/test_oracle_winograd.py, test_gpu_precision.py, test_gpu_large_batches.py) ---------------
+def torch_fp64(mode, x, w, b, stride, pad, k):
+    """fp64 evaluation of the layer on the CPU (NHWC numpy in, NHWC torch out): conv with replicate padding, or ConvTranspose2d k,
+    s 2, pad (1 + k) / 2 - 1, output_padding 1 (src/layers/misc/custom_conv_layers.py:129-253); w is OHWI"""
+    import torch
+    import torch.nn.functional as F
+    xt = torch.from_numpy(np.ascontiguousarray(x)).double().permute(0, 3, 1, 2)
+    wt = torch.from_numpy(np.ascontiguousarray(w)).double()
+    bt = None if b is None else torch.from_numpy(np.ascontiguousarray(b)).double()
+    if mode == abi.MODE_CONV:
+        xp = F.pad(xt, (pad, pad, pad, pad), mode='replicate') if pad else xt
+        y = F.conv2d(xp, wt.permute(0, 3, 1, 2), bt, stride=stride)
+    else:
+        y = F.conv_transpose2d(xt, wt.permute(3, 0, 1, 2), bt, stride=2, padding=int((1 + k) / 2 - 1), output_padding=1)
+    return y.permute(0, 2, 3, 1).contiguous()
+
+
+def gdn_fp64(x, beta, gamma, inverse):
+    """x / sqrt(beta + gamma @ x^2) per pixel (inverse: x * sqrt(...)), fp64 torch tensors, channels last"""
+    import torch
+    nrm = torch.sqrt(beta + (x * x) @ gamma.t())
+    return x * nrm if inverse else x / nrm
+
+
+# ---- batches whose tensors contain byte 2^31 and byte 2^32 (tests/test_gpu_large_batches.py) ---------------------------------------
+class Large:
+    """One layer of the default model at 1080p on a batch just large enough that the tensors named in the module's table cross the
+    marks.  kind: 'conv' (ops.conv2d on a float tensor), 'gdn' (ops.gdn) or 'images' (one 8-bit 4:2:0 source as an ops.ImageStack)."""
+
+    def __init__(self, name, variants, kind, n, h, w, ci, co, mode=abi.MODE_CONV, k=1, stride=1, pad=0, act1=0, act2=0, mul=False,
+                 res=False, gdn=None, precision=None):
+        self.name, self.variants, self.kind, self.n, self.h, self.w, self.ci, self.co = name, variants, kind, n, h, w, ci, co
+        self.mode, self.k, self.stride, self.pad, self.act1, self.act2, self.mul, self.res = mode, k, stride, pad, act1, act2, mul, res
+        self.gdn, self.precision = gdn, precision  # gdn: None, False (GDN) or True (inverse): fused for 'conv' / 'images', the op of 'gdn'
+        self.ho, self.wo = abi.conv_out_size(mode, h, w, k, stride, pad)
+
+    def __repr__(self):
+        return self.name
+
+
+_L, _T = abi.ACT_LEAKY, abi.MODE_TCONV
+LARGE_CASES = [
+    Large('301-conv3-128-leaky-res', [301], 'conv', 66, 270, 480, 128, 128, k=3, stride=1, pad=1, act1=_L, res=True),
+    Large('302-conv5s2-64to128', [302], 'conv', 66, 540, 960, 64, 128, k=5, stride=2, pad=2),
+    Large('303-tconv5-128to64-res', [303], 'conv', 66, 270, 480, 128, 64, mode=_T, k=5, stride=2, res=True),
+    Large('400-gdn128-res', [400], 'gdn', 66, 270, 480, 128, 128, mode=abi.MODE_GDN, res=True, gdn=False),
+    Large('400-igdn128-res', [400], 'gdn', 66, 270, 480, 128, 128, mode=abi.MODE_IGDN, res=True, gdn=True),
+    Large('400-gdn64', [400], 'gdn', 34, 540, 960, 64, 64, mode=abi.MODE_GDN, gdn=False),
+    Large('2-tconv5-64to3-leaky-lean', [2], 'conv', 34, 540, 960, 64, 3, mode=_T, k=5, stride=2, act1=_L),
+    Large('2-tconv5-64to6-mul-res-act2', [2], 'conv', 34, 540, 960, 64, 6, mode=_T, k=5, stride=2, act2=_L, mul=True, res=True),
+    Large('1-tconv5-128to3', [1], 'conv', 18, 540, 960, 128, 3, mode=_T, k=5, stride=2),
+    Large('191-images-conv5s2-gdn', [191], 'images', 34, 1080, 1920, 4, 64, k=5, stride=2, pad=2, gdn=False),
+    # the version-1 pair of tests/test_gpu_fullsize_kernels.py::test_batch_beyond_4gb_goes_out_as_sub_batches
+    Large('155-conv5s2-64to128-gdn-fp32', [155], 'conv', 34, 540, 960, 64, 128, k=5, stride=2, pad=2, gdn=False, precision='fp32'),
+    Large('113-tconv3-64to32-leaky-fp32', [113], 'conv', 34, 540, 960, 64, 32, mode=_T, k=3, stride=2, act1=_L, precision='fp32'),
+]
+LARGE_CHUNK = 8     # images per small launch: every tensor of a chunk stays below 2^31 bytes
+LARGE_WINDOW = 24   # output pixels per side of an fp64 window
+LARGE_MARKS = (1 << 31, 1 << 32)
+
+
+def large_tensors(c, dev, seed):
+    """the case's operands, drawn ON THE DEVICE: weights scaled 1 / sqrt(k k c_in), positive GDN parameters, output-shaped gate
+    multiplicand / residual where the case has them"""
+    import torch
+    g = torch.Generator(device=dev).manual_seed(seed)
+
+    def randn(*shape):
+        return torch.randn(shape, device=dev, generator=g)
+    d = {}
+    if c.kind == 'images':
+        hc, wc = (c.h + 1) // 2, (c.w + 1) // 2
+        d['planes'] = {nm: torch.randint(0, 256, (c.n, hh, ww), device=dev, generator=g, dtype=torch.uint8)
+                       for nm, hh, ww in (('y', c.h, c.w), ('u', hc, wc), ('v', hc, wc))}
+        d['w'] = torch.zeros((c.co, c.k, c.k, 4), device=dev)
+        d['w'][..., :3] = randn(c.co, c.k, c.k, 3) / (c.k * c.k * 3) ** 0.5
+    else:
+        d['x'] = randn(c.n, c.h, c.w, c.ci)
+    if c.kind == 'conv':
+        d['w'] = randn(c.co, c.k, c.k, c.ci) / (c.k * c.k * c.ci) ** 0.5
+    if c.kind != 'gdn':
+        d['bias'] = randn(c.co)
+    if c.gdn is not None:
+        d['beta'] = torch.rand(c.co, device=dev, generator=g) + 0.5
+        d['gamma'] = torch.rand((c.co, c.co), device=dev, generator=g) * 0.01
+    for nm in ('mul', 'res'):
+        if getattr(c, nm):
+            d[nm] = randn(c.n, c.ho, c.wo, c.co)
+    return d
+
+
+def large_launch(ops, c, d, lo, hi):
+    """the case's launch on images lo .. hi - 1 (contiguous slices of the operands) -> (output, variant codes)"""
+    mul, res = (d[nm][lo:hi] if nm in d else None for nm in ('mul', 'res'))
+    if c.kind == 'gdn':
+        return profiled(lambda: ops.gdn(d['x'][lo:hi], d['beta'], d['gamma'], inverse=c.gdn, res=res))
+    fused = None if c.gdn is None else (d['beta'], d['gamma'], c.gdn)
+    kw = dict(mode=c.mode, stride=c.stride, pad=c.pad, act1=c.act1, act2=c.act2, mul=mul, res=res, gdn=fused)
+    if c.kind == 'images':
+        stack = ops.ImageStack([{nm: t[lo:hi] for nm, t in d['planes'].items()}], c.h, c.w, d['w'].device)
+        y, codes = profiled(lambda: ops.conv2d(stack, d['w'], d['bias'], **kw))
+        assert stack._packed is None, 'the fused kernel must have taken this layer (no packed tensor)'
+        return y, codes
+    return profiled(lambda: ops.conv2d(d['x'][lo:hi], d['w'], d['bias'], **kw))
+
+
+def _mark_pixels(c, d):
+    """[(tensor name, mark, image, output row, output column)]: where byte 2^31 / 2^32 of each float tensor of the case lies, as the
+    output pixel that reads (input) or is (output, gate, residual) the pixel holding that byte"""
+    out = []
+    for nm in ('x', 'y', 'mul', 'res'):
+        if nm == 'x' and 'x' not in d or nm in ('mul', 'res') and nm not in d:
+            continue
+        hh, ww, cc = (c.h, c.w, c.ci) if nm == 'x' else (c.ho, c.wo, c.co)
+        for mark in LARGE_MARKS:
+            if c.n * hh * ww * cc * 4 <= mark:
+                continue
+            img, off = divmod(mark, hh * ww * cc * 4)
+            py, px = divmod(off // (cc * 4), ww)
+            if nm == 'x' and c.mode == abi.MODE_TCONV:
+                py, px = 2 * py, 2 * px
+            elif nm == 'x':
+                py, px = min(py // c.stride, c.ho - 1), min(px // c.stride, c.wo - 1)
+            out.append((nm, mark, img, py, px))
+    return out
+
+
+def large_windows(c, d):
+    """-> (marks, [(image, row, column)]): origins (even) of the LARGE_WINDOW-square output windows the fp64 comparison takes.
+    Images: those holding a mark, the one before each, image 0 and the last; per image the top-left corner, the window against the
+    bottom-right corner and one around a mark pixel (its own where it holds one, else the case's first)"""
+    marks = _mark_pixels(c, d)
+    s = LARGE_WINDOW
+
+    def around(py, px):
+        return min(max(py - s // 2, 0) & ~1, c.ho - s), min(max(px - s // 2, 0) & ~1, c.wo - s)
+    images = sorted({0, c.n - 1} | {i for m in marks for i in (m[2] - 1, m[2]) if i >= 0})
+    wins = []
+    for img in images:
+        own = [m for m in marks if m[2] == img] or marks[:1]
+        spots = [(0, 0), (c.ho - s, c.wo - s)] + [around(m[3], m[4]) for m in own]
+        wins += [(img,) + sp for sp in dict.fromkeys(spots)]
+    return marks, wins
+
+
+def large_window_fp64(c, d, img, oy0, ox0):
+    """the layer on one output window, in fp64 on the CPU: the input window with its halo is gathered from the device; where it
+    touches the image's border that border is kept (replicate padding / zero extension are the layer's own), inside the image the
+    halo is real pixels.  -> numpy [LARGE_WINDOW, LARGE_WINDOW, c_out]"""
+    import torch
+    import torch.nn.functional as F
+    s = LARGE_WINDOW
+    cpu64 = lambda t: t.detach().cpu().double()  # noqa: E731
+    gdn = None if c.gdn is None else (cpu64(d['beta']), cpu64(d['gamma']))
+    if c.kind == 'gdn':
+        v = gdn_fp64(cpu64(d['x'][img, oy0:oy0 + s, ox0:ox0 + s]), gdn[0], gdn[1], c.gdn)
+    else:
+        tc = c.mode == abi.MODE_TCONV
+        # rows / columns of the input the window reads, before clipping to the image
+        lo = [(o // 2 - 1) if tc else (o * c.stride - c.pad) for o in (oy0, ox0)]
+        hi = [((o + s + 1) // 2) if tc else ((o + s - 1) * c.stride - c.pad + c.k - 1) for o in (oy0, ox0)]
+        r0, c0, r1, c1 = max(lo[0], 0), max(lo[1], 0), min(hi[0], c.h - 1), min(hi[1], c.w - 1)
+        if c.kind == 'images':  # 4:2:0 -> 4:4:4 as aivc_pack_images states it: level / 255, chroma by nearest neighbour, a zero 4th channel
+            assert r0 % 2 == 0 and c0 % 2 == 0
+            pl = d['planes']
+            ch = [cpu64(pl[nm][img, r0 // 2:r1 // 2 + 1, c0 // 2:c1 // 2 + 1]).repeat_interleave(2, 0).repeat_interleave(2, 1)
+                  [:r1 - r0 + 1, :c1 - c0 + 1] for nm in ('u', 'v')]
+            yy = cpu64(pl['y'][img, r0:r1 + 1, c0:c1 + 1])
+            patch = torch.stack([yy, ch[0], ch[1], torch.zeros_like(yy)], dim=-1) / 255.0
+        else:
+            patch = cpu64(d['x'][img, r0:r1 + 1, c0:c1 + 1])
+        cut = (c0 - lo[1], hi[1] - c1, r0 - lo[0], hi[0] - r1)  # what the image's border took away: left, right, top, bottom
+        pt = patch.permute(2, 0, 1)[None]
+        pt = F.pad(pt, cut, mode='constant', value=0.0) if tc else (F.pad(pt, cut, mode='replicate') if any(cut) else pt)
+        v = torch_fp64(c.mode, pt.permute(0, 2, 3, 1).numpy(), cpu64(d['w']).numpy(), cpu64(d['bias']).numpy(), c.stride, 0, c.k)[0]
+        if tc:  # patch row i is input row lo + i: output row 2 (lo + i) + ..; the window starts 2 rows in, the rest is the halo ring
+            v = v[2:2 + s, 2:2 + s]
+        assert tuple(v.shape) == (s, s, c.co), (tuple(v.shape), cut)
+        if gdn is not None:
+            v = gdn_fp64(v, gdn[0], gdn[1], c.gdn)
+    act = lambda a, t: torch.where(t > 0, t, t * 0.01) if a == abi.ACT_LEAKY else (t.clamp(min=0.0) if a == abi.ACT_RELU else t)  # noqa: E731
+    v = act(c.act1, v)
+    if 'mul' in d:
+        v = cpu64(d['mul'][img, oy0:oy0 + s, ox0:ox0 + s]) * v
+    if 'res' in d:
+        v = v + cpu64(d['res'][img, oy0:oy0 + s, ox0:ox0 + s])
+    return act(c.act2, v).numpy()

@@ -90,29 +90,53 @@ def test_range_coder_round_trip_4k_latent(cuda):
 
 
 def test_batch_beyond_4gb_goes_out_as_sub_batches(cuda):
-    """the LDS-DMA loader addresses its input with 32-bit BYTE offsets: a batch of more than 4 GB (34 half-resolution
-    64-channel maps of a 1080p frame = 4.5 GB) is split into sub-batch launches inside aivc_conv2d -- same bits as the
-    caller splitting it, fused GDN and the transposed conv included"""
+    """A batch of more than 4 GB (34 half-resolution 64-channel maps of a 1080p frame = 4.5 GB) gives the bits of the caller
+    splitting it, with every launch on the kernel named here (tests/test_gpu_large_batches.py holds the same launches to fp64):
+      1. 5x5 s2 64 -> 128 + GDN under the default contract (version 2): the Winograd chain covers the conv and has no fused GDN,
+         so ops.conv2d issues 302 + 400, both of which address the batch with 64-bit bases -- no splitter involved;
+      2. the same request under 'fp32' (version 1): one fused launch (155) of the LDS-DMA loader, whose 32-bit BYTE offsets
+         for_sub_batches of conv_mfma_kernel.h serves by sub-batches of 32 + 2 images inside aivc_conv2d;
+      3. ... under 'bf16x3': the precision mode's kernels (1150) behind the same splitter (conv_bf16x3.hip);
+      4. the transposed 3x3 64 -> 32 (not covered by version 2: 113 under either contract) behind the splitter."""
     from aivc_amd import ops
-    g = torch.Generator(device='cpu').manual_seed(21)
-    x = torch.randn((34, 540, 960, 64), generator=g).to(cuda)
-    w = (torch.randn((128, 5, 5, 64), generator=g) / 40.0).to(cuda)
-    b = torch.randn(128, generator=g).to(cuda)
-    beta = (torch.rand(128, generator=g) + 0.5).to(cuda)
-    gamma = (torch.rand((128, 128), generator=g) * 0.01).to(cuda)
+    from op_cases import profiled
+    g = torch.Generator(device=cuda).manual_seed(21)
+    x = torch.randn((34, 540, 960, 64), device=cuda, generator=g)
+    w = torch.randn((128, 5, 5, 64), device=cuda, generator=g) / 40.0
+    b = torch.randn(128, device=cuda, generator=g)
+    beta = torch.rand(128, device=cuda, generator=g) + 0.5
+    gamma = torch.rand((128, 128), device=cuda, generator=g) * 0.01
     assert x.numel() * 4 > 2 ** 32
-    full = ops.conv2d(x, w, b, stride=2, pad=2, gdn=(beta, gamma, False))
+
+    def conv_gdn(lo, hi, codes):
+        y, got = profiled(lambda: ops.conv2d(x[lo:hi].contiguous(), w, b, stride=2, pad=2, gdn=(beta, gamma, False)))
+        assert got == codes, (lo, hi, got)
+        return y
+    full = conv_gdn(0, 34, [302, 400])
     for lo, hi in ((0, 17), (17, 34)):
-        assert torch.equal(full[lo:hi], ops.conv2d(x[lo:hi].contiguous(), w, b, stride=2, pad=2, gdn=(beta, gamma, False)))
+        assert torch.equal(full[lo:hi], conv_gdn(lo, hi, [302, 400]))
     del full
-    prev = ops.set_precision('bf16x3')  # the precision mode's launches split the same way (its own kernels)
+    prev = ops.set_precision('fp32')  # version 1: the fused launch, split inside aivc_conv2d
     try:
-        full = ops.conv2d(x, w, b, stride=2, pad=2, gdn=(beta, gamma, False))
-        assert torch.equal(full[30:34], ops.conv2d(x[30:34].contiguous(), w, b, stride=2, pad=2, gdn=(beta, gamma, False)))
+        full = conv_gdn(0, 34, [155])
+        for lo, hi in ((0, 17), (17, 34)):
+            assert torch.equal(full[lo:hi], conv_gdn(lo, hi, [155]))
         del full
     finally:
         ops.set_precision(prev)
-    wt = (torch.randn((32, 3, 3, 64), generator=g) / 24.0).to(cuda)
-    bt = torch.randn(32, generator=g).to(cuda)
-    full = ops.conv2d(x, wt, bt, mode=abi.MODE_TCONV, stride=2, act1=abi.ACT_LEAKY)
-    assert torch.equal(full[30:34], ops.conv2d(x[30:34].contiguous(), wt, bt, mode=abi.MODE_TCONV, stride=2, act1=abi.ACT_LEAKY))
+    prev = ops.set_precision('bf16x3')  # the precision mode's launches split the same way (its own kernels)
+    try:
+        full = conv_gdn(0, 34, [1150])
+        assert torch.equal(full[30:34], conv_gdn(30, 34, [1150]))
+        del full
+    finally:
+        ops.set_precision(prev)
+    wt = torch.randn((32, 3, 3, 64), device=cuda, generator=g) / 24.0
+    bt = torch.randn(32, device=cuda, generator=g)
+
+    def tconv(lo, hi):
+        y, got = profiled(lambda: ops.conv2d(x[lo:hi].contiguous(), wt, bt, mode=abi.MODE_TCONV, stride=2, act1=abi.ACT_LEAKY))
+        assert got == [113], (lo, hi, got)
+        return y
+    full = tconv(0, 34)
+    assert torch.equal(full[30:34], tconv(30, 34))

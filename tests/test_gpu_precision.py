@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from aivc_amd import abi
+from conv_cases import torch_fp64
 
 pytestmark = pytest.mark.gpu
 
@@ -26,21 +27,6 @@ LAYERS = [  # mode, k, stride, pad, c_in, c_out, h, w, fused gdn (0 / 1 / 2), re
 ]
 
 
-def _torch_fp64(mode, x, w, b, stride, pad, k):
-    """fp64 evaluation of the layer on the CPU (NHWC in / out): conv with replicate padding, or ConvTranspose2d k, s 2,
-    pad (1 + k) / 2 - 1, output_padding 1 (src/layers/misc/custom_conv_layers.py:129-253)"""
-    import torch.nn.functional as F
-    xt = torch.from_numpy(x).double().permute(0, 3, 1, 2)
-    wt = torch.from_numpy(w).double()  # OHWI
-    if mode == abi.MODE_CONV:
-        xp = F.pad(xt, (pad, pad, pad, pad), mode='replicate') if pad else xt
-        y = F.conv2d(xp, wt.permute(0, 3, 1, 2), torch.from_numpy(b).double(), stride=stride)
-    else:
-        y = F.conv_transpose2d(xt, wt.permute(3, 0, 1, 2), torch.from_numpy(b).double(), stride=2,
-                               padding=int((1 + k) / 2 - 1), output_padding=1)
-    return y.permute(0, 2, 3, 1).contiguous()
-
-
 @pytest.mark.parametrize('case', LAYERS)
 def test_layer_error_against_fp64(case, cuda):
     from aivc_amd import ops
@@ -49,7 +35,7 @@ def test_layer_error_against_fp64(case, cuda):
     x = rng.standard_normal((2, h, w, ci), dtype=np.float32)
     wt = (rng.standard_normal((co, k, k, ci), dtype=np.float32) / np.sqrt(k * k * ci)).astype(np.float32)
     b = rng.standard_normal(co, dtype=np.float32)
-    ref = _torch_fp64(mode, x, wt, b, s, pad, k)
+    ref = torch_fp64(mode, x, wt, b, s, pad, k)
     g = None
     if gdn:
         beta = (np.abs(rng.standard_normal(co)) + 0.5).astype(np.float32)

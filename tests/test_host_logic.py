@@ -97,16 +97,17 @@ def test_conv_dispatch_of_the_default_model_at_1080p():
         assert got == r[16:], (r[:16], got, r[16:])
 
 
-def _variant(mode, k, s, pad, n, h, w, ci, co, gdn=0, tail=0, algo=None):
-    """aivc_conv2d_variant of one fp32 launch with stand-in pointers (nothing is allocated, nothing launched)"""
+def _variant(mode, k, s, pad, n, h, w, ci, co, gdn=0, tail=0, algo=None, precision=None, flags=0):
+    """aivc_conv2d_variant of one launch (fp32 unless precision says otherwise) with stand-in pointers (nothing is allocated, nothing
+    launched)"""
     from aivc_amd import _lib, abi
     a = 1 << 20
     ho, wo = abi.conv_out_size(mode, h, w, k, s, pad)
-    p = abi.ConvParams(mode, k, s, pad, n, h, w, ci, ho, wo, co, 0, 0, abi.ALGO_AUTO if algo is None else algo, gdn, 0, a, 2 * a, 3 * a,
+    p = abi.ConvParams(mode, k, s, pad, n, h, w, ci, ho, wo, co, 0, 0, abi.ALGO_AUTO if algo is None else algo, gdn, flags, a, 2 * a, 3 * a,
                        None, None, 6 * a, 7 * a if gdn else None, 8 * a if gdn else None)
     if tail:
         p.tail_w, p.tail_bias, p.tail_c_out = 9 * a, 10 * a, tail
-    p.precision = abi.PREC_FP32
+    p.precision = abi.PREC_FP32 if precision is None else precision
     return _lib.load()['aivc_conv2d_variant'](ctypes.byref(p))
 
 
@@ -139,6 +140,56 @@ def test_conv_dispatch_at_the_loaders_4_gib_limit():
     assert 4096 * 8192 * 48 * 4 > 1 << 32 and 4096 * 8192 * 48 < (1 << 32) - 1
     assert _variant(*tconv, 1, 4096, 8192, 48, 64) == 111
     assert _variant(*tconv, 1, 4096, 8192, 48, 64, gdn=2) == 161
+
+
+def test_conv_dispatch_limits_of_winograd_thin_and_resident_gdn():
+    """The addressing limits the other families declare, at the limit and just below it (stand-in pointers, nothing launched).
+    Winograd chain (conv2d_wino_supported): 32-bit byte offsets inside ONE image's input (below 0xFFFF0000 bytes), a block list an
+    int counts (below 2^31 - 1 entries), the transposed form's 4 KB zero page (c_in <= 960).  A covered layer beyond a limit is
+    AIVC_ERR_UNSUPPORTED, never a version-1 code: the header says it is computed by the Winograd chain or not at all.
+    Thin transposed layers (thin_mfma_ok): an image below 0x7FFFFFC0 bytes goes through the MFMA kernel's buffer descriptor (2), a
+    larger one to the VALU kernel (1), which indexes with size_t throughout and has no limit of its own.
+    Resident (I)GDN (gdn_resident_supported): an int counts the pixels (below 0x7FFFFFC0); from there the launch is version 1's
+    GDN mode, which at 128 channels and that many pixels is the scalar kernel (0: the MFMA family stops at 2^32 - 1 elements)."""
+    from aivc_amd import abi
+    w2, unsupported = abi.PREC_FP32_WINO, abi.ERR_UNSUPPORTED
+    conv3, conv5, tconv5 = (abi.MODE_CONV, 3, 1, 1), (abi.MODE_CONV, 5, 2, 2), (abi.MODE_TCONV, 5, 2, 0)
+    forms = ((conv3, 128, 301), (conv5, 128, 302), (tconv5, 64, 303))
+    # one image's input: c_in 32 = 128 bytes per pixel, 0xFFFF0000 / 128 = 33553920 = 65535 * 512 pixels
+    assert 33553920 * 128 == 0xFFFF0000 and 33553919 == 7 * 4793417
+    for form, co, code in forms:
+        assert _variant(*form, 1, 4793417, 7, 32, co, precision=w2) == code      # 128 bytes below the limit
+        assert _variant(*form, 1, 65535, 512, 32, co, precision=w2) == unsupported
+        assert _variant(*form, 1, 65535, 512, 32, co) not in (code, unsupported)  # (version 1 has kernels for it)
+    # the block list: images x blocks of 16 x 16 grid pixels x blocks of 64 output channels (x 4 classes, transposed form).
+    # conv forms, c_out 128: an even count; 2^31 - 2 = 2 * 17043521 * 7 * 9 (100 x 130 grid pixels: 7 x 9 blocks)
+    assert 2 * 17043521 * 63 == 0x7FFFFFFE
+    assert _variant(*conv3, 17043521, 100, 130, 32, 128, precision=w2) == 301
+    assert _variant(*conv5, 17043521, 200, 260, 32, 128, precision=w2) == 302
+    for form in (conv3, conv5):  # 2^31 entries
+        g = 2 if form is conv5 else 1
+        assert _variant(*form, 1 << 24, 128 * g, 128 * g, 32, 128, precision=w2) == unsupported
+    # transposed form, c_out 64: a multiple of 4; 2^31 - 4 = 4 * 2304167 * 233 (3728 x 16 grid pixels: 233 x 1 blocks)
+    assert 4 * 2304167 * 233 == 0x7FFFFFFC
+    assert _variant(*tconv5, 2304167, 3728, 16, 32, 64, precision=w2) == 303
+    assert _variant(*tconv5, 1 << 21, 4096, 16, 32, 64, precision=w2) == unsupported
+    # the transposed form's zero page
+    assert _variant(*tconv5, 1, 270, 480, 960, 64, precision=w2) == 303
+    assert _variant(*tconv5, 1, 270, 480, 992, 64, precision=w2) == unsupported
+    assert _variant(*tconv5, 1, 270, 480, 992, 64) == 111
+    # thin transposed layer, c_in 64 = 256 bytes per pixel: 2^23 - 1 = 47 * 178481 pixels are 192 bytes below 0x7FFFFFC0
+    assert 47 * 178481 * 256 == 0x7FFFFFC0 - 192 and 2048 * 4096 * 256 == 0x7FFFFFC0 + 64
+    for prec in (abi.PREC_FP32, w2):
+        assert _variant(*tconv5, 1, 47, 178481, 64, 3, precision=prec) == 2
+        assert _variant(*tconv5, 1, 2048, 4096, 64, 3, precision=prec) == 1
+        assert _variant(*tconv5, 2, 2048, 4096, 64, 3, precision=prec) == 1
+    # stand-alone (I)GDN of 128 channels: the pixels of the whole batch
+    for mode in (abi.MODE_GDN, abi.MODE_IGDN):
+        for prec in (abi.PREC_FP32, w2):
+            assert _variant(mode, 1, 1, 0, 1, 1, 0x7FFFFFBF, 128, 128, precision=prec) == 400
+            assert _variant(mode, 1, 1, 0, 243, 7, 1262483, 128, 128, precision=prec) == 400  # 3^5 * 7 * 1262483 = 0x7FFFFFBF
+            assert _variant(mode, 1, 1, 0, 1, 1, 0x7FFFFFC0, 128, 128, precision=prec) == 0
+            assert _variant(mode, 1, 1, 0, 64, 31 * 601, 1801, 128, 128, precision=prec) == 0  # 2^6 * 31 * 601 * 1801 = 0x7FFFFFC0
 
 
 def test_product_path_refuses_cpu_tensors():

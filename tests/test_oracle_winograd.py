@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from aivc_amd import abi
+from conv_cases import torch_fp64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -26,14 +27,9 @@ def both(oracle):
 
 
 def _ref(kind, x, w, b):
-    xt = torch.from_numpy(x).double().permute(0, 3, 1, 2)
-    if kind == 'conv3':
-        y = torch.nn.functional.conv2d(torch.nn.functional.pad(xt, (1, 1, 1, 1), mode='replicate'), torch.from_numpy(w).double().permute(0, 3, 1, 2), torch.from_numpy(b).double())
-    elif kind == 'conv5s2':
-        y = torch.nn.functional.conv2d(torch.nn.functional.pad(xt, (2, 2, 2, 2), mode='replicate'), torch.from_numpy(w).double().permute(0, 3, 1, 2), torch.from_numpy(b).double(), stride=2)
-    else:  # transposed 5x5 stride 2: w[co][ky][kx][ci] = torch weight[ci][co][ky][kx]; padding int((1 + k) / 2 - 1) = 2, output_padding 1
-        y = torch.nn.functional.conv_transpose2d(xt, torch.from_numpy(w).double().permute(3, 0, 1, 2), torch.from_numpy(b).double(), stride=2, padding=2, output_padding=1)
-    return y.permute(0, 2, 3, 1).numpy()
+    """the layer in fp64 (tests/conv_cases.py, torch_fp64)"""
+    mode, stride, pad, k = {'conv3': (abi.MODE_CONV, 1, 1, 3), 'conv5s2': (abi.MODE_CONV, 2, 2, 5), 'tconv5': (abi.MODE_TCONV, 2, 0, 5)}[kind]
+    return torch_fp64(mode, x, w, b, stride, pad, k).numpy()
 
 
 @pytest.mark.parametrize('kind,shape', [('conv3', (1, 13, 17, 32, 128)), ('conv5s2', (2, 15, 18, 32, 128)), ('tconv5', (1, 9, 11, 32, 64))])

@@ -1,5 +1,5 @@
-"""ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h and
-include/aivc_hip_rates.h (struct layouts, constants, prototypes).
+"""ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h,
+include/aivc_hip_rates.h and include/aivc_hip_digest.h (struct layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -7,7 +7,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -195,6 +195,11 @@ RATES_PROTOTYPES = {
     'aivc_dequantize_rows': [_f, _f, _f, _i32, _sz, _i32, _f],
 }
 
+# include/aivc_hip_digest.h: device only (its statement is RFC 1321, i.e. hashlib: tests/test_gpu_digest.py)
+DIGEST_PROTOTYPES = {
+    'aivc_md5_batch': [_f, C.c_int64, _i32, _f],
+}
+
 
 def declare(lib, suffix=''):
     """Attach argtypes/restype for every entry of the header; raises AttributeError when the
@@ -222,7 +227,8 @@ def declare(lib, suffix=''):
         wm.argtypes = [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, C.c_void_p]
         wm.restype = C.c_int
         fns['aivc_warp_modes'] = wm
-        for name, args in list(COLOR_PROTOTYPES.items()) + list(QUALITY_PROTOTYPES.items()) + list(RATES_PROTOTYPES.items()):
+        for name, args in list(COLOR_PROTOTYPES.items()) + list(QUALITY_PROTOTYPES.items()) + list(RATES_PROTOTYPES.items()) \
+                + list(DIGEST_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.argtypes = list(args) + [C.c_void_p]
             fn.restype = C.c_int

@@ -39,6 +39,11 @@ def parse_args(argv=None):
     p.add_argument('--rng_seed', default=666, type=int)
     p.add_argument('--cpu', action='store_true')
     p.add_argument('--log_dir', default='', type=str, help="the encoder's per-frame table goes to <log_dir>/detailed.txt (encode.py)")
+    p.add_argument('--digests', action='store_true',
+                   help='the encoder writes the manifest <bitstream_out>.md5 (encode.py --digests) and the decode is verified against it')
+    dec_cli.add_verify_flag(p)
+    from aivc_amd.cli_common import add_contract_flag
+    add_contract_flag(p, ('fp32', 'fp32w', 'auto'))
     enc_cli.add_rate_flags(p)
     a = p.parse_args(argv)
     enc_cli.check_rate_flags(p, a)
@@ -57,10 +62,15 @@ def main(argv=None):
                   '-o', a.bitstream_out, '--rate_step', str(a.rate_step)] + common
                  + (['--log_dir', a.log_dir] if a.log_dir else [])
                  + (['--idx_rate', str(a.idx_rate)] if a.idx_rate is not None else [])
-                 + (['--target_bpp', str(a.target_bpp)] if a.target_bpp > 0 else []))
+                 + (['--target_bpp', str(a.target_bpp)] if a.target_bpp > 0 else [])
+                 + (['--digests'] if a.digests else [])
+                 + (['--contract', a.contract] if a.contract not in (None, 'auto') else []))  # (auto is the decoder's choice)
     banner(('*' * 80).center(120))
     banner('Starting decoding'.center(120))
-    status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common)
+    verify = a.verify if a.verify else bool(a.digests)  # --digests verifies its own decode
+    status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common
+                          + ([] if not verify else ['--verify'] if verify is True else ['--verify', verify])
+                          + (['--contract', a.contract] if a.contract else []))
     from aivc_amd import parallel
     if parallel.rank_world()[0] != 0:  # multi-rank job: rank 0 evaluates
         return status

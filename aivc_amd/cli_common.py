@@ -30,6 +30,36 @@ def resolve_device(cpu_flag):
     return dev
 
 
+def add_contract_flag(p, choices):
+    """--contract (encode.py, decode.py, aivc.py): unset is the behaviour without the flag, AIVC_CONTRACT or the library default"""
+    p.add_argument('--contract', default=None, choices=list(choices),
+                   help='arithmetic contract of the run (aivc_amd.ops.set_precision); an encoder and a decoder must agree.  '
+                        'Unset: AIVC_CONTRACT or the library default'
+                        + ('.  auto: the contract named by the manifest <bitstream>.md5, else a trial decode of the first unit'
+                           if 'auto' in choices else ''))
+
+
+class contract_scope:
+    """`with contract_scope(name):` the run inside computes in contract `name` (None or 'auto': untouched here), the precision of
+    the process is what it was afterwards: tests call the CLIs' main() in-process"""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __enter__(self):
+        self.prev = None
+        if self.name and self.name != 'auto':
+            from . import ops
+            self.prev = ops.set_precision(self.name)
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev is not None:
+            from . import ops
+            ops.set_precision(self.prev)
+        return False
+
+
 def get_model(name, device, models_dir=None):
     import aivc_amd
     # the reference runs from src/ and reads ../models/<name>/0_model.pt (src/encode.py:101-103); AIVC_MODELS_DIR moves it

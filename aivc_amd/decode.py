@@ -2,24 +2,39 @@
 """decode.py CLI (flags of src/decode.py:24-40)."""
 import argparse
 
-from aivc_amd.cli_common import get_model, resolve_device
+from aivc_amd.cli_common import add_contract_flag, contract_scope, get_model, resolve_device
 from aivc_amd.real_life.decode import Decoder, decode_one_video, is_png_folder
 
 
-def main(argv=None):
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--cpu', action='store_true')
     p.add_argument('-i', default='../bitstream.bin', type=str)
     p.add_argument('-o', default='../compressed.yuv', type=str)
     p.add_argument('--model', default='ms_ssim-2021cc-6', type=str)
     p.add_argument('--rng_seed', default=666, type=int)
-    a = p.parse_args(argv)
+    add_verify_flag(p)
+    add_contract_flag(p, ('fp32', 'fp32w', 'auto'))
+    return p.parse_args(argv)
+
+
+def add_verify_flag(p):
+    """--verify [MANIFEST] (shared with aivc.py): '' is off, True the manifest next to the bitstream"""
+    p.add_argument('--verify', nargs='?', const=True, default='', metavar='MANIFEST',
+                   help='digest the decoded planes on the device and compare them with the manifest the encoder wrote under '
+                        '--digests (default: <bitstream>.md5); exit status 4 when planes differ and the stream itself decoded cleanly')
+
+
+def main(argv=None):
+    a = parse_args(argv)
     dev = resolve_device(a.cpu)
     out = a.o if a.o.endswith('.yuv') or is_png_folder(a.o) else a.o + '.yuv'  # ('dir/' or an existing directory: <idx>.png)
     dec = Decoder({'full_net': get_model(a.model, dev)}).eval()
     from aivc_amd.real_life.cat_binary_files import ContainerError
     try:
-        decode_one_video({'decoder': dec, 'bitstream_path': a.i, 'device': str(dev), 'out_file': out})
+        with contract_scope(a.contract):
+            decode_one_video({'decoder': dec, 'bitstream_path': a.i, 'device': str(dev), 'out_file': out, 'verify': a.verify,
+                              'contract': 'auto' if a.contract == 'auto' else ''})
     except ContainerError as e:  # a truncated / damaged file: say so and stop (exit status 2), no frames are written
         print('[ERROR] %s is not a complete bitstream: %s' % (a.i, e))
         raise SystemExit(2)
@@ -28,9 +43,12 @@ def main(argv=None):
 
 def exit_status():
     """0, or 3 when the frames were written but some section did not decode cleanly ON ANY RANK (every rank records
-    the sections it decoded; the counts are summed over the job so that rank 0's status speaks for all of them)"""
-    from aivc_amd.real_life.decode import stream_error_count
-    return 3 if stream_error_count() else 0
+    the sections it decoded; the counts are summed over the job so that rank 0's status speaks for all of them), or 4 when every
+    section decoded cleanly but planes differ from the manifest's digests (--verify; a stream error takes precedence)"""
+    from aivc_amd.real_life.decode import stream_error_count, verify_mismatch_count
+    if stream_error_count():
+        return 3
+    return 4 if verify_mismatch_count() else 0
 
 
 def cli():

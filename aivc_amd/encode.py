@@ -3,7 +3,7 @@
 -i may also name a folder of the reference's pictures: PNG triplets (<idx>_{y,u,v}.png, or the CLIC layout) or <idx>.png RGB."""
 import argparse
 
-from aivc_amd.cli_common import get_model, resolve_device
+from aivc_amd.cli_common import add_contract_flag, contract_scope, get_model, resolve_device
 from aivc_amd.func_util.GOP_structure import generate_gop_struct
 from aivc_amd.real_life.encode import encode
 
@@ -45,6 +45,10 @@ def parse_args(argv=None):
     p.add_argument('--log_dir', default='', type=str,
                    help='write the per-frame table <log_dir>/detailed.txt (PSNR, rates, alpha, beta, loss, MS-SSIM) and print '
                         'the Estimated MS-SSIM line; off by default')
+    p.add_argument('--digests', action='store_true',
+                   help='write the sidecar manifest <bitstream>.md5: the arithmetic contract and one MD5 per reconstructed plane, '
+                        'computed on the device (decode.py --verify checks a decode against it); the bitstream does not change')
+    add_contract_flag(p, ('fp32', 'fp32w'))
     add_rate_flags(p)
     a = p.parse_args(argv)
     a.idx_rate = check_rate_flags(p, a)
@@ -58,9 +62,11 @@ def main(argv=None):
     nb_rates = len(model.codec_net.codec_net.gain_I.enc_gain_list) if a.idx_rate else 1
     if a.idx_rate > nb_rates - 1:
         raise SystemExit('[ERROR] --idx_rate %s: model %s has %d rate indices (0 ... %d)' % (a.idx_rate, a.model, nb_rates, nb_rates - 1))
-    return encode({'model': model, 'sequence_path': a.i, 'GOP_struct': generate_gop_struct(a.gop),
-                   'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
-                   'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp, 'rate_step': a.rate_step})
+    with contract_scope(a.contract):
+        return encode({'model': model, 'sequence_path': a.i, 'GOP_struct': generate_gop_struct(a.gop),
+                       'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
+                       'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp,
+                       'rate_step': a.rate_step, 'digests': a.digests})
 
 
 if __name__ == '__main__':

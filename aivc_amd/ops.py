@@ -110,6 +110,11 @@ if DEFAULT_CONTRACT not in _CONTRACT_NAMES:
 PRECISION = _CONTRACT_NAMES[DEFAULT_CONTRACT]
 
 
+def precision_name():
+    """the name set_precision() knows the current mode by"""
+    return {abi.PREC_FP32: 'fp32', abi.PREC_BF16X3: 'bf16x3', abi.PREC_FP32_WINO: 'fp32w'}[PRECISION]
+
+
 def set_precision(mode):
     """'fp32': version 1 of the arithmetic contract (9-tap chains) -- HIP == CPU oracle bit for bit, bitstreams reproducible on every GPU.
     'bf16x3': the precision MODE of the wide convolutions (include/aivc_hip.h, aivc_conv_params.precision): fp32 operands
@@ -517,6 +522,44 @@ def yuv8_to_rgb8(y, u, v, chroma_shift=1):
     _hbm_profiled('yuv8_to_rgb8', n * (h * w * 4 + 2 * ch * cw),
                   lambda: call('aivc_yuv8_to_rgb8', _p(y), _p(u), _p(v), n, h, w, ch, cw, chroma_shift, _p(rgb), _stream()))
     return rgb
+
+
+def md5_planes(planes):
+    """MD5 of n equal-sized uint8 buffers on the device (include/aivc_hip_digest.h): one message per lane, one launch.
+    planes: a contiguous uint8 CUDA tensor [n, ...] (message i is planes[i]), or a list of n contiguous uint8 CUDA tensors of one
+    size (views into a batch stack as they are: a message may start at any byte).  -> uint8 [n, 16] on the device, row i the
+    digest of message i in RFC 1321 byte order (bytes(row).hex() == hashlib.md5(message).hexdigest()).  No synchronisation: the
+    pointer table is one small host-to-device copy, the launch goes on the current stream."""
+    if isinstance(planes, (list, tuple)):
+        planes = [_dev(t, torch.uint8, 'planes[%d]' % i) for i, t in enumerate(planes)]
+        n = len(planes)
+        length = planes[0].numel() if n else 0
+        if any(t.numel() != length for t in planes):
+            raise ValueError('md5_planes: the planes of one call have one size, got %s' % sorted({t.numel() for t in planes}))
+        if len({t.device for t in planes}) > 1:
+            raise ValueError('md5_planes: planes on several devices')
+        device = planes[0].device if n else torch.device('cuda', torch.cuda.current_device())
+        ptrs = [t.data_ptr() for t in planes]
+    else:
+        planes = _dev(planes, torch.uint8, 'planes')
+        if planes.dim() < 1:
+            raise ValueError('md5_planes: expected [n, ...], got a scalar')
+        n = planes.shape[0]
+        length = planes.numel() // n if n else 0
+        device = planes.device
+        ptrs = [planes.data_ptr() + i * length for i in range(n)]
+    if length >= 1 << 31:
+        raise ValueError('md5_planes: %d bytes per plane, the kernel takes less than 2^31' % length)
+    out = torch.empty((n, 16), dtype=torch.uint8, device=device)
+    if n == 0:
+        return out
+    host = _pinned_staging(8 * n)  # (pinned staging and an asynchronous copy, as frame_maps_to_device)
+    host.numpy().view(np.uint64)[:] = np.asarray(ptrs, np.uint64)
+    table = torch.empty(8 * n, dtype=torch.uint8, device=device)
+    table.copy_(host, non_blocking=True)
+    _pinned_release(host)
+    _hbm_profiled('md5_planes', n * (length + 16), lambda: call('aivc_md5_batch', _p(table), length, n, _p(out), _stream()))
+    return out
 
 
 def downsample2x(x, ch0, nch):

@@ -102,15 +102,77 @@ def is_png_folder(out_file):
     return bool(out_file) and (out_file.endswith('/') or os.path.isdir(out_file))
 
 
+def digest_frames(frames, device):
+    """frames: a list of dicts of uint8 planes [1, h, w] (device tensors, or host tensors / arrays: those are copied over)
+    -> three uint8 device tensors [n, 16], the MD5 of every y, u and v plane (aivc_amd.ops.md5_planes: one launch per kind of
+    plane, so that the equal-sized planes of a kind share wavefronts; no synchronisation)"""
+    from .. import ops
+    return tuple(ops.md5_planes([torch.as_tensor(fr[c]).to(device).contiguous() for fr in frames]) for c in 'yuv')
+
+
+def digest_rows(frames, first, device):
+    """-> {absolute frame index: (md5 y, md5 u, md5 v)} as the manifest lists them (aivc_amd/digests.py); waits for the digests"""
+    from .. import digests
+    if not frames:
+        return {}
+    return digests.hex_rows(first, [d.cpu().numpy() for d in digest_frames(frames, device)])
+
+
+def probe_unit0(frame_codec, blob, device, contract):
+    """decode the first intra-period unit under `contract` -> how many of its sections did not decode to where their payload
+    ends (the trial decode of `--contract auto`, aivc_amd/digests.py: choose_contract); the precision is put back"""
+    from .. import ops
+    prev = ops.set_precision(contract)
+    try:
+        with torch.no_grad():
+            frame_codec.decode_video(blob, device, unit_filter=lambda u: u == 0)
+        torch.cuda.synchronize()
+        return len(frame_codec.stream_errors())
+    finally:
+        ops.set_precision(prev)
+
+
 def decode_one_video(param):
-    default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False}
+    """verify: '' (off), the path of a manifest (aivc_amd/digests.py), or True for '<bitstream>.md5': the decoded planes are
+    digested on the device and compared with the manifest's; one `[VERIFY] <n> frames, <k> planes differ` line and the first
+    eight differing '<idx>_<c>' names are printed, the frames are written regardless, verify_mismatch_count() says how many.
+    contract: '' (whatever the process runs in), a name of aivc_amd.ops.set_precision, or 'auto': the manifest's when there is
+    one (verification is then implied), else a trial decode of unit 0 (aivc_amd/digests.py: choose_contract).  The
+    precision of the process is put back before this returns."""
+    default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
+               'verify': '', 'contract': ''}
     decoder = get_value('decoder', param, default).eval()
     path = get_value('bitstream_path', param, default)
     dev = torch.device(get_value('device', param, default))
     out_file = get_value('out_file', param, default)
+    verify = get_value('verify', param, default)
+    contract = get_value('contract', param, default)
     print_log_msg('INFO', 'Bitstream path', '', path)
     with open(path, 'rb') as f:
         blob = f.read()
+    from .. import digests, ops, parallel
+    _VERIFY_BAD[0] = 0
+    manifest = None
+    manifest_file = verify if isinstance(verify, str) and verify else digests.manifest_path(path)
+    if verify or (contract == 'auto' and os.path.exists(manifest_file)):
+        manifest = digests.read_manifest(manifest_file)
+    prev_precision = ops.precision_name()
+    try:
+        if contract == 'auto':
+            fc0 = FrameCodec(decoder.full_net)
+            choice, _, note = digests.choose_contract(None if manifest is None else manifest.contract, prev_precision,
+                                                      lambda name: probe_unit0(fc0, blob, dev, name), parallel.rank_world()[1])
+            if note and parallel.rank_world()[0] == 0:
+                print(note)
+            ops.set_precision(choice)
+        elif contract:
+            ops.set_precision(contract)
+        return _decode_one_video(decoder, path, blob, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default))
+    finally:
+        ops.set_precision(prev_precision)
+
+
+def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstream_debug):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel
@@ -140,14 +202,31 @@ def decode_one_video(param):
     print_log_msg('RESULT', 'Number of frames', '[frame]', int(n))
     print_log_msg('RESULT', 'Decoding time', '[s]', '%.1f' % dt)
     print_log_msg('RESULT', 'Decoding FPS', '[frame/s]', '%.1f' % (n / dt))
+    found = None
+    if manifest is not None:  # (queued now, read after the frames have been written)
+        found = digest_frames(frames, dev) if frames else None
     if is_png_folder(out_file):
         write_png_folder(frames, first, out_file, dev)
     elif out_file:
         write_yuv(frames, out_file)
     dist_barrier_after_write(world)
-    if get_value('flag_bitstream_debug', param, default):
+    if manifest is not None:
+        from .. import digests
+        rows = {} if found is None else digests.hex_rows(first, [d.cpu().numpy() for d in found])
+        differing = digests.compare(manifest.rows, rows)
+        _VERIFY_BAD[0] = len(differing)
+        for line in digests.verify_lines(len(rows), differing):
+            print(line)
+    if flag_bitstream_debug:
         check_debug_md5(frames, first, debug_dir(path))
     return frames
+
+
+_VERIFY_BAD = [0]  # planes of the last decode_one_video whose digest is not the manifest's (rank 0)
+
+
+def verify_mismatch_count():
+    return _VERIFY_BAD[0]
 
 
 STREAM_ERRORS = []  # what the last decode_one_video found on THIS rank

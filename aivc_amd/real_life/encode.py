@@ -68,11 +68,15 @@ def encode(param):
     idx_rate): every unit gets the richest rate index of the grid 0, rate_step, ..., nb_rates - 1 whose GOP record fits
     target_bpp x w x h x (frames of the unit) / 8 bytes (aivc_amd/rate_control.py: a few bitstream-only encodes, then the
     final one); one `[RATE]` line per unit, a `[WARN]` line for a unit that does not fit at any rate; the returned dictionary
-    gains 'rates'.  Under torch.distributed.run every rank searches the units it codes."""
+    gains 'rates'.  Under torch.distributed.run every rank searches the units it codes.
+    digests: True -- the sidecar manifest '<final_file>.md5' (aivc_amd/digests.py): the arithmetic contract the encode ran in
+    and one MD5 per reconstructed plane, computed on the device where the planes lie (aivc_amd.ops.md5_planes); every rank
+    digests the frames of its units, rank 0 writes the file.  The bitstream is the same with and without it."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
-               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16}
+               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False}
     model = get_value('model', param, default)
+    want_digests = get_value('digests', param, default)
     seq = get_value('sequence_path', param, default)
     gop_name = get_value('GOP_struct_name', param, default)
     final_file = get_value('final_file', param, default)
@@ -108,9 +112,16 @@ def encode(param):
         else:
             enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last, idx_rate=idx_rate, stats=stats)
             blob = fc.assemble_video(enc)
+        n = last - first + 1
+        digested = None
+        if want_digests:  # (queued behind the encode, before the device is waited for)
+            from .. import ops
+            from .decode import digest_frames
+            contract = ops.precision_name()
+            digested = [(first + idx, r) for idx, r in _own_frames(enc) if idx < n]
+            digested = ([i for i, _ in digested], digest_frames([r for _, r in digested], dev) if digested else None)
         torch.cuda.synchronize()
     dt = time.time() - t0
-    n = last - first + 1
     est_bits, payload = fc.estimated_bits, float(fc.coded_payload_bytes)
     # squared error of the frames THIS process reconstructed (all of them on one GPU), summed over the ranks
     se = cnt = 0.0
@@ -144,6 +155,19 @@ def encode(param):
             seq_res = sequence_result_from_rows(rows, enc['nb_gop'], unit, first, n, lambdas)
             name = os.path.basename(os.path.normpath(seq))
             write_detailed_log(working_dir, seq_res, name[:-4] if name.endswith('.yuv') else name)
+    if digested is not None:  # 48 bytes per frame travel to rank 0 (to all, in fact), like the quality rows
+        from .. import digests
+        idxs, dig = digested
+        host = [] if dig is None else [t.cpu().numpy() for t in dig]  # y, u, v: [frames of this rank, 16] each
+        rows = {i: b''.join(d[k].tobytes() for d in host) for k, i in enumerate(idxs)}
+        if world > 1:
+            rows = parallel.gather_bytes_all(rows, list(range(first, first + n)), None, world, dev)
+        if rank == 0:
+            parent = os.path.dirname(final_file)
+            if parent:
+                os.makedirs(parent, exist_ok=True)
+            digests.write_manifest(digests.manifest_path(final_file), contract,
+                                   {i: (b[:16].hex(), b[16:32].hex(), b[32:].hex()) for i, b in rows.items()})
     if get_value('flag_bitstream_debug', param, default):
         from .decode import debug_dir, write_debug_md5
         for idx, r in mine:  # every rank writes the digests of its own frames
@@ -188,6 +212,14 @@ def encode(param):
     if budgeted is not None:
         out['rates'] = list(idx_rate)
     return out
+
+
+def _own_frames(enc):
+    """(display index in the video, reconstruction) of the frames of the units THIS process coded, padded repeats included"""
+    for u, g in enumerate(enc['recs']):
+        if g is not None:
+            for i, r in enumerate(g):
+                yield u * len(g) + i, r
 
 
 def _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev):

@@ -602,10 +602,11 @@ class FrameCodec:
             # stream is still doing (in encode -> decode sequences: the last level's synthesis of the encoder), so the
             # side streams do NOT wait for it: the first levels' serial y streams decode under that work.  (Kernel-
             # ready parameters are synchronised when they are built, layers/_cache.py.)
-            # Parameters the entropy stage reads DIRECTLY (conv biases, gain vectors, the hyperprior's inputs) are not
-            # behind that cache: if any parameter was modified in place or moved since the last decode (an asynchronous
-            # bias.add_ of a calibration, load_state_dict, .to() -- on the main stream), the side streams wait for the
-            # main stream once, here.
+            # Parameters the entropy stage reads DIRECTLY (gain vectors, the hyperprior's inputs) are not behind that
+            # cache (a conv bias is read in place too, but it is part of its layer's cache stamp: changing it rebuilds
+            # the entry behind the cache's device-wide wait): if any parameter was modified in place or moved since the
+            # last decode (an asynchronous gain.add_ of a calibration, load_state_dict, .to() -- on the main stream),
+            # the side streams wait for the main stream once, here (tests/test_gpu_schedules.py).
             stamp = self._param_stamp()
             if _os.environ.get('AIVC_DEC_WAIT_MAIN') or stamp != getattr(self, '_dec_param_stamp', None):
                 for sd in sides:

@@ -12,7 +12,7 @@ import os as _os
 import torch
 
 from . import abi, ops, rate_control
-from .func_util.GOP_structure import FRAME_B, FRAME_I, FRAME_P, coding_levels, generate_gop_struct
+from .func_util.GOP_structure import FRAME_B, FRAME_I, FRAME_P, coding_levels, generate_gop_struct, reference_closure
 from .real_life import cat_binary_files as container
 from .real_life import header as hdr
 from .real_life.bitstream import finalize_frames, launch_finalize, prepare_finalize, split_sections
@@ -65,16 +65,17 @@ def frame_types(gop, frames):
     return sorted({gop[f]['type'] for f in frames})
 
 
-def level_items(gop, level, unit_ids, ftype):
-    """[(unit, frame name), ...] of one frame type in a level: unit-major, then the level's order"""
-    return [(u, f) for u in unit_ids for f in level if gop[f]['type'] == ftype]
+def level_items(gop, level, unit_ids, ftype, need=None):
+    """[(unit, frame name), ...] of one frame type in a level: unit-major, then the level's order.
+    need (a partial decode): {unit: the frames of it that are decoded}; None: all of every unit"""
+    return [(u, f) for u in unit_ids for f in level if gop[f]['type'] == ftype and (need is None or f in need[u])]
 
 
-def level_batches(gop, level, unit_ids, max_batch, shard=None):
+def level_batches(gop, level, unit_ids, max_batch, shard=None, need=None):
     """(frame type, [(unit, frame name), ...]) batches of at most max_batch same-type frames of one
     dependency level (a level of a chained GOP mixes P and B frames); with a shard, this rank's share."""
     for ftype in frame_types(gop, level):
-        items = level_items(gop, level, unit_ids, ftype)
+        items = level_items(gop, level, unit_ids, ftype, need)
         if shard is not None:
             items = shard.mine(items)
         for s in range(0, len(items), max_batch):
@@ -366,18 +367,25 @@ class FrameCodec:
             ac.md5_errors = []
         return out
 
-    def check_sections(self, parsed):
+    def check_sections(self, parsed, need=None):
         """The section framing and the y map lists of EVERY frame of every unit, on the host, before any kernel or
         collective: a malformed file is then a ContainerError on every rank alike (each holds the whole bitstream) --
         with the check left to decode_y only the rank that owns the bad frame raised while its peers went on into
-        the level's exchange and waited for the collective timeout."""
-        for u, (gop_name, _, frames) in enumerate(parsed):
+        the level's exchange and waited for the collective timeout.
+        need (a partial decode): {unit: the frames of it that are decoded}; only those are looked at, and an entry of `parsed`
+        may be None for a unit that is not decoded at all."""
+        for u, rec in enumerate(parsed):
+            if rec is None:
+                continue
+            gop_name, _, frames = rec
             gop = generate_gop_struct(gop_name)
             names = sorted(gop, key=frame_index)
             if len(names) != len(frames):
                 raise container.ContainerError('unit %d: %d frames in the record, coding structure %s has %d'
                                                % (u, len(frames), gop_name, len(names)))
             for k, fb in enumerate(frames):
+                if need is not None and names[k] not in need[u]:
+                    continue
                 secs = split_sections(fb)
                 for net, sy in ((self.mof, secs[1]), (self.cod, secs[3])):
                     if net is self.mof and gop[names[k]]['type'] == FRAME_I:
@@ -386,17 +394,20 @@ class FrameCodec:
                     if ac is not None:
                         ac._parse_maps(sy[32:] if ac.flag_md5sum else sy, net.nb_ft_y, k)
 
-    def _entropy_bytes(self, parsed, members, data_dim):
+    def _entropy_bytes(self, parsed, members, data_dim, need=None):
         """device bytes the entropy stage of these units holds when all of it is issued at once: per coded y symbol the
         64-entry CDF window + sigma (132 B, real_life/bitstream.py _rows_workspace) + the symbol, per frame the
         hyperprior's activations and latents (bounded by 64 floats per y position per network).  The coded map counts
         are in the sections' first byte -- behind the 32-character md5 text under flag_md5sum
-        (ArithmeticCoder._strip_md5) -- and never more than the format's map limit."""
+        (ArithmeticCoder._strip_md5) -- and never more than the format's map limit.  need (a partial decode): {unit: the frames
+        of it that are decoded}; only those are counted."""
         h_y, w_y = data_dim['y']
         npix = h_y * w_y
         total = 0
         for i in members:
-            for fb in parsed[i][2]:
+            for k, fb in enumerate(parsed[i][2]):
+                if need is not None and 'frame_%d' % k not in need[i]:
+                    continue
                 secs = split_sections(fb)
                 for net, sy in ((self.mof, secs[1]), (self.cod, secs[3])):
                     ac = getattr(net, 'ac', None)
@@ -421,12 +432,13 @@ class FrameCodec:
             ts = self._param_list = list(self.net.parameters()) + list(self.net.buffers())
         return hash(tuple((t.data_ptr(), t._version) for t in ts))
 
-    def _level_work(self, shard, gop, level, unit_ids, h, w):
+    def _level_work(self, shard, gop, level, unit_ids, h, w, need=None):
         """-> (row-band context or None, this rank's batches of the level).  A banded level (_banded) is the same plan with
-        one-frame batches of EVERY frame: every rank of the group works on each of them, a band of rows each."""
+        one-frame batches of EVERY frame: every rank of the group works on each of them, a band of rows each.
+        need: as in level_items (a partial decode; never with a shard)."""
         if self._banded(shard, len(unit_ids) * len(level), h, w):
             return shard.bands(), level_batches(gop, level, unit_ids, 1)
-        return None, level_batches(gop, level, unit_ids, self.max_batch, shard)
+        return None, level_batches(gop, level, unit_ids, self.max_batch, shard, need)
 
     def encode_units(self, units, gop_name, idx_rate=0., shard=None, recon='all', stats=None, stats_units=None):
         """units: list of frame lists (display order, each len == len(GOP struct)).
@@ -546,11 +558,11 @@ class FrameCodec:
         blobs = [container.pack_gop(heads[u], [fbytes[u][f] for f in names]) for u in range(len(units))]
         return blobs, [[rec[u][f] for f in names] for u in range(len(units))], data_dim
 
-    def decode_units(self, gop_blobs, data_dim, device=None, shard=None):
+    def decode_units(self, gop_blobs, data_dim, device=None, shard=None, wanted=None):
         """-> [reconstructions (display order) per unit]; see _decode_units_gen."""
-        return self.decode_units_finish(self.decode_units_begin(gop_blobs, data_dim, device, shard))
+        return self.decode_units_finish(self.decode_units_begin(gop_blobs, data_dim, device, shard, wanted))
 
-    def decode_units_begin(self, gop_blobs, data_dim, device=None, shard=None):
+    def decode_units_begin(self, gop_blobs, data_dim, device=None, shard=None, wanted=None):
         """First half of decode_units: parse the records and issue the entropy stage of the WHOLE video on the side
         streams (when its CDF windows fit, _entropy_budget); nothing is queued on the main stream.  A caller with other
         main-stream work -- the next clip's encode (src/real_life/encode.py and decode.py are two processes on two
@@ -558,7 +570,7 @@ class FrameCodec:
         _begin and _finish: the serial range-coder streams (the I frame's y stream at the head, 0.5 / 2.1 M symbols at
         1080p / 4K high rate) then decode under that work instead of in front of the first synthesis.
         -> a handle for decode_units_finish."""
-        g = self._decode_units_gen(gop_blobs, data_dim, device, shard)
+        g = self._decode_units_gen(gop_blobs, data_dim, device, shard, wanted)
         try:
             next(g)
         except StopIteration as e:
@@ -576,7 +588,20 @@ class FrameCodec:
             except StopIteration as e:
                 return e.value
 
-    def _decode_units_gen(self, gop_blobs, data_dim, device=None, shard=None):
+    def _needed_frames(self, parsed, wanted):
+        """a partial decode's plan: {unit: the reference closure of wanted[unit]} for the units something is wanted from"""
+        need = {}
+        for i, rec in enumerate(parsed):
+            if rec is None:
+                continue
+            gop = generate_gop_struct(rec[0])
+            unknown = sorted(set(wanted[i]) - set(gop))
+            if unknown:
+                raise ValueError('unit %d: coding structure %s has no %s' % (i, rec[0], ', '.join(unknown)))
+            need[i] = reference_closure(gop, wanted[i])
+        return need
+
+    def _decode_units_gen(self, gop_blobs, data_dim, device=None, shard=None, wanted=None):
         """-> [reconstructions (display order) per unit] (a generator: yields once per coding-structure group, right
         after that group's entropy stage has been issued up front; decode_units runs it through).  Units are grouped by
         their coding structure; each carries the rate index of its own GOP header, so a video whose units were coded at
@@ -584,13 +609,25 @@ class FrameCodec:
         for this rank's frames; one exchange of the new reconstructions per level).
         Stage 1 entropy-decodes EVERY frame of every unit (entropy_chunk frames at a time: that many
         range-coder streams run concurrently, one wavefront each; the serial coder is off the
-        frame-to-frame critical path).  Stage 2 reconstructs level by level in batches."""
-        parsed = [container.unpack_gop(g) for g in gop_blobs]
-        self.check_sections(parsed)
+        frame-to-frame critical path).  Stage 2 reconstructs level by level in batches.
+        wanted (a partial decode; None: everything, as above): one collection of frame names per unit, empty or None for
+        a unit nothing is asked of -- that unit is not looked at (its record may be None) and comes back as None.  Of the
+        others both stages run for the reference closure of the wanted frames only (`need` below restricts every list
+        of frames the stages are fed from); frames of one level from different units still share a batch.  The unit's
+        list keeps display order and full length, None where a frame was not asked for: an ancestor that is decoded
+        but not wanted is dropped with the generator's state.  Same bits as the whole decode; not with a shard."""
+        if wanted is not None and shard is not None:
+            raise ValueError('wanted= is an option of unit-wise decoding (the level-sharded paths spread a unit over ranks)')
+        if wanted is not None and len(wanted) != len(gop_blobs):
+            raise ValueError('%d selections for %d units' % (len(wanted), len(gop_blobs)))
+        parsed = [container.unpack_gop(g) if wanted is None or wanted[i] else None for i, g in enumerate(gop_blobs)]
+        need = None if wanted is None else self._needed_frames(parsed, wanted)
+        self.check_sections(parsed, need)
         out = [None] * len(gop_blobs)
         groups = {}  # by coding structure alone: the members keep their own rate index, a level batch may mix them
-        for i, (name, _, _) in enumerate(parsed):
-            groups.setdefault(name, []).append(i)
+        for i, rec in enumerate(parsed):
+            if rec is not None:
+                groups.setdefault(rec[0], []).append(i)
         for gop_name, members in groups.items():
             gop = generate_gop_struct(gop_name)
             names = sorted(gop, key=frame_index)
@@ -613,13 +650,15 @@ class FrameCodec:
                     sd.wait_stream(main)
                 self._dec_param_stamp = stamp
             levels = coding_levels(gop)
+            if need is not None:  # a closure holds the references of its frames: the levels left empty are the deepest ones
+                levels = [level for level in levels if any(f in need[i] for i in members for f in level)]
             lat, ready = {}, {}
             rr = [0]
 
             h, w = data_dim['x']
 
             def my_items(level, ftype):
-                items = level_items(gop, level, members, ftype)
+                items = level_items(gop, level, members, ftype, need)
                 if shard is not None and not self._banded(shard, len(members) * len(level), h, w):
                     items = shard.mine(items)  # (a banded level's latents are decoded by every rank: no exchange)
                 return items
@@ -644,7 +683,7 @@ class FrameCodec:
 
             rec = {i: {} for i in members}
             ahead = self.entropy_lookahead
-            if ahead is None and self._entropy_bytes(parsed, members, data_dim) > self._entropy_budget(device):
+            if ahead is None and self._entropy_bytes(parsed, members, data_dim, need) > self._entropy_budget(device):
                 ahead = 2  # the windows of the whole group do not fit beside the activations: level by level
             if ahead is None:
                 # the WHOLE group's entropy stage up front, frames of one type from all dependency levels in the same
@@ -662,7 +701,7 @@ class FrameCodec:
             for li, level in enumerate(levels):
                 if li + ahead < len(levels):
                     issue_entropy(levels[li + ahead])
-                bands, batches = self._level_work(shard, gop, level, members, h, w)
+                bands, batches = self._level_work(shard, gop, level, members, h, w, need)
                 for ftype, chunk in batches:
                     for ev in {id(e): e for it in chunk for e in ready[it]}.values():
                         main.wait_event(ev)
@@ -680,7 +719,7 @@ class FrameCodec:
                 if bands is None:
                     share_level(shard, rec, gop, level, members, h, w, device or torch.device('cuda'))
             for i in members:
-                out[i] = [rec[i][f] for f in names]
+                out[i] = [rec[i][f] if wanted is None or f in wanted[i] else None for f in names]
         return out
 
     def encode_gop(self, frames, gop_name, idx_rate=0.):
@@ -724,9 +763,13 @@ class FrameCodec:
                                     enc['idx_end_frame'])
         return container.pack_video(vh, enc['gops'])
 
-    def decode_video(self, blob, device=None, unit_filter=None):
+    def decode_video(self, blob, device=None, unit_filter=None, frames=None, max_level=None):
         """-> list of uint8 plane dicts for frames idx_first..idx_last (padded frames removed);
-        frames of units filtered out are None."""
+        frames of units filtered out are None.
+        frames / max_level: a partial decode, see decode_indexed (the list is then None where a frame was not asked for)."""
+        if frames is not None or max_level is not None:
+            from . import partial
+            return self.decode_indexed(partial.indexed_from_blob(blob), device, unit_filter, frames, max_level)
         data_dim, first, last, gops = container.unpack_video(blob)
         if unit_filter is not None:
             self.check_sections([container.unpack_gop(g) for g in gops])  # (every rank: the units of its peers as well)
@@ -739,3 +782,27 @@ class FrameCodec:
             else:
                 frames.extend([None] * len(container.unpack_gop(g)[2]))
         return frames[:last - first + 1], data_dim, first, last
+
+    def decode_indexed(self, video, device=None, unit_filter=None, frames=None, max_level=None):
+        """Partial decode of a video given as aivc_amd.partial.IndexedVideo (a whole container, partial.indexed_from_blob,
+        or a file read through real_life.cat_binary_files.index_video: records of units the request does not touch may
+        be None).  -> (frames, data_dim, idx_first, idx_last) like decode_video, None where a frame was not asked for.
+        frames: absolute display indices (the video header's numbering, as in the manifest and the PNG names); max_level:
+        only frames whose dependency depth in their unit is at most that (a level deeper than the structure selects
+        everything); both: a frame must pass both.  Every unit counts with the length of its own coding structure.  The
+        padded repeats behind idx_last cannot be asked for; they are decoded where a wanted frame references them.
+        partial.FrameSelectionError (a ValueError) naming the stream's range for an empty selection, an index outside
+        idx_first ... idx_last or a negative level.  What is decoded is the reference closure of the selection, unit
+        by unit (decode_units, wanted=): the frames are bit-identical to those of a whole decode."""
+        from . import partial
+        wanted = partial.select(video.names, video.first, video.last, frames, max_level)
+        if unit_filter is not None:  # (every rank: the units of its peers as well, as in decode_video)
+            touched = [container.unpack_gop(g) if w else None for g, w in zip(video.gops, wanted)]
+            self.check_sections(touched, self._needed_frames(touched, wanted))
+            wanted = [w if unit_filter(u) else None for u, w in enumerate(wanted)]
+        dec = self.decode_units(video.gops, video.data_dim, device, wanted=wanted) if any(wanted) else [None] * len(wanted)
+        out = []
+        for d, n in zip(dec, partial.unit_lengths(video.names)):
+            out.extend([None] * n if d is None else d)
+        n_real = video.last - video.first + 1
+        return (out + [None] * n_real)[:n_real], video.data_dim, video.first, video.last

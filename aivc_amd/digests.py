@@ -97,6 +97,12 @@ def compare(expected, found):
     return out
 
 
+def manifest_subset(rows, indices):
+    """the manifest's rows of the frames a partial decode returned (compare() then counts exactly those; a returned frame the
+    manifest does not list has no row here and differs with all three planes)"""
+    return {i: rows[i] for i in indices if i in rows}
+
+
 def verify_lines(n_frames, differing):
     """what a decoder prints about a comparison"""
     lines = ['[VERIFY] %d frames, %d planes differ' % (n_frames, len(differing))]

@@ -87,3 +87,22 @@ def coding_levels(GOP_struct):
     for f, v in depth.items():
         levels.setdefault(v, []).append(f)
     return [sorted(levels[k], key=lambda s: int(s.split('_')[-1])) for k in sorted(levels)]
+
+
+def frame_depths(GOP_struct):
+    """{frame name: its dependency depth}, read off coding_levels (the level a frame is coded in IS its depth): the
+    `temporal level` of a partial decode.  1_GOP_8 has the depths 0 ... 4, 1_GOP_32 0 ... 6."""
+    return {f: k for k, level in enumerate(coding_levels(GOP_struct)) for f in level}
+
+
+def reference_closure(GOP_struct, names):
+    """the named frames and everything they reference, transitively through prev_ref / next_ref: what a decoder has to
+    reconstruct to hand out `names` (frame_5 of 1_GOP_32: frames 0, 32, 16, 8, 4, 6 and 5 of the 33)"""
+    out, todo = set(), list(names)
+    while todo:
+        f = todo.pop()
+        if f in out:
+            continue
+        out.add(f)  # (a name the structure does not have is a KeyError on the next line)
+        todo += [r for r in (GOP_struct[f]['prev_ref'], GOP_struct[f]['next_ref']) if r is not None]
+    return out

@@ -193,12 +193,27 @@ def gather_quality_rows(rows, keys, device=None):
     return {keys[i]: np.frombuffer(b, np.float64).copy() for i, b in got.items()}
 
 
-def decode_video_sharded(frame_codec, blob, device=None):
+def decode_video_sharded(frame_codec, blob, device=None, frames=None, max_level=None):
     """Every rank holds the bitstream; each decodes its units; rank 0 returns all frames as lists of
-    dicts of CPU uint8 tensors (None elsewhere)."""
+    dicts of CPU uint8 tensors (None elsewhere).
+    frames / max_level: a partial decode (FrameCodec.decode_indexed; `blob` may then also be an
+    aivc_amd.partial.IndexedVideo, the same on every rank).  The units keep their owners, a rank that owns none of the
+    units the request touches decodes nothing, only the frames asked for travel, and rank 0 returns the list of a single
+    process: None where a frame was not asked for."""
     rank, world = rank_world()
-    frames, data_dim, first, last = frame_codec.decode_video(
-        blob, device, unit_filter=lambda u: unit_owner(u, world) == rank)
+    mine = lambda u: unit_owner(u, world) == rank
+    if frames is None and max_level is None:
+        frames, data_dim, first, last = frame_codec.decode_video(blob, device, unit_filter=mine)
+        lengths = unit_lengths(blob) if world > 1 else None
+        asked = range(len(frames))
+    else:
+        from . import partial
+        video = blob if isinstance(blob, partial.IndexedVideo) else partial.indexed_from_blob(blob)
+        frames = None if frames is None else list(frames)
+        wanted = partial.select(video.names, video.first, video.last, frames, max_level)
+        frames, data_dim, first, last = frame_codec.decode_indexed(video, device, mine, frames, max_level)
+        lengths = partial.unit_lengths(video.names)
+        asked = [i - first for i in partial.selected_indices(video.names, first, wanted)]
     if world == 1:
         return [None if f is None else {k: f[k].cpu() for k in 'yuv'} for f in frames]
     # one all_gather of the 8-bit planes (every rank sends `per` frame slots of h*w + 2*hc*wc bytes, its decoded
@@ -206,18 +221,17 @@ def decode_video_sharded(frame_codec, blob, device=None):
     h, w = data_dim['x']
     hc, wc = (h + 1) // 2, (w + 1) // 2
     fsz = h * w + 2 * hc * wc
-    owner = [None] * len(frames)  # (rank, slot) of every frame: units are dealt round-robin, known everywhere
+    owner = [None] * len(frames)  # (rank, slot) of every frame asked for: units are dealt round-robin, known everywhere
     counts = [0] * world
     # every unit's OWN length: a container may mix coding structures (decode_video / decode_units accept that), and
     # the padded frames of the last unit are cut from the end of `frames`
-    i = 0
-    for u, n_u in enumerate(unit_lengths(blob)):
-        for _ in range(n_u):
-            if i < len(frames):
-                owner[i] = (unit_owner(u, world), counts[unit_owner(u, world)])
-                counts[unit_owner(u, world)] += 1
-                i += 1
-    assert i == len(frames), 'the container holds %d frames, decode_video returned %d' % (i, len(frames))
+    unit_of = [u for u, n_u in enumerate(lengths) for _ in range(n_u)]
+    assert len(unit_of) >= len(asked) and all(i < len(unit_of) for i in asked), \
+        'the container holds %d frames, decode_video returned %d' % (len(unit_of), len(frames))
+    for i in asked:
+        r = unit_owner(unit_of[i], world)
+        owner[i] = (r, counts[r])
+        counts[r] += 1
     per = max(counts)
     dev = next(f['y'].device for f in frames if f is not None) if any(f is not None for f in frames) else device
     cdev = _comm_device(None, dev)
@@ -233,8 +247,11 @@ def decode_video_sharded(frame_codec, blob, device=None):
     with _host_wait('decoded planes to the host'):
         recv = recv.cpu()
     out = []
-    for r, slot in owner:
-        row = recv[r * per + slot]
+    for at in owner:
+        if at is None:  # (a partial decode: not asked for)
+            out.append(None)
+            continue
+        row = recv[at[0] * per + at[1]]
         out.append({'y': row[:h * w].view(1, h, w), 'u': row[h * w:h * w + hc * wc].view(1, hc, wc),
                     'v': row[h * w + hc * wc:].view(1, hc, wc)})
     return out

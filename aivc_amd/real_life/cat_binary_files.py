@@ -66,6 +66,56 @@ def unpack_gop(blob):
     return name, idx_rate, frames
 
 
+# ---- the same framing read from a seekable file, without the payloads ----------------------------
+def _read_exact(f, n, what):
+    b = f.read(n)
+    if len(b) != n:
+        raise ContainerError('%s: %d bytes at byte %d, need %d' % (what, len(b), f.tell() - len(b), n))
+    return b
+
+
+def index_video(fileobj, upto=None, upto_frame=None):
+    """-> (data_dim, idx_first, idx_last, [(offset, nbytes, gop_name, idx_rate) per unit walked]): where every GOP record
+    lies (offset of its first byte, behind the length prefix) and what its header says.  Reads the 18-byte video header and
+    10 bytes per unit -- the length prefix and the GOP header -- and seeks over the rest.
+    upto: stop behind that unit's prefix and header; upto_frame: stop behind the first unit that holds that absolute display
+    index (every unit counts with the length of its own coding structure).  What lies behind the last unit walked is not
+    looked at: a file that is truncated, or still being written, there decodes its earlier units.  Inside the walked part a
+    record that ends behind the end of the file is a ContainerError, as in unpack_video."""
+    from ..func_util.GOP_structure import generate_gop_struct
+    fileobj.seek(0, 2)
+    size = fileobj.tell()
+    fileobj.seek(0)
+    data_dim, nb_gop, first, last = hdr.parse_video_header(_read_exact(fileobj, hdr.VIDEO_HEADER_SIZE_BYTES, 'video header'))
+    pos, units, covered = hdr.VIDEO_HEADER_SIZE_BYTES, [], first
+    for g in range(nb_gop):
+        what = 'GOP record %d of %d' % (g, nb_gop)
+        fileobj.seek(pos)
+        n = int.from_bytes(_read_exact(fileobj, 4, what + ': length prefix'), 'big')
+        if pos + 4 + n > size:
+            raise ContainerError('%s: %d bytes announced at byte %d, only %d left' % (what, n, pos, size - pos - 4))
+        if n < hdr.GOP_HEADER_SIZE_BYTES:
+            raise ContainerError('%s: %d bytes, a GOP header has %d' % (what, n, hdr.GOP_HEADER_SIZE_BYTES))
+        name, idx_rate = hdr.parse_gop_header(_read_exact(fileobj, hdr.GOP_HEADER_SIZE_BYTES, what + ': GOP header'))
+        units.append((pos + 4, n, name, idx_rate))
+        pos += 4 + n
+        covered += len(generate_gop_struct(name))
+        if (upto is not None and g >= upto) or (upto_frame is not None and covered > upto_frame):
+            break
+    return data_dim, first, last, units
+
+
+def read_units(fileobj, units, chosen):
+    """units: the list index_video returned; chosen: unit numbers -> [GOP record or None per unit of the list]: the bytes of
+    the chosen units, nothing else is read"""
+    out = [None] * len(units)
+    for u in sorted(set(chosen)):
+        offset, n = units[u][:2]
+        fileobj.seek(offset)
+        out[u] = _read_exact(fileobj, n, 'GOP record %d' % u)
+    return out
+
+
 # ---- path-based API with the reference's signatures -------------------------------------------
 def cat_one_gop(param):
     default = {'idx_gop': 0, 'bitstream_dir': ''}

@@ -88,13 +88,15 @@ def write_yuv(frames, path):
                 f.write(np.ascontiguousarray(a).tobytes())
 
 
-def write_png_folder(frames, first, directory, device):
+def write_png_folder(frames, first, directory, device, indices=None):
     """decoded frames -> <directory>/<idx>.png, RGB pictures (func_util.img_processing.save_tensor_as_img, mode 'yuv420':
-    the colour conversion runs on the device, straight from the decoder's 8-bit planes)"""
+    the colour conversion runs on the device, straight from the decoder's 8-bit planes).  indices (a partial decode): the
+    absolute index of every frame handed in, instead of first, first + 1, ..."""
     from ..func_util.img_processing import save_tensor_as_img
     os.makedirs(directory, exist_ok=True)
     for i, fr in enumerate(frames):
-        save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % (first + i)), mode='yuv420')
+        idx = first + i if indices is None else indices[i]
+        save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % idx), mode='yuv420')
 
 
 def is_png_folder(out_file):
@@ -138,18 +140,31 @@ def decode_one_video(param):
     eight differing '<idx>_<c>' names are printed, the frames are written regardless, verify_mismatch_count() says how many.
     contract: '' (whatever the process runs in), a name of aivc_amd.ops.set_precision, or 'auto': the manifest's when there is
     one (verification is then implied), else a trial decode of unit 0 (aivc_amd/digests.py: choose_contract).  The
-    precision of the process is put back before this returns."""
+    precision of the process is put back before this returns.
+    frames: (a, b), absolute display indices, either end None for the stream's; max_level: a temporal level (the dependency
+    depth of a frame in its unit).  With either, this is a partial decode (FrameCodec.decode_indexed): the file is opened
+    through its index and only the units the request touches are read (what lies behind the last of them may be missing),
+    only the reference closure of the request is decoded, and the frames asked for are written in ascending order (pictures
+    under their absolute index), counted by `Number of frames` and compared with their rows of the manifest.  One line more
+    is printed: `[INFO] partial decode: <K> frames written, <D> of <C> coded frames decoded`.  A request outside the stream
+    is an aivc_amd.partial.FrameSelectionError."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
-               'verify': '', 'contract': ''}
+               'verify': '', 'contract': '', 'frames': None, 'max_level': None}
     decoder = get_value('decoder', param, default).eval()
     path = get_value('bitstream_path', param, default)
     dev = torch.device(get_value('device', param, default))
     out_file = get_value('out_file', param, default)
     verify = get_value('verify', param, default)
     contract = get_value('contract', param, default)
+    span, max_level = get_value('frames', param, default), get_value('max_level', param, default)
     print_log_msg('INFO', 'Bitstream path', '', path)
-    with open(path, 'rb') as f:
-        blob = f.read()
+    part = None
+    if span is not None or max_level is not None:
+        part = read_partial(path, span, max_level)
+        blob = None
+    else:
+        with open(path, 'rb') as f:
+            blob = f.read()
     from .. import digests, ops, parallel
     _VERIFY_BAD[0] = 0
     manifest = None
@@ -161,18 +176,43 @@ def decode_one_video(param):
         if contract == 'auto':
             fc0 = FrameCodec(decoder.full_net)
             choice, _, note = digests.choose_contract(None if manifest is None else manifest.contract, prev_precision,
-                                                      lambda name: probe_unit0(fc0, blob, dev, name), parallel.rank_world()[1])
+                                                      lambda name: probe_unit0(fc0, unit0_blob(path) if blob is None else blob, dev, name),
+                                                      parallel.rank_world()[1])
             if note and parallel.rank_world()[0] == 0:
                 print(note)
             ops.set_precision(choice)
         elif contract:
             ops.set_precision(contract)
-        return _decode_one_video(decoder, path, blob, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default))
+        return _decode_one_video(decoder, path, blob, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default), part)
     finally:
         ops.set_precision(prev_precision)
 
 
-def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstream_debug):
+def read_partial(path, span, max_level):
+    """the file of a partial decode -> (aivc_amd.partial.IndexedVideo with the records of the units the request touches, the
+    absolute indices asked for or None, max_level, the selection per unit): the index is walked as far as the request
+    reaches, and of the payload only those units are read"""
+    from .. import partial
+    from . import cat_binary_files as container
+    with open(path, 'rb') as f:
+        data_dim, first, last, units = container.index_video(f, upto_frame=None if span is None else span[1])
+        names = [u[2] for u in units]
+        idxs = None if span is None else list(partial.frame_range(span, first, last))
+        wanted = partial.select(names, first, last, idxs, max_level)
+        gops = container.read_units(f, units, [u for u, w in enumerate(wanted) if w])
+    return partial.IndexedVideo(data_dim, first, last, names, gops), idxs, max_level, wanted
+
+
+def unit0_blob(path):
+    """the first intra-period unit of a file as a container of its own (what probe_unit0 decodes), read through the index"""
+    from . import cat_binary_files as container
+    from . import header as hdr
+    with open(path, 'rb') as f:
+        data_dim, first, last, units = container.index_video(f, upto=0)
+        return container.pack_video(hdr.video_header_bytes(data_dim, 1, first, last), container.read_units(f, units, [0]))
+
+
+def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstream_debug, part=None):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel
@@ -180,7 +220,14 @@ def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstre
     rank, world = parallel.rank_world()
     fc = FrameCodec(decoder.full_net)
     with torch.no_grad():
-        if world > 1:  # one process per GPU: every rank decodes its intra-period units, rank 0 collects the planes
+        if part is not None:  # (the same calls, on the units that were read and for the frames asked for)
+            video, idxs, max_level, wanted = part
+            first, last = video.first, video.last
+            if world > 1:
+                frames = parallel.decode_video_sharded(fc, video, dev, frames=idxs, max_level=max_level)
+            else:
+                frames = fc.decode_indexed(video, dev, None, idxs, max_level)[0]
+        elif world > 1:  # one process per GPU: every rank decodes its intra-period units, rank 0 collects the planes
             _, first, last, _ = container.unpack_video(blob)
             frames = parallel.decode_video_sharded(fc, blob, dev)
         else:
@@ -197,8 +244,16 @@ def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstre
     if rank != 0:
         dist_barrier_after_write(world)
         return None
-    n = last - first + 1
+    shown = None  # a partial decode: the absolute indices of the frames asked for, ascending; `frames` becomes those frames
+    if part is not None:
+        from .. import partial
+        shown = partial.selected_indices(video.names, first, wanted)
+        frames = [frames[i - first] for i in shown]
+    n = last - first + 1 if shown is None else len(shown)
     print_log_msg('INFO', 'Decoding done', '', '')
+    if part is not None:
+        print('[INFO] partial decode: %d frames written, %d of %d coded frames decoded'
+              % (n, sum(len(c) for c in partial.closures(video.names, wanted)), partial.coded_frames(video.names, first, last)))
     print_log_msg('RESULT', 'Number of frames', '[frame]', int(n))
     print_log_msg('RESULT', 'Decoding time', '[s]', '%.1f' % dt)
     print_log_msg('RESULT', 'Decoding FPS', '[frame/s]', '%.1f' % (n / dt))
@@ -206,19 +261,27 @@ def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstre
     if manifest is not None:  # (queued now, read after the frames have been written)
         found = digest_frames(frames, dev) if frames else None
     if is_png_folder(out_file):
-        write_png_folder(frames, first, out_file, dev)
+        write_png_folder(frames, first, out_file, dev, indices=shown)
     elif out_file:
         write_yuv(frames, out_file)
     dist_barrier_after_write(world)
     if manifest is not None:
         from .. import digests
         rows = {} if found is None else digests.hex_rows(first, [d.cpu().numpy() for d in found])
-        differing = digests.compare(manifest.rows, rows)
+        expected = manifest.rows
+        if shown is not None:  # exactly the frames returned against their rows of the manifest
+            rows = {shown[k - first]: row for k, row in rows.items()}
+            expected = digests.manifest_subset(manifest.rows, shown)
+        differing = digests.compare(expected, rows)
         _VERIFY_BAD[0] = len(differing)
         for line in digests.verify_lines(len(rows), differing):
             print(line)
     if flag_bitstream_debug:
-        check_debug_md5(frames, first, debug_dir(path))
+        if shown is None:
+            check_debug_md5(frames, first, debug_dir(path))
+        else:
+            for idx, fr in zip(shown, frames):
+                check_debug_md5([fr], idx, debug_dir(path))
     return frames
 
 

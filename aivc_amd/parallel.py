@@ -193,27 +193,21 @@ def gather_quality_rows(rows, keys, device=None):
     return {keys[i]: np.frombuffer(b, np.float64).copy() for i, b in got.items()}
 
 
-def decode_video_sharded(frame_codec, blob, device=None, frames=None, max_level=None):
-    """Every rank holds the bitstream; each decodes its units; rank 0 returns all frames as lists of
-    dicts of CPU uint8 tensors (None elsewhere).
-    frames / max_level: a partial decode (FrameCodec.decode_indexed; `blob` may then also be an
-    aivc_amd.partial.IndexedVideo, the same on every rank).  The units keep their owners, a rank that owns none of the
-    units the request touches decodes nothing, only the frames asked for travel, and rank 0 returns the list of a single
-    process: None where a frame was not asked for."""
+def decode_video_sharded(frame_codec, video, device=None, frames=None, max_level=None, plan=None):
+    """Every rank holds the bitstream (its bytes, or an aivc_amd.partial.IndexedVideo, the same on every rank); each decodes
+    its units; rank 0 returns all frames as lists of dicts of CPU uint8 tensors (None elsewhere).
+    frames / max_level: a partial decode (FrameCodec.decode_video); plan: the aivc_amd.partial.Plan of this decode where the
+    caller has made it already.  The units keep their owners, a rank that owns none of the units the request touches decodes
+    nothing, only the frames asked for travel, and rank 0 returns the list of a single process: None where a frame was
+    not asked for.  A whole decode of bytes is asked of the codec as that, without the selection keywords."""
+    from . import partial
     rank, world = rank_world()
-    mine = lambda u: unit_owner(u, world) == rank
-    if frames is None and max_level is None:
-        frames, data_dim, first, last = frame_codec.decode_video(blob, device, unit_filter=mine)
-        lengths = unit_lengths(blob) if world > 1 else None
-        asked = range(len(frames))
-    else:
-        from . import partial
-        video = blob if isinstance(blob, partial.IndexedVideo) else partial.indexed_from_blob(blob)
-        frames = None if frames is None else list(frames)
-        wanted = partial.select(video.names, video.first, video.last, frames, max_level)
-        frames, data_dim, first, last = frame_codec.decode_indexed(video, device, mine, frames, max_level)
-        lengths = partial.unit_lengths(video.names)
-        asked = [i - first for i in partial.selected_indices(video.names, first, wanted)]
+    given = plan is not None
+    plan = plan or partial.plan(video, frames, max_level)
+    frames, data_dim, first, last = frame_codec.decode_video(video, device, unit_filter=lambda u: unit_owner(u, world) == rank,
+                                                             **({} if plan.whole and not given else {'plan': plan}))
+    lengths = partial.unit_lengths(plan.video.names)
+    asked = [i - first for i in plan.indices]
     if world == 1:
         return [None if f is None else {k: f[k].cpu() for k in 'yuv'} for f in frames]
     # one all_gather of the 8-bit planes (every rank sends `per` frame slots of h*w + 2*hc*wc bytes, its decoded
@@ -255,13 +249,6 @@ def decode_video_sharded(frame_codec, blob, device=None, frames=None, max_level=
         out.append({'y': row[:h * w].view(1, h, w), 'u': row[h * w:h * w + hc * wc].view(1, hc, wc),
                     'v': row[h * w + hc * wc:].view(1, hc, wc)})
     return out
-
-
-def unit_lengths(blob):
-    """number of frames of every intra-period unit of the video `blob`, in order"""
-    from .real_life import cat_binary_files as container
-    _, _, _, gops = container.unpack_video(blob)
-    return [len(container.unpack_gop(g)[2]) for g in gops]
 
 
 # ---- one clip over all GPUs: unit groups x temporal-layer sharding (SURVEY.md 8e) ---------------------------

@@ -1,6 +1,7 @@
 """Partial decode, the host side: which frames of which intra-period units a request names, and what has to be decoded
-for them.  No device work and no torch: FrameCodec.decode_indexed, parallel.decode_video_sharded and the drivers of
-real_life/decode.py all take their selection from here.
+for them.  No device work and no torch: FrameCodec.decode_video, parallel.decode_video_sharded and the drivers of
+real_life/decode.py all take their selection from here, as one Plan (plan()) that is made once per decode.  A whole decode is
+the plan of the request for everything.
 
 A request is a set of ABSOLUTE display indices (the numbering of the video header, idx_first ... idx_last, which the
 manifest and the PNG names use) and / or a temporal level: the dependency depth of a frame inside its unit
@@ -13,6 +14,11 @@ from .func_util.GOP_structure import frame_depths, generate_gop_struct, referenc
 # One video as the decoder takes it when it has not read the whole file: the header's fields, the coding structure of every
 # unit that was walked (in order, from unit 0) and the GOP records -- None for a unit whose bytes were not read.
 IndexedVideo = collections.namedtuple('IndexedVideo', 'data_dim first last names gops')
+
+# One decode, stated once.  video: the IndexedVideo; wanted: per unit the set of frame names that are RETURNED (select());
+# need: per unit the set that is DECODED; indices: the absolute display indices returned, ascending; whole: nothing was
+# selected, the decode is that of the whole stream.
+Plan = collections.namedtuple('Plan', 'video wanted need indices whole')
 
 
 class FrameSelectionError(ValueError):
@@ -39,14 +45,17 @@ def unit_lengths(names):
     return [len(generate_gop_struct(n)) for n in names]
 
 
-def locate(names, first, idx):
-    """absolute display index -> (unit, frame of the unit); None behind the units listed"""
-    pos = idx - first
-    for u, n in enumerate(unit_lengths(names)):
+def _locate(lengths, pos):
+    for u, n in enumerate(lengths):
         if pos < n:
             return u, pos
         pos -= n
     return None
+
+
+def locate(names, first, idx):
+    """absolute display index -> (unit, frame of the unit); None behind the units listed"""
+    return _locate(unit_lengths(names), idx - first)
 
 
 def _range_text(first, last):
@@ -77,9 +86,9 @@ def select(names, first, last, frames=None, max_level=None):
         if off:
             raise FrameSelectionError('frame %d is not in the stream; %s' % (off[0], _range_text(first, last)))
     wanted = [set() for _ in names]
-    depths = {}
+    depths, lengths = {}, unit_lengths(names)
     for idx in idxs:
-        at = locate(names, first, idx)
+        at = _locate(lengths, idx - first)
         if at is None:  # (a driver that indexed a file only as far as its request reaches never asks behind that)
             if frames is None:
                 break
@@ -97,8 +106,29 @@ def select(names, first, last, frames=None, max_level=None):
 
 
 def closures(names, wanted):
-    """per unit: the frames that have to be decoded for wanted[u] (reference_closure; empty where nothing is wanted)"""
-    return [reference_closure(generate_gop_struct(n), w) if w else set() for n, w in zip(names, wanted)]
+    """per unit: the frames that have to be decoded for wanted[u] (reference_closure; empty where nothing is wanted, and the
+    name of such a unit is not looked at).  ValueError for a frame name the unit's coding structure does not have."""
+    out = []
+    for u, (n, w) in enumerate(zip(names, wanted)):
+        gop = generate_gop_struct(n) if w else {}
+        unknown = sorted(set(w or ()) - set(gop))
+        if unknown:
+            raise ValueError('unit %d: coding structure %s has no %s' % (u, n, ', '.join(unknown)))
+        out.append(reference_closure(gop, w or ()))
+    return out
+
+
+def plan(video, frames=None, max_level=None):
+    """video: an IndexedVideo, or the bytes of a whole container; frames / max_level: as in select() -> Plan.
+    A request is decoded as far as its reference closure reaches.  A whole decode (neither frames nor max_level) decodes every
+    frame of every unit's coding structure, the padded repeats behind idx_last included -- they are part of its launches
+    and of what the bit-count check looks at -- and returns what select() returns for it: idx_first ... idx_last."""
+    if not isinstance(video, IndexedVideo):
+        video = indexed_from_blob(video)
+    whole = frames is None and max_level is None
+    wanted = select(video.names, video.first, video.last, frames, max_level)
+    need = [set(generate_gop_struct(n)) for n in video.names] if whole else closures(video.names, wanted)
+    return Plan(video, wanted, need, selected_indices(video.names, video.first, wanted), whole)
 
 
 def selected_indices(names, first, wanted):

@@ -88,14 +88,13 @@ def write_yuv(frames, path):
                 f.write(np.ascontiguousarray(a).tobytes())
 
 
-def write_png_folder(frames, first, directory, device, indices=None):
+def write_png_folder(frames, directory, device, indices):
     """decoded frames -> <directory>/<idx>.png, RGB pictures (func_util.img_processing.save_tensor_as_img, mode 'yuv420':
-    the colour conversion runs on the device, straight from the decoder's 8-bit planes).  indices (a partial decode): the
-    absolute index of every frame handed in, instead of first, first + 1, ..."""
+    the colour conversion runs on the device, straight from the decoder's 8-bit planes).  indices: the absolute index of
+    every frame handed in"""
     from ..func_util.img_processing import save_tensor_as_img
     os.makedirs(directory, exist_ok=True)
-    for i, fr in enumerate(frames):
-        idx = first + i if indices is None else indices[i]
+    for idx, fr in zip(indices, frames):
         save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % idx), mode='yuv420')
 
 
@@ -112,22 +111,21 @@ def digest_frames(frames, device):
     return tuple(ops.md5_planes([torch.as_tensor(fr[c]).to(device).contiguous() for fr in frames]) for c in 'yuv')
 
 
-def digest_rows(frames, first, device):
-    """-> {absolute frame index: (md5 y, md5 u, md5 v)} as the manifest lists them (aivc_amd/digests.py); waits for the digests"""
-    from .. import digests
-    if not frames:
-        return {}
-    return digests.hex_rows(first, [d.cpu().numpy() for d in digest_frames(frames, device)])
-
-
-def probe_unit0(frame_codec, blob, device, contract):
-    """decode the first intra-period unit under `contract` -> how many of its sections did not decode to where their payload
-    ends (the trial decode of `--contract auto`, aivc_amd/digests.py: choose_contract); the precision is put back"""
+def probe_unit0(frame_codec, path, plan, device, contract):
+    """decode the first intra-period unit, as a video of that one unit, under `contract` -> how many of its sections did not
+    decode to where their payload ends (the trial decode of `--contract auto`, aivc_amd/digests.py: choose_contract); the
+    precision is put back.  The unit's record is the plan's, or read through the index where the request does not touch it."""
     from .. import ops
+    from . import cat_binary_files as container
+    video = plan.video
+    unit0 = video.gops[0]
+    if unit0 is None:
+        with open(path, 'rb') as f:
+            unit0 = container.read_units(f, container.index_video(f, upto=0)[3], [0])[0]
     prev = ops.set_precision(contract)
     try:
         with torch.no_grad():
-            frame_codec.decode_video(blob, device, unit_filter=lambda u: u == 0)
+            frame_codec.decode_video(video._replace(names=video.names[:1], gops=[unit0]), device)
         torch.cuda.synchronize()
         return len(frame_codec.stream_errors())
     finally:
@@ -142,12 +140,12 @@ def decode_one_video(param):
     one (verification is then implied), else a trial decode of unit 0 (aivc_amd/digests.py: choose_contract).  The
     precision of the process is put back before this returns.
     frames: (a, b), absolute display indices, either end None for the stream's; max_level: a temporal level (the dependency
-    depth of a frame in its unit).  With either, this is a partial decode (FrameCodec.decode_indexed): the file is opened
-    through its index and only the units the request touches are read (what lies behind the last of them may be missing),
-    only the reference closure of the request is decoded, and the frames asked for are written in ascending order (pictures
+    depth of a frame in its unit).  With either, this is a partial decode: the index of the file is walked only as far as the
+    request reaches and only the units it touches are read (what lies behind the last of them may be missing), only the
+    reference closure of the request is decoded, and the frames asked for are written in ascending order (pictures
     under their absolute index), counted by `Number of frames` and compared with their rows of the manifest.  One line more
     is printed: `[INFO] partial decode: <K> frames written, <D> of <C> coded frames decoded`.  A request outside the stream
-    is an aivc_amd.partial.FrameSelectionError."""
+    is an aivc_amd.partial.FrameSelectionError.  Without either it is the same decode with the request for everything."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
                'verify': '', 'contract': '', 'frames': None, 'max_level': None}
     decoder = get_value('decoder', param, default).eval()
@@ -156,15 +154,8 @@ def decode_one_video(param):
     out_file = get_value('out_file', param, default)
     verify = get_value('verify', param, default)
     contract = get_value('contract', param, default)
-    span, max_level = get_value('frames', param, default), get_value('max_level', param, default)
     print_log_msg('INFO', 'Bitstream path', '', path)
-    part = None
-    if span is not None or max_level is not None:
-        part = read_partial(path, span, max_level)
-        blob = None
-    else:
-        with open(path, 'rb') as f:
-            blob = f.read()
+    plan = read_plan(path, get_value('frames', param, default), get_value('max_level', param, default))
     from .. import digests, ops, parallel
     _VERIFY_BAD[0] = 0
     manifest = None
@@ -176,62 +167,43 @@ def decode_one_video(param):
         if contract == 'auto':
             fc0 = FrameCodec(decoder.full_net)
             choice, _, note = digests.choose_contract(None if manifest is None else manifest.contract, prev_precision,
-                                                      lambda name: probe_unit0(fc0, unit0_blob(path) if blob is None else blob, dev, name),
-                                                      parallel.rank_world()[1])
+                                                      lambda name: probe_unit0(fc0, path, plan, dev, name), parallel.rank_world()[1])
             if note and parallel.rank_world()[0] == 0:
                 print(note)
             ops.set_precision(choice)
         elif contract:
             ops.set_precision(contract)
-        return _decode_one_video(decoder, path, blob, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default), part)
+        return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default))
     finally:
         ops.set_precision(prev_precision)
 
 
-def read_partial(path, span, max_level):
-    """the file of a partial decode -> (aivc_amd.partial.IndexedVideo with the records of the units the request touches, the
-    absolute indices asked for or None, max_level, the selection per unit): the index is walked as far as the request
-    reaches, and of the payload only those units are read"""
+def read_plan(path, span, max_level):
+    """the file of a decode -> its aivc_amd.partial.Plan, the video holding the records of the units that are decoded: the
+    index is walked as far as the request reaches (span: (a, b) or None; all of it for a whole decode), and of the payload
+    only those units are read"""
     from .. import partial
     from . import cat_binary_files as container
     with open(path, 'rb') as f:
         data_dim, first, last, units = container.index_video(f, upto_frame=None if span is None else span[1])
-        names = [u[2] for u in units]
-        idxs = None if span is None else list(partial.frame_range(span, first, last))
-        wanted = partial.select(names, first, last, idxs, max_level)
-        gops = container.read_units(f, units, [u for u, w in enumerate(wanted) if w])
-    return partial.IndexedVideo(data_dim, first, last, names, gops), idxs, max_level, wanted
+        video = partial.IndexedVideo(data_dim, first, last, [u[2] for u in units], [None] * len(units))
+        plan = partial.plan(video, None if span is None else partial.frame_range(span, first, last), max_level)
+        gops = container.read_units(f, units, [u for u, need in enumerate(plan.need) if need])
+    return plan._replace(video=video._replace(gops=gops))
 
 
-def unit0_blob(path):
-    """the first intra-period unit of a file as a container of its own (what probe_unit0 decodes), read through the index"""
-    from . import cat_binary_files as container
-    from . import header as hdr
-    with open(path, 'rb') as f:
-        data_dim, first, last, units = container.index_video(f, upto=0)
-        return container.pack_video(hdr.video_header_bytes(data_dim, 1, first, last), container.read_units(f, units, [0]))
-
-
-def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstream_debug, part=None):
+def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
-    from .. import parallel
-    from . import cat_binary_files as container
+    from .. import parallel, partial
     rank, world = parallel.rank_world()
     fc = FrameCodec(decoder.full_net)
+    video, first = plan.video, plan.video.first
     with torch.no_grad():
-        if part is not None:  # (the same calls, on the units that were read and for the frames asked for)
-            video, idxs, max_level, wanted = part
-            first, last = video.first, video.last
-            if world > 1:
-                frames = parallel.decode_video_sharded(fc, video, dev, frames=idxs, max_level=max_level)
-            else:
-                frames = fc.decode_indexed(video, dev, None, idxs, max_level)[0]
-        elif world > 1:  # one process per GPU: every rank decodes its intra-period units, rank 0 collects the planes
-            _, first, last, _ = container.unpack_video(blob)
-            frames = parallel.decode_video_sharded(fc, blob, dev)
+        if world > 1:  # one process per GPU: every rank decodes its intra-period units, rank 0 collects the planes
+            frames = parallel.decode_video_sharded(fc, video, dev, plan=plan)
         else:
-            frames, data_dim, first, last = fc.decode_video(blob, dev)
+            frames = fc.decode_video(video, dev, plan=plan)[0]
     torch.cuda.synchronize()
     dt = time.time() - t0
     errs = report_stream_errors(fc, path)  # (every rank reports the sections IT decoded)
@@ -244,44 +216,34 @@ def _decode_one_video(decoder, path, blob, dev, out_file, manifest, flag_bitstre
     if rank != 0:
         dist_barrier_after_write(world)
         return None
-    shown = None  # a partial decode: the absolute indices of the frames asked for, ascending; `frames` becomes those frames
-    if part is not None:
-        from .. import partial
-        shown = partial.selected_indices(video.names, first, wanted)
-        frames = [frames[i - first] for i in shown]
-    n = last - first + 1 if shown is None else len(shown)
+    shown = plan.indices  # the absolute indices of the frames asked for, ascending; `frames` becomes those frames
+    frames = [frames[i - first] for i in shown]
+    n = len(shown)
     print_log_msg('INFO', 'Decoding done', '', '')
-    if part is not None:
+    if not plan.whole:
         print('[INFO] partial decode: %d frames written, %d of %d coded frames decoded'
-              % (n, sum(len(c) for c in partial.closures(video.names, wanted)), partial.coded_frames(video.names, first, last)))
+              % (n, sum(len(c) for c in plan.need), partial.coded_frames(video.names, first, video.last)))
     print_log_msg('RESULT', 'Number of frames', '[frame]', int(n))
     print_log_msg('RESULT', 'Decoding time', '[s]', '%.1f' % dt)
     print_log_msg('RESULT', 'Decoding FPS', '[frame/s]', '%.1f' % (n / dt))
     found = None
     if manifest is not None:  # (queued now, read after the frames have been written)
-        found = digest_frames(frames, dev) if frames else None
+        found = digest_frames(frames, dev)
     if is_png_folder(out_file):
-        write_png_folder(frames, first, out_file, dev, indices=shown)
+        write_png_folder(frames, out_file, dev, shown)
     elif out_file:
         write_yuv(frames, out_file)
     dist_barrier_after_write(world)
-    if manifest is not None:
+    if manifest is not None:  # the frames returned against their rows of the manifest; a whole decode against all of it
         from .. import digests
-        rows = {} if found is None else digests.hex_rows(first, [d.cpu().numpy() for d in found])
-        expected = manifest.rows
-        if shown is not None:  # exactly the frames returned against their rows of the manifest
-            rows = {shown[k - first]: row for k, row in rows.items()}
-            expected = digests.manifest_subset(manifest.rows, shown)
-        differing = digests.compare(expected, rows)
+        rows = dict(zip(shown, digests.hex_rows(0, [d.cpu().numpy() for d in found]).values()))
+        differing = digests.compare(manifest.rows if plan.whole else digests.manifest_subset(manifest.rows, shown), rows)
         _VERIFY_BAD[0] = len(differing)
         for line in digests.verify_lines(len(rows), differing):
             print(line)
     if flag_bitstream_debug:
-        if shown is None:
-            check_debug_md5(frames, first, debug_dir(path))
-        else:
-            for idx, fr in zip(shown, frames):
-                check_debug_md5([fr], idx, debug_dir(path))
+        for idx, fr in zip(shown, frames):
+            check_debug_md5([fr], idx, debug_dir(path))
     return frames
 
 

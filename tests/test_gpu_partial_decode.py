@@ -1,7 +1,8 @@
 """Partial decode on the device against the CPU oracle's WHOLE decode, bit for bit: frame ranges and temporal levels through
 FrameCodec.decode_video, under the decoder knobs that move chunk boundaries, launch one frame at a time and run the entropy
 stage level by level; the work actually saved (how many frames reach the entropy stage and the synthesis, which units are
-parsed); a padded last unit; the command line (--frames, --verify, pictures, exit statuses, a truncated file) and two ranks.
+parsed); a padded last unit, and its whole decode as the request for everything (the launches of decode_units, one selection
+per command line); the command line (--frames, --verify, pictures, exit statuses, a truncated file) and two ranks.
 
 The reference is oracle.codec.decode_video on oracle.spec.export_model(model) (tests/schedule_cases.py: reference), computed
 once per module.  No tolerances: planes with array_equal against the oracle's frames of the same indices, None in every slot
@@ -172,6 +173,37 @@ def test_padded_unit(model, refs, cuda, monkeypatch):
         fc.decode_video(ref['blob'], cuda, frames=[12])
 
 
+def test_whole_decode_of_a_padded_clip(model, refs, cuda, monkeypatch):
+    """a whole decode is the request for everything, and it still decodes the six repeats behind frame 11: the launches of
+    decode_units on the same records, from the bytes and from an IndexedVideo alike"""
+    from collections import Counter
+    from aivc_amd import partial
+    ref = refs['padded']
+    spies = pc.WorkSpies(monkeypatch)
+    fc = _codec(model)
+    with torch.no_grad():
+        got, data_dim, first, last = fc.decode_video(ref['blob'], cuda)
+    assert (first, last) == (0, 11) and len(got) == 12 and data_dim['x'] == ref['data_dim']['x']
+    sc.assert_frames(got, ref['dec'])
+    assert fc.stream_errors() == []
+    assert spies.frames('e') == 18 and spies.frames('s') == 18, spies.calls
+    # the whole entropy stage up front, one launch per frame type (entropy_chunk 64), then the five levels of 1_GOP_8 with both
+    # units in every batch (max_batch 16)
+    assert spies.calls == [('e', 0, 2), ('e', 1, 2), ('e', 2, 14), ('s', 0, 2), ('s', 1, 2), ('s', 2, 2), ('s', 2, 4), ('s', 2, 8)]
+    record = (list(spies.calls), Counter(spies.parsed))
+    spies.clear()
+    with torch.no_grad():
+        units = fc.decode_units(ref['gops'], ref['data_dim'], cuda)  # (the layer below)
+    assert (spies.calls, Counter(spies.parsed)) == record
+    sc.assert_frames((units[0] + units[1])[:12], ref['dec'])
+    spies.clear()
+    with torch.no_grad():
+        same = fc.decode_video(partial.indexed_from_blob(ref['blob']), cuda)[0]
+    assert (spies.calls, Counter(spies.parsed)) == record
+    sc.assert_frames(same, ref['dec'])
+    assert fc.stream_errors() == []
+
+
 # ---- the command line ----------------------------------------------------------------------------------------------------------
 @pytest.fixture
 def clis(model, monkeypatch):
@@ -230,6 +262,40 @@ def test_cli_frames(coded, refs, clis, capsys):
     (tmp / 'short.md5').write_text('\n'.join(l for l in lines if not l.startswith('9 ')))
     assert dec_cli.main(['-i', bits, '-o', str(tmp / 's.yuv'), '--frames', '7:11', '--verify', str(tmp / 'short.md5')]) == 4
     assert '[VERIFY] 5 frames, 3 planes differ' in capsys.readouterr().out
+
+
+def test_cli_whole_decode_goes_through_the_index(refs, clis, tmp_path, capsys, monkeypatch):
+    """the command line without a request: the same reader and the same driver, every coded frame decoded, one selection"""
+    from aivc_amd import partial
+    _, dec_cli = clis
+    ref = refs['padded']
+    _, w, h, _, _ = pc.PADDED
+    bits, out = str(tmp_path / 'padded.bin'), str(tmp_path / 'whole.yuv')
+    (tmp_path / 'padded.bin').write_bytes(ref['blob'])
+    selections, select = [], partial.select
+
+    def counting_select(*a, **kw):
+        selections.append(a[3:])
+        return select(*a, **kw)
+    monkeypatch.setattr(partial, 'select', counting_select)
+    spies = pc.WorkSpies(monkeypatch)
+    capsys.readouterr()
+    assert dec_cli.main(['-i', bits, '-o', out]) == 0
+    text = capsys.readouterr().out
+    number = [line for line in text.split('\n') if 'Number of frames' in line]
+    assert len(number) == 1 and number[0].split()[-1] == '12' and '[INFO] partial decode' not in text, text
+    got = pc.read_planes(out, w, h)
+    assert len(got) == 12 and all(np.array_equal(g[k], r[k]) for g, r in zip(got, ref['dec']) for k in 'yuv')
+    assert spies.frames('e') == 18 and spies.frames('s') == 18, spies.calls
+    assert len(selections) == 1, selections
+    del selections[:]
+    spies.clear()
+    assert dec_cli.main(['-i', bits, '-o', out, '--frames', '9:10']) == 0
+    assert '[INFO] partial decode: 2 frames written, 5 of 18 coded frames decoded' in capsys.readouterr().out
+    assert len(selections) == 1, selections
+    got = pc.read_planes(out, w, h)
+    assert len(got) == 2 and all(np.array_equal(g[k], r[k]) for g, r in zip(got, ref['dec'][9:11]) for k in 'yuv')
+    assert spies.frames('s') == 5, spies.calls  # frames 0, 8, 4, 2, 1 of unit 1
 
 
 def test_cli_pictures_keep_their_absolute_index(coded, clis):

@@ -221,6 +221,32 @@ def test_contract_from_a_trial_decode(model, cuda, clis, tmp_path, capsys):
     assert ops.precision_name() == default
 
 
+def test_trial_decode_for_a_request_that_does_not_touch_unit_0(model, cuda, clis, tmp_path, capsys):
+    """two units (two I frames of the stream above) without a manifest: a request inside unit 1 still probes unit 0, read
+    through the index, and prints the note of the whole decode"""
+    from aivc_amd import ops
+    enc_cli, dec_cli = clis
+    default = ops.precision_name()
+    other = 'fp32' if default == 'fp32w' else 'fp32w'
+    w, h = 1440, 1424
+    frames, raw = write_clip(tmp_path, w, h, 2, seed=32)
+    bits = str(tmp_path / 'two.bin')
+    enc_cli.main(['-i', raw, '--gop', '1_GOP_0', '-o', bits, '--contract', other])
+    assert not os.path.exists(bits + '.md5')
+    _, recs = library_encode(model, frames, '1_GOP_0', cuda, other)
+    note = '[INFO] arithmetic contract: %s (detected on unit 0)' % other
+    capsys.readouterr()
+    assert dec_cli.main(['-i', bits, '-o', str(tmp_path / 'whole.yuv'), '--contract', 'auto']) == 0
+    out = capsys.readouterr().out
+    assert note in out and '[WARN]' not in out and '[INFO] partial decode' not in out
+    assert dec_cli.main(['-i', bits, '-o', str(tmp_path / 'part.yuv'), '--contract', 'auto', '--frames', '1']) == 0
+    out = capsys.readouterr().out
+    assert note in out and '[WARN]' not in out and '[INFO] partial decode: 1 frames written, 1 of 2 coded frames decoded' in out
+    assert planes_differ(read_planes(tmp_path / 'whole.yuv', w, h, 2), [{k: r[k].cpu().numpy() for k in 'yuv'} for r in recs]) == 0
+    assert planes_differ(read_planes(tmp_path / 'part.yuv', w, h, 1), [{k: recs[1][k].cpu().numpy() for k in 'yuv'}]) == 0
+    assert ops.precision_name() == default
+
+
 def test_two_ranks_write_the_manifest_of_one_process(model, cuda, tmp_path):
     """aivc.py --digests under `torch.distributed.run` with two ranks on the one GPU over gloo (as
     tests/test_gpu_multi_process.py::test_cli_two_ranks_equals_one_process): every rank digests the units it coded, the 48-byte

@@ -444,15 +444,15 @@ def test_distributed_watchdog_names_the_wait(capfd, monkeypatch):
 
 def test_unit_lengths_of_a_container_with_mixed_coding_structures():
     """decode_video_sharded places the gathered frames by every unit's OWN length (a container may mix GOP structures:
-    decode_video / decode_units accept that) -- parallel.unit_lengths reads them from the GOP records"""
-    from aivc_amd import parallel
+    decode_video / decode_units accept that) -- partial.unit_lengths has them from the names in the GOP headers"""
+    from aivc_amd import partial
     from aivc_amd.real_life import cat_binary_files as container
     from aivc_amd.real_life import header as hdr
     frame = (0).to_bytes(4, 'big') * 2 + (1).to_bytes(4, 'big') + b'z' + (1).to_bytes(4, 'big') + b'\x00'
     gops = [container.pack_gop(hdr.gop_header_bytes(name, 0.), [frame] * n) for name, n in (('1_GOP_2', 3), ('1_GOP_4', 5), ('LDP_2', 3))]
     dd = {'x': (48, 80), 'y': (3, 5), 'z': (1, 2)}
     blob = container.pack_video(hdr.video_header_bytes(dd, len(gops), 0, 10), gops)
-    assert parallel.unit_lengths(blob) == [3, 5, 3]
+    assert partial.unit_lengths(partial.indexed_from_blob(blob).names) == [3, 5, 3]
 
 
 def test_truncated_container_is_an_error_not_garbage():

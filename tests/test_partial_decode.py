@@ -1,5 +1,5 @@
 """Partial decode, the host side (no GPU): the reference closure and the depths of the coding structures, absolute index ->
-(unit, frame) on containers of dummy payloads, the container index (what it reads, where it stops, what it refuses), the
+(unit, frame) on containers of dummy payloads, the plan of a request and of a whole decode, the container index (what it reads, where it stops, what it refuses), the
 --frames / --max_level flags and the manifest rows a partial --verify compares.  The decodes themselves are in
 tests/test_gpu_partial_decode.py."""
 import io
@@ -86,6 +86,47 @@ def test_mapping_padded_last_unit():
     assert everything[1] == {pc.name(0), pc.name(1), pc.name(2)}
 
 
+# ---- the plan: what every layer of a decode is handed ------------------------------------------------------------------
+def test_plan_of_a_whole_decode_keeps_the_padded_repeats():
+    from aivc_amd import partial
+    blob, gops = pc.dummy_video(['1_GOP_8', '1_GOP_8'], 0, 12)
+    p = partial.plan(partial.indexed_from_blob(blob))
+    every = {pc.name(i) for i in range(9)}
+    assert p.whole is True and p.need == [every, every] and p.indices == list(range(12))
+    assert p.wanted == [every, {pc.name(0), pc.name(1), pc.name(2)}]
+    assert p.video.gops == gops and partial.plan(blob) == p  # (bytes are indexed on the way)
+
+
+def test_plan_of_one_frame_behind_the_padding():
+    from aivc_amd import partial
+    blob, _ = pc.dummy_video(['1_GOP_8', '1_GOP_8'], 0, 12)
+    p = partial.plan(partial.indexed_from_blob(blob), [10])
+    assert p.whole is False and p.indices == [10]
+    assert p.wanted == [set(), {pc.name(1)}] and p.need == [set(), {pc.name(i) for i in (0, 1, 2, 4, 8)}]
+    assert partial.plan(blob, None, 99).whole is False  # (a level is a request, however deep)
+
+
+def test_plan_with_mixed_structures_and_offset_numbering():
+    """the video of test_mapping_mixed_structures_and_offset_numbering: the plan holds what the single functions return"""
+    from aivc_amd import partial
+    v = partial.indexed_from_blob(pc.dummy_video(['LDP_2', '1_GOP_8', 'LDP_2'], 100, 15)[0])
+    for frames, max_level in (([102, 108, 114], None), (None, 2), ([101, 104, 107], 2), (None, None)):
+        p = partial.plan(v, frames, max_level)
+        wanted = partial.select(v.names, v.first, v.last, frames, max_level)
+        assert p.video is v and p.wanted == wanted and p.indices == partial.selected_indices(v.names, v.first, wanted)
+        if frames is None and max_level is None:
+            assert p.need == [{pc.name(i) for i in range(n)} for n in (3, 9, 3)] and p.indices == list(range(100, 115))
+        else:
+            assert p.need == partial.closures(v.names, wanted)
+    p = partial.plan(v, [102, 108, 114])
+    assert p.indices == [102, 108, 114] and p.need == [{pc.name(i) for i in (0, 1, 2)}, {pc.name(i) for i in (0, 8, 4, 6, 5)},
+                                                       {pc.name(i) for i in (0, 1, 2)}]
+    with pytest.raises(partial.FrameSelectionError, match='100 ... 114'):
+        partial.plan(v, [99])
+    with pytest.raises(ValueError, match='unit 1: coding structure 1_GOP_8 has no frame_9'):
+        partial.closures(v.names, [set(), {pc.name(9)}, None])
+
+
 @pytest.mark.parametrize('frames,max_level', [([], None), ([18], None), ([-1], None), ([3], -1), (None, -2), ([1, 3, 5], 1)])
 def test_requests_outside_the_stream_name_its_range(frames, max_level):
     from aivc_amd import partial
@@ -157,6 +198,23 @@ def test_index_of_a_truncated_file():
     for short in (blob[:10], blob[:20], blob[:25]):  # inside the video header, the first prefix, the first GOP header
         with pytest.raises(container.ContainerError):
             container.index_video(io.BytesIO(short), upto=0)
+
+
+def test_the_driver_reads_a_file_once_as_far_as_the_request_reaches(tmp_path):
+    from aivc_amd.real_life import cat_binary_files as container
+    from aivc_amd.real_life.decode import read_plan
+    blob, gops = pc.dummy_video(['1_GOP_8'] * 3, 0, 27)
+    (tmp_path / 'v.bin').write_bytes(blob)
+    p = read_plan(str(tmp_path / 'v.bin'), None, None)
+    assert p.whole and p.video.gops == gops and p.indices == list(range(27))
+    p = read_plan(str(tmp_path / 'v.bin'), (10, 12), None)  # the index stops behind unit 1, and unit 0 is not read
+    assert not p.whole and p.video.names == ['1_GOP_8'] * 2 and p.video.gops == [None, gops[1]] and p.indices == [10, 11, 12]
+    units = container.index_video(io.BytesIO(blob))[3]
+    (tmp_path / 'cut.bin').write_bytes(blob[:units[2][0] + units[2][1] // 2])  # cut inside unit 2
+    assert read_plan(str(tmp_path / 'cut.bin'), (None, 17), None).video.gops == gops[:2]
+    for span, max_level in ((None, None), ((None, 18), None), (None, 1)):
+        with pytest.raises(container.ContainerError):
+            read_plan(str(tmp_path / 'cut.bin'), span, max_level)
 
 
 # ---- the scheduler's argument checks (they come before any device work) -------------------------------------------------

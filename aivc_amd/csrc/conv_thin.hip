@@ -127,7 +127,7 @@ __global__ __launch_bounds__(TH * 16) void thin_tconv_kernel(aivc_conv_params p)
 // ky = pyc + TPAD - 2 dy, kx = pxc + TPAD - 2 dx when that is a kernel tap of the class, else 0.
 // Walking the neighbourhood with dy, dx DESCENDING makes ky, kx ascend for every class at once, so each
 // output sees exactly the contract's fmaf chain (taps of its class in (ky, kx) order, channels in groups of 8
-// in AIVC_K_ORDER) with exact no-ops (fmaf(x, 0, acc)) in between.  v_mfma_f32_16x16x4_f32 accumulates its 4
+// in AIVC_K_ORDER) with exact no-ops (fmaf(x, 0, acc)) in between -- for finite x; see thin_exact_acc.  v_mfma_f32_16x16x4_f32 accumulates its 4
 // k-slots in order (tools/mfma_probe.hip checks it against an fmaf chain), lane group g = lane / 16 supplies
 // slot g, so inside every group of 16 channels LDS position 4 g + e holds channel thin_chan(g, e): one
 // ds_read_b128 feeds 4 consecutive MFMA steps.
@@ -163,6 +163,30 @@ __device__ __host__ constexpr int thin_chan(int g, int e) { return 8 * (e >> 1) 
 struct ThinOrigin {
   int n, ry, rx;  // image, tile row, tile column
 };
+
+// The accumulator of ONE output of the transposed layer by the contract's chain itself (the taps of the pixel's parity class in
+// (ky, kx) order, an out-of-image tap a zero input in its place, channels in groups of 8 in AIVC_K_ORDER; c_in % 16 == 0: no
+// padded group).  The matrix-core kernel below multiplies the taps a class LACKS by a zero weight: an exact no-op for every
+// finite input, but inf * 0 = NaN -- so an accumulator that comes out NaN is computed again here, from the taps the contract
+// gives it (a NaN the chain itself produces comes out NaN again).  Cold: the codec never feeds this layer a non-finite value.
+__device__ __noinline__ float thin_exact_acc(const float *x, const float *w, int n, int H, int W, int Cin, int ks, int oy, int ox, int o) {
+  const int tpad = (ks + 1) / 2 - 1;
+  const float *xn = x + (size_t)n * H * W * Cin;
+  float acc = 0.0f;
+  for (int ky = (oy + tpad) & 1; ky < ks; ky += 2)
+    for (int kx = (ox + tpad) & 1; kx < ks; kx += 2) {
+      const int ty = oy + tpad - ky, tx = ox + tpad - kx, iy = ty >> 1, ix = tx >> 1;
+      const bool ok = ty >= 0 && tx >= 0 && iy < H && ix < W;
+      const float *xp = xn + ((size_t)(ok ? iy : 0) * W + (ok ? ix : 0)) * Cin;
+      const float *wp = w + (size_t)((o * ks + ky) * ks + kx) * Cin;
+      for (int g0 = 0; g0 < Cin; g0 += 8)
+        for (int i = 0; i < 8; ++i) {
+          const int ci = g0 + AIVC_K_ORDER(i);
+          acc = __builtin_fmaf(ok ? xp[ci] : 0.0f, wp[ci], acc);
+        }
+    }
+  return acc;
+}
 
 // LEAN: the layer as the codec launches it -- bias, one activation, no gate / residual, no second activation -- without the
 // run-time flags of the general epilogue (the compiler turns them into a thicket of uniform branches around every store)
@@ -315,6 +339,8 @@ __global__ __launch_bounds__(512) void thin_mfma_kernel(aivc_conv_params p, int 
           if (colok && (full || qx0 + mg * 16 + r < W)) {
             const int off = lane_out + (2 * (mg * 16 + r)) * CO;
             float v = eacc[mg][r];
+            if (__builtin_expect(v != v, 0))  // a zero-weight term met a non-finite input: the contract's own chain (thin_exact_acc)
+              v = thin_exact_acc(p.x, p.w, t.n, H, W, Cin, KS, 2 * qy + pyc, 2 * (qx0 + mg * 16 + r) + pxc, o);
             if constexpr (LEAN) {
               v = act(v + bias_o, slope1, keep1);
             } else {

@@ -27,7 +27,15 @@
  *   (the last group zero padded), inside a group in the order 0, 4, 1, 5, 2, 6, 3, 7
  *   (AIVC_K_ORDER): the order in which v_mfma_f32_32x32x2_f32 consumes an operand row held in
  *   natural K order, so the MFMA kernels need no operand shuffling; the scalar HIP kernels and
- *   the CPU oracle walk the same order and all agree bitwise.  A zero term is an exact no-op.
+ *   the CPU oracle walk the same order and all agree bitwise.  A zero term (a zero input or a zero
+ *   weight: the padding of the last group, an out-of-image tap, the zero pad channel of an image)
+ *   leaves every accumulator unchanged EXCEPT an accumulator of -0, which a term of +0 turns into
+ *   +0 (fmaf(0, w, -0.0f) is +0 for w > 0).  An accumulator is -0 only after products have
+ *   underflowed to zero, and the result of such a chain is itself a zero.  The terms named above
+ *   ARE part of the chain (the oracle adds them); a kernel may skip one, or add further terms
+ *   whose weight is zero, so: where the contract's result of a launch is a zero, the launches
+ *   listed in tests/numeric_regimes.py (ZERO_SIGN_OPEN) return a zero whose SIGN is open.  Every
+ *   other result, every non-zero value, infinity and NaN, is the chain's, bit for bit.
  *   Then v = acc + bias, then the epilogue in the order documented at aivc_conv2d.
  *   Transcendentals (exp for sigma / sigmoid, expm1 for the Laplace CDF, the factorised
  *   prior's softplus/tanh/sigmoid) are evaluated by a fixed fp64 polynomial scheme

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from aivc_amd import abi
+from numeric_regimes import assert_bits, row_facts
 from op_cases import Case, on, profiled
 
 CONV_CASES = [
@@ -134,15 +135,33 @@ GDN_RESIDENT_CASES = [
 ATTENTION_GATE_CASES = [(2, 16, 32, 128, 1.0), (1, 9, 11, 128, 1.0), (2, 8, 8, 64, 1.0), (1, 9, 11, 128, 40.0)]  # n, h, w, c, weight scale
 
 
-def attention_gate_case(oracle, n, h, w, c, scale):
+def _dressed(dress, rng, inputs, row):
+    """the drawn inputs, or what the regime `dress` (tests/numeric_regimes.py) makes of them"""
+    return inputs if dress is None else dress(rng, inputs, row)
+
+
+def _reached(dress, row, inputs, want, chain):
+    """{} or, having asserted that the oracle's result proves the regime reached, the facts a dressed case carries"""
+    if dress is None:
+        return {}
+    with np.errstate(all='ignore'):
+        dress.reach(row, inputs, want, chain)
+    return {'regime': dress, 'row': row}
+
+
+def attention_gate_case(oracle, n, h, w, c, scale, dress=None):
     rng = np.random.default_rng(n * 100 + h)
     a = rng.standard_normal((n, h, w, c), dtype=np.float32)
     wt = (rng.standard_normal((c, 1, 1, c), dtype=np.float32) / np.sqrt(c)).astype(np.float32) * np.float32(scale)
     b = rng.standard_normal(c, dtype=np.float32)
     trunk = rng.standard_normal((n, h, w, c), dtype=np.float32)
     x = rng.standard_normal((n, h, w, c), dtype=np.float32)
-    return Case({'x': a, 'w': wt, 'bias': b, 'mul': trunk, 'res': x}, _conv_call(('mul', 'res'), act1=abi.ACT_SIGMOID),
-                oracle.conv2d(a, wt, b, act1=abi.ACT_SIGMOID, mul=trunk, res=x), pre_activation=oracle.conv2d(a, wt, b))
+    row = row_facts(act1=abi.ACT_SIGMOID)
+    i = _dressed(dress, rng, {'x': a, 'w': wt, 'bias': b, 'mul': trunk, 'res': x}, row)
+    pre = oracle.conv2d(i['x'], i['w'], i['bias'])
+    want = oracle.conv2d(i['x'], i['w'], i['bias'], act1=abi.ACT_SIGMOID, mul=i['mul'], res=i['res'])
+    return Case(i, _conv_call(('mul', 'res'), act1=abi.ACT_SIGMOID), want, pre_activation=pre,
+                **_reached(dress, row, i, want, lambda: pre))
 
 
 WINO_CASES = [  # n, h, w, c_in, c_out, act1, act2, bias, mul, res
@@ -203,7 +222,7 @@ def _conv_call(names, **fixed):
     return call
 
 
-def conv_case(oracle, row, seed, n=2):
+def conv_case(oracle, row, seed, n=2, dress=None):
     """a row of CONV_CASES: bias, two activations, gate multiplicand, residual; the GDN modes with positive gamma and beta"""
     mode, k, s, pad, ci, co, h, w, a1, a2, use_mul, use_res = row[:12]
     rng = np.random.default_rng(seed)
@@ -221,15 +240,22 @@ def conv_case(oracle, row, seed, n=2):
     res = rng.standard_normal((n, ho, wo, co), dtype=np.float32) if use_res else None
     fixed = dict(mode=mode, stride=s, pad=pad, act1=a1, act2=a2)
     facts = {}
-    if len(row) > 12:  # the range the row exists for, whatever the seed
+    rf = row_facts(mode, k, s, pad, a1, a2)
+    i = _dressed(dress, rng, {'x': x, 'w': wt, 'bias': bias, 'mul': mul, 'res': res}, rf)
+    x, wt, bias, mul, res = (i[nm] for nm in ('x', 'w', 'bias', 'mul', 'res'))
+    if len(row) > 12 and dress is None:  # the range the row exists for, whatever the seed
         pre = facts['pre_activation'] = oracle.conv2d(x, wt, bias, mode=mode, stride=s, pad=pad)
         for lo, hi in ((-np.inf, -103.98), (-103.97, -88.73), (-88.72, -87.34), (87.34, 88.72), (88.73, 103.97), (103.98, np.inf)):
             assert ((pre > lo) & (pre < hi)).any(), (lo, hi, float(pre.min()), float(pre.max()))
-    return Case({'x': x, 'w': wt, 'bias': bias, 'mul': mul, 'res': res}, _conv_call(('mul', 'res'), **fixed),
-                oracle.conv2d(x, wt, bias, mul=mul, res=res, **fixed), **facts)
+    with np.errstate(all='ignore'):
+        want = oracle.conv2d(x, wt, bias, mul=mul, res=res, **fixed)
+
+    def chain(inverse=False):  # (inverse: the GDN mode's normaliser through its inverse form)
+        return oracle.conv2d(x, wt, bias, mode=abi.MODE_IGDN if inverse else mode, stride=s, pad=pad)
+    return Case(i, _conv_call(('mul', 'res'), **fixed), want, **facts, **_reached(dress, rf, i, want, chain))
 
 
-def thin_walk_case(oracle, row, seed, with_bias=True):
+def thin_walk_case(oracle, row, seed, with_bias=True, dress=None):
     """a row of THIN_WALK_CASES over 3 images: the transposed thin output layer, leaky, with or without its bias (drawn either way)"""
     co, k, ci, h, w = row
     rng = np.random.default_rng(seed)
@@ -239,14 +265,19 @@ def thin_walk_case(oracle, row, seed, with_bias=True):
     if not with_bias:
         bias = None
     fixed = dict(mode=abi.MODE_TCONV, stride=2, pad=0, act1=abi.ACT_LEAKY)
-    return Case({'x': x, 'w': wt, 'bias': bias}, _conv_call((), **fixed), oracle.conv2d(x, wt, bias, **fixed))
+    rf = row_facts(abi.MODE_TCONV, k, 2, 0, abi.ACT_LEAKY)
+    i = _dressed(dress, rng, {'x': x, 'w': wt, 'bias': bias}, rf)
+    with np.errstate(all='ignore'):
+        want = oracle.conv2d(i['x'], i['w'], i['bias'], **fixed)
+    return Case(i, _conv_call((), **fixed), want,
+                **_reached(dress, rf, i, want, lambda: oracle.conv2d(i['x'], i['w'], i['bias'], mode=abi.MODE_TCONV, stride=2)))
 
 
 def _gdn_params(rng, co, floor=0.2, scale=0.05):
     return (np.abs(rng.standard_normal(co)) + floor).astype(np.float32), (np.abs(rng.standard_normal((co, co))) * scale).astype(np.float32)
 
 
-def fused_gdn_case(oracle, row, seed):
+def fused_gdn_case(oracle, row, seed, dress=None):
     """a row of FUSED_GDN_CASES: conv + (I)GDN (+ residual) in one request; want: the oracle's fused evaluation"""
     mode, k, s, pad, ci, co, h, w, inv, use_res = row
     rng = np.random.default_rng(seed)
@@ -257,12 +288,15 @@ def fused_gdn_case(oracle, row, seed):
     ho, wo = abi.conv_out_size(mode, h, w, k, s, pad)
     res = rng.standard_normal((2, ho, wo, co), dtype=np.float32) if use_res else None
     fixed = dict(mode=mode, stride=s, pad=pad)
-    return Case({'x': x, 'w': wt, 'bias': bias, 'beta': beta, 'gamma': gamma, 'res': res},
-                lambda ops, d, **kw: ops.conv2d(d['x'], d['w'], d['bias'], res=d['res'], gdn=(d['beta'], d['gamma'], inv), **fixed, **kw),
-                oracle.conv2d(x, wt, bias, res=res, gdn=(beta, gamma, inv), **fixed))
+    rf = row_facts(mode, k, s, pad, fused_gdn=inv)
+    i = _dressed(dress, rng, {'x': x, 'w': wt, 'bias': bias, 'beta': beta, 'gamma': gamma, 'res': res}, rf)
+    with np.errstate(all='ignore'):
+        want = oracle.conv2d(i['x'], i['w'], i['bias'], res=i['res'], gdn=(beta, gamma, inv), **fixed)
+    return Case(i, lambda ops, d, **kw: ops.conv2d(d['x'], d['w'], d['bias'], res=d['res'], gdn=(d['beta'], d['gamma'], inv), **fixed, **kw),
+                want, **_reached(dress, rf, i, want, lambda: oracle.conv2d(i['x'], i['w'], i['bias'], gdn=(beta, gamma, inv), **fixed)))
 
 
-def fused_tail_case(oracle, row, seed):
+def fused_tail_case(oracle, row, seed, dress=None):
     """a row of FUSED_TAIL_CASES: conv + activation + 1x1 conv (+ residual, activation) in one request; want: the oracle's two
     convolutions, the intermediate zero padded to a multiple of 4 channels as the tail's weights are.  covered: version 2 of the
     contract runs the 3x3 on the Winograd chain (size rule in force) and the library declines the fusion."""
@@ -277,29 +311,36 @@ def fused_tail_case(oracle, row, seed):
     b3 = rng.standard_normal(ct, dtype=np.float32)
     ho, wo = abi.conv_out_size(abi.MODE_CONV, h, w, k, s, k // 2)
     res = rng.standard_normal((n, ho, wo, ct), dtype=np.float32) if use_res else None
-    t = oracle.conv2d(x, wt, b1, stride=s, pad=k // 2, act1=a1)
+    rf = row_facts(abi.MODE_CONV, k, s, k // 2, a1, a2, tail=True)
+    i = _dressed(dress, rng, {'x': x, 'w': wt, 'bias': b1, 'w3': w3, 'b3': b3, 'res': res}, rf)
+    with np.errstate(all='ignore'):
+        t = oracle.conv2d(i['x'], i['w'], i['bias'], stride=s, pad=k // 2, act1=a1)
     if cm4 != cm:
         t = np.concatenate([t, np.zeros(t.shape[:3] + (cm4 - cm,), np.float32)], axis=-1)
     fixed = dict(stride=s, pad=k // 2, act1=a1, act2=a2)
-    return Case({'x': x, 'w': wt, 'bias': b1, 'w3': w3, 'b3': b3, 'res': res},
-                lambda ops, d, **kw: ops.conv2d(d['x'], d['w'], d['bias'], res=d['res'], tail=(d['w3'], d['b3']), **fixed, **kw),
-                oracle.conv2d(t, w3, b3, res=res, act2=a2), fixed=fixed,
-                covered=k == 3 and s == 1 and ci % 32 == 0 and cm % 128 == 0 and h * w >= 8000)
+    with np.errstate(all='ignore'):
+        want = oracle.conv2d(t, i['w3'], i['b3'], res=i['res'], act2=a2)
+    return Case(i, lambda ops, d, **kw: ops.conv2d(d['x'], d['w'], d['bias'], res=d['res'], tail=(d['w3'], d['b3']), **fixed, **kw),
+                want, fixed=fixed, covered=k == 3 and s == 1 and ci % 32 == 0 and cm % 128 == 0 and h * w >= 8000,
+                **_reached(dress, rf, i, want, lambda: oracle.conv2d(t, i['w3'], i['b3'])))
 
 
-def gdn_resident_case(oracle, row, with_oracle=True):
+def gdn_resident_case(oracle, row, with_oracle=True, dress=None):
     """a row of GDN_RESIDENT_CASES: the stand-alone (I)GDN; want is None where the test leaves the CPU oracle out (large sizes)"""
     c, n, h, w, inv, use_res = row
     rng = np.random.default_rng(c * 1000 + n * 100 + h + w + (5 if inv else 0))
     x = rng.standard_normal((n, h, w, c), dtype=np.float32)
     beta, gamma = _gdn_params(rng, c)
     res = rng.standard_normal((n, h, w, c), dtype=np.float32) if use_res else None
-    return Case({'x': x, 'beta': beta, 'gamma': gamma, 'res': res},
-                lambda ops, d, **kw: ops.gdn(d['x'], d['beta'], d['gamma'], inverse=inv, res=d['res'], **kw),
-                oracle.gdn(x, beta, gamma, inverse=inv, res=res) if with_oracle else None)
+    rf = row_facts(abi.MODE_IGDN if inv else abi.MODE_GDN)
+    i = _dressed(dress, rng, {'x': x, 'beta': beta, 'gamma': gamma, 'res': res}, rf)
+    with np.errstate(all='ignore'):
+        want = oracle.gdn(i['x'], beta, gamma, inverse=inv, res=i['res']) if with_oracle else None
+    return Case(i, lambda ops, d, **kw: ops.gdn(d['x'], d['beta'], d['gamma'], inverse=inv, res=d['res'], **kw), want,
+                **_reached(dress, rf, i, want, lambda inverse=False: oracle.gdn(i['x'], beta, gamma, inverse=inv or inverse)))
 
 
-def wino_case(oracle, variant, row, seed):
+def wino_case(oracle, variant, row, seed, dress=None):
     """a row of WINO_CASES (variant 301), POLY_CASES (302) or TC_CASES (303, weights scaled for its 4 classes); the 5x5 tables have
     no gate multiplicand.  Needs version 2 of the contract with the size rule lifted on both sides (the tests' fixture)."""
     n, h, w, ci, co, a1, a2, has_b, has_m, has_r = row if len(row) == 10 else row[:8] + (False, row[8])
@@ -312,8 +353,12 @@ def wino_case(oracle, variant, row, seed):
     m = rng.standard_normal((n, ho, wo, co)).astype(np.float32) if has_m else None
     r = rng.standard_normal((n, ho, wo, co)).astype(np.float32) if has_r else None
     fixed = dict(mode=mode, stride=s, pad=pad, act1=a1, act2=a2)
-    return Case({'x': x, 'w': wt, 'bias': b, 'mul': m, 'res': r}, _conv_call(('mul', 'res'), **fixed),
-                oracle.conv2d(x, wt, b, mul=m, res=r, **fixed))
+    rf = row_facts(mode, k, s, pad, a1, a2, variant=variant)
+    i = _dressed(dress, rng, {'x': x, 'w': wt, 'bias': b, 'mul': m, 'res': r}, rf)
+    with np.errstate(all='ignore'):
+        want = oracle.conv2d(i['x'], i['w'], i['bias'], mul=i['mul'], res=i['res'], **fixed)
+    return Case(i, _conv_call(('mul', 'res'), **fixed), want,
+                **_reached(dress, rf, i, want, lambda: oracle.conv2d(i['x'], i['w'], i['bias'], mode=mode, stride=s, pad=pad)))
 
 
 @pytest.fixture()
@@ -343,8 +388,7 @@ def wino_three_launches(variant, c, cuda):
     for launch in range(3):
         got, variants = profiled(lambda: c.call(ops, d))
         assert variants == [variant], (launch, variants)
-        g = got.cpu().numpy()
-        assert np.array_equal(g, c.want), (launch, float(np.abs(g - c.want).max()))
+        assert_bits(got.cpu().numpy(), c.want, 'launch %d' % launch)
 
 
 def wino_weights_case(oracle, form, c_in):
@@ -373,7 +417,7 @@ def bf16x3_case(row, seed):
     return Case({'x': x, 'w': wt, 'bias': b, 'beta': beta, 'gamma': gamma}, call, None)
 
 
-def mfma_tile_case(oracle, seed, c_in):
+def mfma_tile_case(oracle, seed, c_in, dress=None):
     """M = 2 * 9 * 13 = 234 rows and 72 output channels (multiples of no tile side): partial tiles along both; 3x3, leaky, residual"""
     rng = np.random.default_rng(seed)
     x = rng.standard_normal((2, 9, 13, c_in), dtype=np.float32)
@@ -381,7 +425,12 @@ def mfma_tile_case(oracle, seed, c_in):
     b = rng.standard_normal(72, dtype=np.float32)
     res = rng.standard_normal((2, 9, 13, 72), dtype=np.float32)
     fixed = dict(stride=1, pad=1, act1=abi.ACT_LEAKY)
-    return Case({'x': x, 'w': wt, 'bias': b, 'res': res}, _conv_call(('res',), **fixed), oracle.conv2d(x, wt, b, res=res, **fixed))
+    rf = row_facts(abi.MODE_CONV, 3, 1, 1, abi.ACT_LEAKY)
+    i = _dressed(dress, rng, {'x': x, 'w': wt, 'bias': b, 'res': res}, rf)
+    with np.errstate(all='ignore'):
+        want = oracle.conv2d(i['x'], i['w'], i['bias'], res=i['res'], **fixed)
+    return Case(i, _conv_call(('res',), **fixed), want,
+                **_reached(dress, rf, i, want, lambda: oracle.conv2d(i['x'], i['w'], i['bias'], stride=1, pad=1)))
 
 
 # ---- conv_images and pack_images -------------------------------------------------------------------------------------------------
@@ -400,7 +449,7 @@ def _image_sources(rng, n, h, w, zero_pad, with_f3):
     return src
 
 
-def conv_images_cases(oracle, h, w, n, use_gdn, part_lists):
+def conv_images_cases(oracle, h, w, n, use_gdn, part_lists, dress=None):
     """the first analysis layer (5x5 stride 2 -> 64, GDN or leaky) on every list of image sources in part_lists (names of
     _image_sources), weights drawn per list from one stream: call(ops, d) runs it from an ops.ImageStack, which the fused kernel
     must take (no packed tensor); call(ops, d, packed=True) is the pack + conv pair it replaces"""
@@ -423,8 +472,15 @@ def conv_images_cases(oracle, h, w, n, use_gdn, part_lists):
             got = ops.conv2d(stack, d['w'], d['bias'], stride=2, pad=2, act1=act1, gdn=(d['beta'], d['gamma'], False) if use_gdn else None)
             assert packed or stack._packed is None, 'the fused kernel must have taken this layer (no packed tensor)'
             return got
-        want = oracle.conv2d(oracle.pack_images(parts, h, w), wt, bias, stride=2, pad=2, act1=act1, gdn=(beta, gamma, False) if use_gdn else None)
-        cases.append(Case({'parts': parts, 'w': wt, 'bias': bias, 'beta': beta, 'gamma': gamma}, call, want, act1=act1))
+        rf = row_facts(abi.MODE_CONV, 5, 2, 2, act1, fused_gdn=False if use_gdn else None,
+                       plane_cols=[4 * j + ch for j, p in enumerate(parts) if isinstance(p, dict) for ch in range(3)])
+        i = _dressed(dress, rng, {'parts': parts, 'w': wt, 'bias': bias, 'beta': beta, 'gamma': gamma}, rf)
+        gdn = (beta, gamma, False) if use_gdn else None
+        with np.errstate(all='ignore'):
+            packed = oracle.pack_images(i['parts'], h, w)
+            want = oracle.conv2d(packed, i['w'], i['bias'], stride=2, pad=2, act1=act1, gdn=gdn)
+        cases.append(Case(i, call, want, act1=act1,
+                          **_reached(dress, rf, i, want, lambda: oracle.conv2d(packed, i['w'], i['bias'], stride=2, pad=2, gdn=gdn))))
     return cases
 
 

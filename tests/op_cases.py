@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from aivc_amd import abi
+from numeric_regimes import assert_bits
 from warp_modes_cases import BICUBIC_REFERENCE_DEVIATION, case_key, left_out
 
 
@@ -41,7 +42,10 @@ def eq(a_gpu, b_np):
     if a.dtype == np.int32 and b_np.dtype == np.uint32:
         a = a.view(np.uint32)
     assert a.shape == b_np.shape
-    np.testing.assert_array_equal(a, b_np)
+    if a.dtype.kind == 'f' and a.dtype == b_np.dtype:  # bit exact means bits: +0 is not -0, a NaN matches a NaN (assert_bits names the first difference)
+        assert_bits(a, b_np)
+    else:
+        np.testing.assert_array_equal(a, b_np)
 
 
 def eq_all(got, want):

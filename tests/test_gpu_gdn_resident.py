@@ -9,6 +9,7 @@ import torch
 
 from aivc_amd import abi
 from conv_cases import GDN_RESIDENT_CASES, gdn_resident_case
+from numeric_regimes import assert_bits
 from op_cases import T, on
 
 pytestmark = pytest.mark.gpu
@@ -60,7 +61,7 @@ def test_resident_gdn_outside_the_lean_range(kind, inv, oracle, cuda):
         x[0, 7, 1, 99] = np.float32(2.0 ** 50)
     want = oracle.gdn(x, beta, gamma, inverse=inv)
     got = ops.gdn(T(x, cuda), T(beta, cuda), T(gamma, cuda), inverse=inv)
-    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    assert_bits(got.cpu().numpy(), want)
 
 
 def test_unsupported_shapes_fall_back(cuda):

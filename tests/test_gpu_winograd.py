@@ -10,6 +10,7 @@ import torch
 
 from aivc_amd import abi
 from conv_cases import POLY_CASES, TC_CASES, WINO_CASES, fp32w, wino_case, wino_weights_case  # noqa: F401 (fp32w: a fixture)
+from numeric_regimes import assert_bits
 from op_cases import T, on, profiled
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _runs_on(variant, c, cuda, next_to_version_1=True):
     got, variants = profiled(lambda: c.run(ops, on(cuda)))
     assert variants == [variant], variants
     g = got.cpu().numpy()
-    assert np.array_equal(g, c.want), float(np.abs(g - c.want).max())
+    assert_bits(g, c.want)
     if next_to_version_1:
         prev = ops.set_precision('fp32')
         try:
@@ -42,7 +43,7 @@ def test_weight_transform_equals_oracle(cuda, oracle):
     rng = np.random.default_rng(9)
     w = (rng.standard_normal((64, 3, 3, 96)) * 3).astype(np.float32)  # (the transform itself takes any c_out % 64 == 0)
     u = ops.winograd_weights(T(w, cuda)).cpu().numpy()
-    assert np.array_equal(u, oracle.winograd_weights(w))
+    assert_bits(u, oracle.winograd_weights(w))
     # G g G^T in fp64
     G = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], np.float64)
     ref = np.einsum('ik,oklc,jl->oijc', G, w.astype(np.float64), G).reshape(64, 16, 96)
@@ -111,7 +112,7 @@ def test_fused_gdn_request_is_two_launches_with_the_oracle_bits(cuda, oracle, fp
     for inverse in (False, True):
         want = oracle.conv2d(x, wt, b, stride=1, pad=1, gdn=(beta, gamma, inverse), res=res)
         got = ops.conv2d(T(x, cuda), T(wt, cuda), T(b, cuda), stride=1, pad=1, gdn=(T(beta, cuda), T(gamma, cuda), inverse), res=T(res, cuda))
-        assert np.array_equal(got.cpu().numpy(), want), inverse
+        assert_bits(got.cpu().numpy(), want, 'inverse %s' % inverse)
 
 
 def test_size_rule_of_the_version(cuda, oracle):
@@ -130,7 +131,7 @@ def test_size_rule_of_the_version(cuda, oracle):
             variants = [pr[0] for pr in ops.PROFILE]
             ops.PROFILE = None
             assert (variants == [301]) == (want == 301), (h, w, variants)
-            assert np.array_equal(got.cpu().numpy(), oracle.conv2d(x, wt, None, stride=1, pad=1)), (h, w)
+            assert_bits(got.cpu().numpy(), oracle.conv2d(x, wt, None, stride=1, pad=1), '%d x %d' % (h, w))
     finally:
         ops.PROFILE = None
         ops.set_precision(prev_h)
@@ -232,7 +233,7 @@ def test_polyphase_weight_transform_equals_oracle(cuda, oracle):
     w = (rng.standard_normal((64, 5, 5, 32)) * 3).astype(np.float32)
     u = ops.winograd_weights(T(w, cuda)).cpu().numpy()
     assert u.size == 64 * 16 * 4 * 32
-    assert np.array_equal(u, oracle.winograd_weights(w))
+    assert_bits(u, oracle.winograd_weights(w))
     # positions that are zero by construction: i == 3 for py = 1, j == 3 for px = 1 (virtual channel = phase * c_in + ci)
     img = u.reshape(1, 16, 16, 2, 64, 4)  # [co / 64][cv / 8][p][(cv % 8) / 4][co % 64][cv % 4]
     for phase in range(4):
@@ -279,7 +280,7 @@ def test_polyphase_fused_gdn_request_is_two_launches_with_the_oracle_bits(cuda, 
     gamma = (0.1 * np.eye(128) + rng.uniform(0, .05, (128, 128))).astype(np.float32)
     want = oracle.conv2d(x, wt, b, stride=2, pad=2, gdn=(beta, gamma, False))
     got = ops.conv2d(T(x, cuda), T(wt, cuda), T(b, cuda), stride=2, pad=2, gdn=(T(beta, cuda), T(gamma, cuda), False))
-    assert np.array_equal(got.cpu().numpy(), want)
+    assert_bits(got.cpu().numpy(), want)
 
 
 @pytest.mark.parametrize('idx', range(len(TC_CASES)))
@@ -293,7 +294,7 @@ def test_transposed_weight_transform_equals_oracle(cuda, oracle):
     w = (rng.standard_normal((64, 5, 5, 32)) * 3).astype(np.float32)
     u = ops.winograd_weights(T(w, cuda), transposed=True).cpu().numpy()
     assert u.size == 4 * 64 * 16 * 32
-    assert np.array_equal(u, oracle.winograd_weights(w, transposed=True))
+    assert_bits(u, oracle.winograd_weights(w, transposed=True))
     img = u.reshape(4, 4, 16, 2, 64, 4)  # [class (co_virtual / 64)][ci / 8][p][(ci % 8) / 4][co % 64][ci % 4]
     for cls in range(4):
         pyc, pxc = cls >> 1, cls & 1
@@ -313,4 +314,4 @@ def test_transposed_fused_igdn_request_is_two_launches_with_the_oracle_bits(cuda
     gamma = (0.1 * np.eye(64) + rng.uniform(0, .05, (64, 64))).astype(np.float32)
     want = oracle.conv2d(x, wt, b, mode=abi.MODE_TCONV, stride=2, gdn=(beta, gamma, True))
     got = ops.conv2d(T(x, cuda), T(wt, cuda), T(b, cuda), mode=abi.MODE_TCONV, stride=2, gdn=(T(beta, cuda), T(gamma, cuda), True))
-    assert np.array_equal(got.cpu().numpy(), want)
+    assert_bits(got.cpu().numpy(), want)

@@ -26,7 +26,8 @@ __global__ __launch_bounds__(256) void quantize_center_rows_kernel(const float *
   const float m = mu ? mu[gid] : 0.0f;
   float r = __builtin_rintf(mu ? y[gid] - m : y[gid]);
   r = r < -256.0f ? -256.0f : (r > 256.0f ? 256.0f : r);  // the alphabet of the coder: symbols 0 .. 512
-  if (q) q[gid] = (int16_t)r;
+  const float level = r == r ? r : 0.0f;  // in [-256, 256]; a NaN latent: q = 0 (its y_hat stays NaN)
+  if (q) q[gid] = (int16_t)level;
   if (y_hat) {
     float v = mu ? r + m : r;
     if (gains) v = v * __builtin_fabsf(gains[(size_t)blockIdx.y * c + e % c]);

@@ -101,7 +101,8 @@ __device__ __forceinline__ float cast8(float x, uint8_t *byte) {
   float c = x < 0.0f ? 0.0f : x;
   c = c > 1.0f ? 1.0f : c;
   const float r = __builtin_rintf(255.0f * c);
-  *byte = (uint8_t)r;
+  const float level = r == r ? r : 0.0f;  // in [0, 255]; a NaN pixel: byte 0 (its float level stays NaN)
+  *byte = (uint8_t)level;
   return r / 255.0f;
 }
 
@@ -218,9 +219,9 @@ __device__ __forceinline__ float warp_coord(float pos, int size) {
   const int d = size - 1 > 1 ? size - 1 : 1;
   const float g = 2.0f * pos / (float)d - 1.0f;
   float ix = ((g + 1.0f) / 2.0f) * (float)(size - 1);
-  ix = ix < 0.0f ? 0.0f : ix;
-  ix = ix > (float)(size - 1) ? (float)(size - 1) : ix;
-  return ix;
+  ix = ix > 0.0f ? ix : 0.0f;  // as warp_modes_pad: a NaN position (a NaN flow, inf * 0 on an axis of size 1) is position 0
+  const float hi = (float)(size - 1);
+  return ix < hi ? ix : hi;
 }
 
 struct WarpTap {
@@ -237,6 +238,7 @@ __device__ __forceinline__ WarpTap warp_taps(int h, int w, float fx, float fy, i
   t.ne = (ix - x0) * (y1 - iy);
   t.sw = (x1 - ix) * (iy - y0);
   t.se = (ix - x0) * (iy - y0);
+  // (warp_coord: ix, iy are finite and inside [0, size - 1], so are their floors)
   const int xi0 = (int)x0, yi0 = (int)y0, xi1 = xi0 + 1, yi1 = yi0 + 1;
   const bool x0ok = xi0 >= 0 && xi0 < w, x1ok = xi1 >= 0 && xi1 < w;
   const bool y0ok = yi0 >= 0 && yi0 < h, y1ok = yi1 >= 0 && yi1 < h;
@@ -453,7 +455,8 @@ __global__ __launch_bounds__(256) void quantize_center_kernel(const float *__res
   const float m = mu ? mu[gid] : 0.0f;
   float r = __builtin_rintf(mu ? y[gid] - m : y[gid]);
   r = r < -256.0f ? -256.0f : (r > 256.0f ? 256.0f : r);  // the alphabet of the coder: symbols 0 .. 512
-  if (q) q[gid] = (int16_t)r;
+  const float level = r == r ? r : 0.0f;  // in [-256, 256]; a NaN latent: q = 0 (its y_hat stays NaN)
+  if (q) q[gid] = (int16_t)level;
   if (y_hat) {
     float v = mu ? r + m : r;
     if (gain) v = v * __builtin_fabsf(gain[gid % c]);

@@ -76,6 +76,7 @@ AIVC_HD double aivc_det_exp_core(double x) {
   p = AIVC_FMA(p, r, 0.5);
   p = AIVC_FMA(p, r, 1.0);
   p = AIVC_FMA(p, r, 1.0);
+  /* |kd| <= 1075 and not NaN: every caller has x inside [-745, 709] (aivc_det_exp's tests, aivc_laplace_cdf_u16_scale's) */
   const int k = (int)kd;
   const int k1 = k / 2;
   const int k2 = k - k1;
@@ -220,13 +221,17 @@ AIVC_HD float aivc_laplace_cdf(float t, float sigma) {
   return 0.5f - hs * e;
 }
 /* torchac float -> uint16 CDF quantisation for point k of an Lp = 514 row:
- * int16 cast of round(cdf * (2^16 - (Lp - 1))) then + k, wrapping. */
+ * int16 cast of round(cdf * (2^16 - (Lp - 1))) then + k, wrapping.  A cdf is a value in [0, 1] and is taken as one:
+ * what lies outside (the +-inf of a negative or -0 sigma) goes to the nearer end, a NaN (a NaN sigma) to 0. */
 AIVC_HD uint16_t aivc_cdf_quant(float cdf, int k) {
+  const float lo = cdf > 0.0f ? cdf : 0.0f; /* (false for a NaN) */
+  const float c = lo < 1.0f ? lo : 1.0f;
 #if defined(__HIPCC__)
-  const float r = __builtin_rintf(cdf * 65023.0f);
+  const float r = __builtin_rintf(c * 65023.0f);
 #else
-  const float r = rintf(cdf * 65023.0f);
+  const float r = rintf(c * 65023.0f);
 #endif
+  /* r is a whole number in [0, 65023] */
   return (uint16_t)(((int32_t)r + k) & 0xFFFF);
 }
 AIVC_HD uint16_t aivc_laplace_cdf_u16(int k, float sigma) {
@@ -234,11 +239,13 @@ AIVC_HD uint16_t aivc_laplace_cdf_u16(int k, float sigma) {
 }
 /* The scale of the Laplace law as aivc_laplace_cdf derives it from sigma (one IEEE division). */
 AIVC_HD float aivc_laplace_scale(float sigma) { return sigma / 1.41421354f; }
-/* aivc_laplace_cdf_u16(k, sigma) for b = aivc_laplace_scale(sigma), sigma > 0 and not NaN, 0 <= k <= 512: the same
- * operations on the same values, laid out for a wavefront that evaluates one entry per lane in the range decoder's rare
- * path (csrc/entropy.hip) -- the argument of expm1 is clamped to the saturation point instead of branching around the
- * fp64 work (expm1f(x) = -1 for x < -17.5 either way), and exp() runs without its NaN / overflow / underflow tests
- * (x is in [-17.5, -0.34] there).  Equality with aivc_laplace_cdf_u16 over sigma and k is a test
+/* aivc_laplace_cdf_u16(k, sigma) for b = aivc_laplace_scale(sigma), any sigma (zeros, negative, infinite and NaN
+ * included), 0 <= k <= 512: the same operations on the same values, laid out for a wavefront that evaluates one entry
+ * per lane in the range decoder's rare path (csrc/entropy.hip) -- the argument of expm1 is clamped to the saturation
+ * point instead of branching around the fp64 work (expm1f(x) = -1 for x < -17.5 either way), and exp() runs without
+ * its NaN / overflow / underflow tests where x is in [-17.5, -0.34].  An argument that is not <= 0 (a negative or -0
+ * sigma: up to +inf; a NaN sigma: NaN) takes aivc_det_expm1 with those tests, as the row function does.  Equality with
+ * aivc_laplace_cdf_u16 over sigma and k is a test
  * (tests/test_oracle_golden.py::test_laplace_tail_entries_equal_row_entries). */
 AIVC_HD uint16_t aivc_laplace_cdf_u16_scale(int k, float b) {
   const float t = (float)k - 256.5f; /* never 0 */
@@ -247,7 +254,9 @@ AIVC_HD uint16_t aivc_laplace_cdf_u16_scale(int k, float b) {
   const float x = -a;
   const float xc = x < -17.5f ? -17.5f : x;
   const double xd = (double)xc;
-  const double em = AIVC_FABS(xd) < 0.34 ? aivc_det_expm1_small(xd) : aivc_det_exp_core(xd) - 1.0;
+  double em;
+  if (!(xc <= 0.0f)) em = aivc_det_expm1(xd); /* positive or NaN: outside aivc_det_exp_core's domain */
+  else em = AIVC_FABS(xd) < 0.34 ? aivc_det_expm1_small(xd) : aivc_det_exp_core(xd) - 1.0; /* xd in [-17.5, -0.34] */
   const float e = x < -17.5f ? -1.0f : (float)em;
   const float hs = t < 0.0f ? -0.5f : 0.5f;
   return aivc_cdf_quant(0.5f - hs * e, k);

@@ -333,6 +333,7 @@ int aivc_conv_images(const aivc_image_src *src, int32_t n_img, const aivc_conv_p
  * ceil(w/2), then the 8-bit cast round(255*clamp(v,0,1))/255 (half-to-even).
  * x is [n][hx][wx][cx] with hx>=h, wx>=w, cx>=3; skip is [n][h][w][cs] (cs>=3) or NULL.
  * Outputs (each may be NULL): fp32 planes holding 8-bit levels and/or the bytes themselves.
+ * A NaN value (a NaN pixel, inf + -inf with skip) gives byte 0 and a NaN float level; +-inf clamp to 1 / 0.
  * Replaces src/real_life/decode.py:549-578, src/layers/ae/ae_layers.py:38-56,
  *          src/func_util/img_processing.py:68-73. */
 int aivc_frame_to_yuv420(const float *x, int32_t n, int32_t hx, int32_t wx, int32_t cx,
@@ -364,14 +365,21 @@ int aivc_warp_blend(const float *mof, int32_t hm, int32_t wm, int32_t cm, const 
  * GPUs): mof is the band of the MOFNet output, [n][hm][wm][cm] with its local row 0 = frame row row0
  * (hm >= rows); prev / next are the WHOLE references [n][h][w][cr] (motion vectors reach anywhere);
  * pred / skip / x_warp are [n][rows][w][co], alpha_out / beta_out [n][rows][w].  Row r of the outputs is bit-identical
- * to row row0 + r of aivc_warp_blend on the whole frame. */
+ * to row row0 + r of aivc_warp_blend on the whole frame.
+ * The sample position of either flow is clamped to [0, size - 1] as aivc_warp_modes clamps it (p > 0 ? p : 0, then
+ * p < size - 1 ? p : size - 1): a NaN position -- a NaN flow, or inf * 0 from an infinite flow on an axis of size 1 --
+ * is position 0, +-inf the nearer edge.  No flow value forms a tap outside the frame.  alpha and beta clamp with
+ * comparisons that a NaN passes: a NaN alpha / beta stays NaN in alpha_out / beta_out and in the blend. */
 int aivc_warp_blend_rows(const float *mof, int32_t hm, int32_t wm, int32_t cm, const float *prev,
                          const float *next, int32_t cr, int32_t n, int32_t h, int32_t w, int32_t row0, int32_t rows,
                          int32_t frame_type, float *pred, float *skip, float *x_warp, int32_t co,
                          float *alpha_out, float *beta_out, aivc_stream_t stream);
 
 /* Stand-alone warp (src/func_util/optical_flow.py:14-55): x [n][h][w][c], flow [n][h][w][2]
- * (channel 0 = horizontal, 1 = vertical, pixel units) -> out [n][h][w][c]. */
+ * (channel 0 = horizontal, 1 = vertical, pixel units) -> out [n][h][w][c].
+ * grid_sample(bilinear, border, align_corners=True): the position is clamped to [0, size - 1], a NaN position (a NaN
+ * flow, or inf * 0 on an axis of size 1) is position 0.  A tap of weight 0 still multiplies its pixel (0 * inf = NaN),
+ * except the tap past the last row / column, which is skipped. */
 int aivc_warp(const float *x, const float *flow, int32_t n, int32_t h, int32_t w, int32_t c,
               float *out, aivc_stream_t stream);
 
@@ -397,7 +405,7 @@ int aivc_gain_interp(const float *g_r, const float *g_t, int32_t c, float l, flo
 
 /* Encoder side: q = clamp(rint(y - mu), -256, 255) (half-to-even); y_hat = (q + mu) * |gain_dec|.
  * mu == NULL means mu = 0 (the z latent); gain_dec == NULL means gain 1.  q (int16) and y_hat
- * may each be NULL.  Replaces Quantizer (src/layers/misc/misc_layers.py:162-169) and the
+ * may each be NULL.  A NaN y - mu gives q = 0 and a NaN y_hat (+-inf clamp to +-256).  Replaces Quantizer (src/layers/misc/misc_layers.py:162-169) and the
  * centring/gain of src/real_life/decode.py:867-885. */
 int aivc_quantize_center(const float *y, const float *mu, const float *gain_dec, size_t npix,
                          int32_t c, int16_t *q, float *y_hat, aivc_stream_t stream);
@@ -443,6 +451,10 @@ typedef struct aivc_map_list {
 /* Laplace(0, sigma/sqrt(2)) CDF rows for every coded symbol position, channel-major order
  * (stream position p = (m * npix + pix), channel = maps.idx[m]):
  *   rows[p][k] = (uint16)(rint(cdf(k - 256.5) * 65023) + k),  k = 0..513.
+ * Any float is accepted as sigma.  The cdf is clamped to [0, 1] before it is quantised, a NaN cdf to 0: a NaN sigma
+ * gives the row k, sigma = 0 the rows k / 65023 + k of a point mass, sigma = +inf 32512 + k; entries 0..512 of these
+ * rows increase strictly and can be coded.  sigma < 0 or -0.0 gives rows that do not increase (for -0.0: 65023 + k
+ * below the centre, k above it): the same values on host and device, but no range coder may be run on them.
  * sigma is NHWC [npix][c].  Replaces src/real_life/bitstream.py:127-154 without ever holding
  * the fp32 [C,H,W,514] tensor. */
 int aivc_laplace_cdf_rows(const float *sigma, size_t npix, int32_t c, const aivc_map_list *maps,

@@ -27,6 +27,7 @@ from op_cases import (AUX, FRAME_BATCH_CASES, FRAME_SIZES, RANGE_DECODE_CASES, W
                       eq, frame_batch_case, frame_sources, frame_to_yuv420_case, gain_interp_case, latent_ops_case, metrics_case, on,
                       pad_channels_case, profiled, range_coder_case, range_coder_pmf_case, range_encode_case, rate_estimates_case,
                       stream_bytes, warp_blend_case, warp_blend_sources, warp_case, warp_modes_case, yuv420_to_444_case, yuv_planes)
+from op_regimes import REGIME_CASES
 from warp_modes_cases import CASES as WARP_CASES, case_key
 
 pytestmark = pytest.mark.gpu
@@ -433,6 +434,13 @@ def test_bounds_rate(n, oracle, cuda):
 def test_rate_estimates(shape, oracle, cuda):
     """laplace_prob with and without mu, table_prob, rate_bits"""
     run_guarded(rate_estimates_case(oracle, shape[-1], shape), cuda)
+
+
+# ---- the regimes of tests/op_regimes.py ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case_id', sorted(REGIME_CASES))
+def test_op_regimes(case_id, oracle, cuda):
+    """every builder of tests/op_regimes.py once more: non-finite flows, pixels, latents and sigmas next to the guards"""
+    run_guarded(REGIME_CASES[case_id](oracle), cuda)
 
 
 # ---- deterministic transcendentals -----------------------------------------------------------------------------------------------

@@ -57,13 +57,24 @@ def test_three_channel_frames_go_through_every_mode(cuda, golden):
     np.testing.assert_allclose(warp(x, flo, 'bilinear').cpu().numpy(), g['y_0_bilinear_border_1'], rtol=1e-5, atol=2e-6)
 
 
-@pytest.mark.parametrize('i', range(3))
-def test_codec_mode_is_aivc_warp_bit_for_bit(i, cuda, golden):
+def _codec_mode_inputs(i, golden, oracle):
+    """the reference-run fixtures warp_0 .. warp_2 (finite flows), or a flow set of tests/op_regimes.py FLOWS on one of its shapes"""
+    if isinstance(i, int):
+        g = golden('warp_%d' % i)
+        return g['x'], g['flow']
+    import op_regimes
+    d = op_regimes.REGIME_CASES[i](oracle).inputs
+    return (np.ascontiguousarray(np.transpose(d[k], (0, 3, 1, 2))) for k in ('x', 'flow'))
+
+
+@pytest.mark.parametrize('i', list(range(3)) + ['warp-%s-%dx%dx%d' % ((nm,) + sh) for nm in ('nan_x', 'nan_y', 'nan_xy', 'inf', 'big', 'integer')
+                                                for sh in ((2, 5, 7), (2, 5, 1), (1, 1, 1))])
+def test_codec_mode_is_aivc_warp_bit_for_bit(i, cuda, golden, oracle):
     from aivc_amd import abi, ops
     from aivc_amd._lib import call
-    g = golden('warp_%d' % i)
-    x = ops.to_nhwc(torch.from_numpy(g['x']).to(cuda))
-    flo = ops.to_nhwc(torch.from_numpy(g['flow']).to(cuda))
+    x, flo = _codec_mode_inputs(i, golden, oracle)
+    x = ops.to_nhwc(torch.from_numpy(x).to(cuda))
+    flo = ops.to_nhwc(torch.from_numpy(flo).to(cuda))
     n, h, w, c = x.shape
     a, b = torch.full_like(x, 7.0), torch.full_like(x, -7.0)
     call('aivc_warp', x.data_ptr(), flo.data_ptr(), n, h, w, c, a.data_ptr(), ops._stream())

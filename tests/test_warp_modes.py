@@ -42,15 +42,18 @@ def pad_coordinate(p, size, pad, ac):
             a = np.abs(p - lo)
             extra = a - np.trunc(a / twice_span) * twice_span
             p = np.minimum(extra, twice_span - extra) + lo
-    return np.clip(p, t(0.0), t(size - 1))
+    with np.errstate(invalid='ignore'):  # grid_sample's clip, written as its min / max: a NaN coordinate ends at 0
+        p = np.where(p > t(0.0), p, t(0.0))
+        return np.where(p < t(size - 1), p, t(size - 1))
 
 
 def gather(x, iy, ix):
     """x [c, h, w], integer-valued float indices [h, w] -> (values [c, h, w] with 0 outside, inside [h, w] as 0. / 1.)"""
     _, h, w = x.shape
-    ok = (iy >= 0) & (iy < h) & (ix >= 0) & (ix < w)
-    v = x[:, np.clip(iy, 0, h - 1).astype(np.int64), np.clip(ix, 0, w - 1).astype(np.int64)]
-    return v * ok, ok.astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        ok = (iy >= 0) & (iy < h) & (ix >= 0) & (ix < w)  # (false for a NaN index: `zeros` padding leaves a NaN position alone)
+    v = x[:, np.where(ok, iy, 0).astype(np.int64), np.where(ok, ix, 0).astype(np.int64)]
+    return np.where(ok, v, 0.0), ok.astype(np.float64)  # (a tap outside is skipped, not multiplied by 0: the pixel may be inf)
 
 
 def cubic_weights(t):
@@ -183,3 +186,7 @@ def test_fixture_regenerates_bit_for_bit(tmp_path, golden):
     for k in old.files:
         assert new[k].dtype == old[k].dtype and new[k].shape == old[k].shape, k
         assert new[k].tobytes() == old[k].tobytes(), k
+    new, old = np.load(str(tmp_path / 'warp_nonfinite.npz')), golden('warp_nonfinite')  # (the non-finite flow sets of tests/op_regimes.py)
+    assert sorted(new.files) == sorted(old.files)
+    for k in old.files:
+        assert new[k].dtype == old[k].dtype and new[k].tobytes() == old[k].tobytes(), k

@@ -20,7 +20,11 @@ The tool asserts what tests/test_warp_modes.py and tests/test_gpu_warp_modes.py 
 case have a mask within 1e-5 of the threshold 0.9999, and at most 0.5 % of the `nearest` samples lie within 1e-4 of a
 half-integer without being exactly on it.
 
-    python tools/gen_golden_warp.py [--out DIR]     # rewrites tests/golden/warp_modes.npz
+A second, small file, tests/golden/warp_nonfinite.npz, holds one set x [1, 4, 9, 11] in the same layout (shape index 0) whose
+N(0, 1) * 2 flow carries the sets of nonfinite_flow_sets() below (those of FLOWS in tests/op_regimes.py) -- NaN in x, in y, in
+both, +-inf, +-3e38, whole positions -- at 5 pixels each: what the reference does with a flow that is not finite, in all 18 modes.
+
+    python tools/gen_golden_warp.py [--out DIR]     # rewrites tests/golden/warp_modes.npz and warp_nonfinite.npz
 """
 import os
 import sys
@@ -39,6 +43,7 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests', 'g
 INTERP = ('bilinear', 'nearest', 'bicubic')
 PAD = ('border', 'zeros', 'reflection')
 SHAPES = ((1, 4, 29, 53), (1, 8, 17, 33))
+NONFINITE_SHAPE = (1, 4, 9, 11)
 MASK_THRESHOLD = 0.9999
 MASK_BAND = 1e-5    # pixels whose stored mask is this close to the threshold are left out of the comparisons
 TIE_BAND = 1e-4     # `nearest` samples this close to a half-integer (and not on it) likewise
@@ -66,6 +71,36 @@ def make_flow(gen, h, w, ties):
         flo[0, 1, 7:9, 1:13] = torch.randint(-2, 3, (2, 12), generator=gen).float()  # ... horizontal tie only
         flo[0, 0, 9:10, 1:7] = torch.randint(-2, 3, (1, 6), generator=gen).float()  # ... vertical tie only
     return flo
+
+
+def nonfinite_flow_sets():
+    """The flow sets of the non-finite fixture, in order: [(name, kinds)], a kind (fx, fy) with None = the drawn value stays, or a
+    function (row, col, h, w) -> (fx, fy).  Pixel i of a set takes kind i modulo their number.  The same sets, in the same
+    order, as FLOWS of tests/op_regimes.py; tests/test_op_regimes.py rebuilds the fixture's flow from that table and compares."""
+    nan, inf, big = np.float32(np.nan), np.float32(np.inf), np.float32(3e38)
+    return [('nan_x', [(nan, None)]), ('nan_y', [(None, nan)]), ('nan_xy', [(nan, nan)]),
+            ('inf', [(inf, None), (-inf, None), (None, inf), (None, -inf), (inf, -inf)]),
+            ('big', [(big, None), (-big, None), (None, big), (None, -big), (-big, big)]),
+            ('integer', [lambda r, q, h, w: (np.float32((q + 2) % w - q), np.float32((r + 1) % h - r)),   # a whole position inside
+                         lambda r, q, h, w: (np.float32(w - 1 - q), np.float32(h - 1 - r)),              # exactly size - 1
+                         lambda r, q, h, w: (np.float32(-q), np.float32(-r))])]                          # position 0
+
+
+def nonfinite_flow(gen, rng, h, w, per_set=5):
+    """[1, 2, h, w]: an N(0, 1) * 2 flow with every set of nonfinite_flow_sets() planted at per_set pixels of its own"""
+    flow = (torch.randn(1, h, w, 2, generator=gen) * 2.0).numpy()
+    sets = nonfinite_flow_sets()
+    _, rows, cols = np.unravel_index(rng.permutation(h * w)[:per_set * len(sets)], (1, h, w))
+    for i, (_, kinds) in enumerate(sets):
+        for j in range(per_set):
+            r, q = int(rows[per_set * i + j]), int(cols[per_set * i + j])
+            kind = kinds[j % len(kinds)]
+            fx, fy = kind(r, q, h, w) if callable(kind) else kind
+            if fx is not None:
+                flow[0, r, q, 0] = fx
+            if fy is not None:
+                flow[0, r, q, 1] = fy
+    return torch.from_numpy(np.ascontiguousarray(np.transpose(flow, (0, 3, 1, 2))))
 
 
 def sample_position(flo, h, w, align_corners):
@@ -118,10 +153,10 @@ def main():
     torch.set_num_threads(1)
     gen = torch.Generator().manual_seed(1418)
     arrs = {}
-    for s, shape in enumerate(SHAPES):
-        _, c, h, w = shape
-        x = torch.randn(*shape, generator=gen)
-        flo = make_flow(gen, h, w, ties=(s == 1))
+
+    def every_mode(arrs, s, x, flo):
+        """the 18 modes of one set into arrs -> the number of exact `nearest` ties"""
+        _, _, h, w = x.shape
         arrs['x_%d' % s], arrs['flow_%d' % s] = x.numpy(), flo.numpy()
         n_exact = 0
         for mode in INTERP:
@@ -130,13 +165,21 @@ def main():
                     y, m = warp_and_mask(warp, x, flo, mode, pad, ac)
                     key = '%d_%s_%s_%d' % (s, mode, pad, int(ac))
                     arrs['y_' + key], arrs['m_' + key] = y.numpy(), m.numpy()
-                    left_out = np.abs(m.numpy() - np.float32(MASK_THRESHOLD)) < MASK_BAND
-                    if mode == 'nearest':
-                        for p in sample_position(flo, h, w, ac):
-                            d = np.abs(p - np.floor(p) - np.float32(0.5))
-                            left_out = left_out | ((d < TIE_BAND) & (d != 0))[None]
-                            n_exact += int((d == 0).sum())
+                    with np.errstate(over='ignore', invalid='ignore'):  # (a NaN mask or position is in no band)
+                        left_out = np.abs(m.numpy() - np.float32(MASK_THRESHOLD)) < MASK_BAND
+                        if mode == 'nearest':
+                            for p in sample_position(flo, h, w, ac):
+                                d = np.abs(p - np.floor(p) - np.float32(0.5))
+                                left_out = left_out | ((d < TIE_BAND) & (d != 0))[None]
+                                n_exact += int((d == 0).sum())
                     assert left_out.mean() <= MAX_LEFT_OUT, (key, left_out.mean())
+        return n_exact
+
+    for s, shape in enumerate(SHAPES):
+        _, c, h, w = shape
+        x = torch.randn(*shape, generator=gen)
+        flo = make_flow(gen, h, w, ties=(s == 1))
+        n_exact = every_mode(arrs, s, x, flo)
         if s == 1:
             assert n_exact >= 100, n_exact  # the tie block does land on half-integers in fp32
         ix, iy = sample_position(flo, h, w, True)
@@ -146,6 +189,20 @@ def main():
     path = os.path.join(out_dir, 'warp_modes.npz')
     np.savez_compressed(path, **arrs)
     print('%-34s %7.1f kB' % ('warp_modes.npz', os.path.getsize(path) / 1e3))
+    assert os.path.getsize(path) < 1 << 20
+
+    # the non-finite set: its own generators, so that warp_modes.npz above does not move
+    _, c, h, w = NONFINITE_SHAPE
+    gen = torch.Generator().manual_seed(1419)
+    rng = np.random.default_rng(1419)
+    x = torch.randn(*NONFINITE_SHAPE, generator=gen)
+    flo = nonfinite_flow(gen, rng, h, w)
+    assert int(torch.isnan(flo).any(dim=1).sum()) == 15 and int(torch.isinf(flo).any(dim=1).sum()) == 5
+    arrs = {}
+    every_mode(arrs, 0, x, flo)
+    path = os.path.join(out_dir, 'warp_nonfinite.npz')
+    np.savez_compressed(path, **arrs)
+    print('%-34s %7.1f kB' % ('warp_nonfinite.npz', os.path.getsize(path) / 1e3))
     assert os.path.getsize(path) < 1 << 20
 
 

@@ -2,7 +2,8 @@
 // convolutions with c_in % 32 == 0 and c_out % 64 == 0 as Winograd F(2x2, 3x3) on the gfx950 matrix cores -- 16 multiplications
 // per 2x2 output pixels and channel pair instead of 36 on the scarce fp32 matrix pipe -- and, on the same kernel, the 5x5
 // stride-2 convolutions (polyphase form) and transposed convolutions (class by class).  What was tried on the way and what it
-// measured: experiments/r06.md (designs), experiments/wino_phases.md (phase offset), experiments/wino5_issue.md (5x5 forms).
+// measured: experiments/r06.md (designs), experiments/wino_phases.md (phase offset), experiments/wino5_issue.md (5x5 forms),
+// experiments/wino_class_walk.md (the transposed form's classes dealt round).
 //
 //   work split     a workgroup = a block of 8 x 8 output tiles (16 x 16 pixels) x 64 output channels, 8 waves: (4 x 8 tiles)
 //                  x 32 channels x 8 of the 16 positions each -- 8 accumulator blocks (128 registers) per wave, two waves per
@@ -31,13 +32,16 @@
 //                  MODE 1, polyphase 5x5 stride 2: 4 phases x c_in channels; the per-lane patch offsets change on phase entry,
 //                  so the issue is split into prepare() (every wave at the chunk head: all address arithmetic) and fire_*()
 //                  (the DMA instructions alone, placed by position half): the offset costs no second copy of the arithmetic.
-//                  MODE 2, transposed 5x5 stride 2: 4 classes in the block list, zero extension through 64-bit per-lane
-//                  addresses, issue_raw / issue_u with both heads at the barrier (no offset), 2 x 2 output stride in the
-//                  epilogue.  In the 5x5 forms a position whose U is zero by construction (wino_zero_pos) is neither
-//                  fetched nor multiplied; its V is computed and never read.
+//                  MODE 2, transposed 5x5 stride 2: 4 classes in the block list, dealt round among the workgroups
+//                  (wino_class_walk.h: the classes issue 16 / 12 / 12 / 9 positions per chunk, and the plain walk hands a
+//                  workgroup one class for the whole launch), zero extension through 64-bit per-lane addresses, issue_raw /
+//                  issue_u with both heads at the barrier (no offset), 2 x 2 output stride in the epilogue.
+//                  In the 5x5 forms a position whose U is zero by construction (wino_zero_pos) is neither fetched nor
+//                  multiplied; its V is computed and never read.
 #include <stdlib.h>
 
 #include "mfma_util.h"
+#include "wino_class_walk.h"
 
 namespace aivc {
 
@@ -84,7 +88,8 @@ __host__ __device__ constexpr uint32_t wino_pos_mask(int pc, int half) {
 // The block walk of a persistent workgroup.  The dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (each with
 // a private L2): workgroup b sits on XCD b & 7 and takes blocks of that XCD's contiguous eighth of the block list, interleaved with
 // the other workgroups of the XCD -- they advance through one region together; the channel blocks of a pixel block are neighbours
-// in the list (same raw patch).
+// in the list (same raw patch).  Which entries a workgroup takes is decided here; what an entry means is make_desc's business (the
+// transposed form reads it through wino_class_walk.h).
 struct WinoWalk {
   uint32_t x_lo, x_hi, slot, wg_per_xcd;  // this XCD's part of the list, this workgroup's place among the XCD's workgroups
   __device__ __forceinline__ WinoWalk(uint32_t total, uint32_t nwg, uint32_t wg) {
@@ -149,8 +154,15 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   const int nch = POLY ? 4 * (Cin >> 3) : (Cin >> 3);  // chunks of 8 (virtual) input channels per block
   auto make_desc = [&](uint32_t blk) {
     Desc d;
-    d.cb = (int)(blk % (uint32_t)gyc);
-    uint32_t rest = blk / (uint32_t)gyc;
+    uint32_t rest;
+    if constexpr (TC) {  // the classes of a pixel block are dealt round among the workgroups (wino_class_walk.h)
+      const WinoClassEntry e = wino_class_entry(blk, (uint32_t)gyc, (uint32_t)a.total, gridDim.x);
+      d.cb = (int)e.cb;
+      rest = e.pb;
+    } else {
+      d.cb = (int)(blk % (uint32_t)gyc);
+      rest = blk / (uint32_t)gyc;
+    }
     d.bxi = (int)(rest % (uint32_t)a.nbx);
     rest /= (uint32_t)a.nbx;
     d.byi = (int)(rest % (uint32_t)a.nby);

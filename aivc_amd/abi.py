@@ -223,6 +223,10 @@ def declare(lib, suffix=''):
         ev.argtypes = list(DETMATH_EVAL_ARGS) + [C.c_void_p]
         ev.restype = C.c_int
         fns['aivc_detmath_eval'] = ev
+        hold = lib.aivc_diag_hold_lds  # include/aivc_hip_diag.h: a workgroup that holds LDS for a bounded time
+        hold.argtypes = [C.c_uint32, C.c_uint32, _f, C.c_void_p]
+        hold.restype = C.c_int
+        fns['aivc_diag_hold_lds'] = hold
         wm = lib.aivc_warp_modes  # include/aivc_hip_warp.h: the warp in every sampling mode, no host twin either
         wm.argtypes = [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, C.c_void_p]
         wm.restype = C.c_int

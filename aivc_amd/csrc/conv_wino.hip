@@ -3,7 +3,8 @@
 // per 2x2 output pixels and channel pair instead of 36 on the scarce fp32 matrix pipe -- and, on the same kernel, the 5x5
 // stride-2 convolutions (polyphase form) and transposed convolutions (class by class).  What was tried on the way and what it
 // measured: experiments/r06.md (designs), experiments/wino_phases.md (phase offset), experiments/wino5_issue.md (5x5 forms),
-// experiments/wino_class_walk.md (the transposed form's classes dealt round).
+// experiments/wino_class_walk.md (the transposed form's classes dealt round), experiments/wino_dynamic_walk.md (blocks claimed
+// at run time).
 //
 //   work split     a workgroup = a block of 8 x 8 output tiles (16 x 16 pixels) x 64 output channels, 8 waves: (4 x 8 tiles)
 //                  x 32 channels x 8 of the 16 positions each -- 8 accumulator blocks (128 registers) per wave, two waves per
@@ -11,7 +12,8 @@
 //                  v_mfma_f32_32x32x2_f32 steps per position); M_p = a fixed-order fmaf chain over ci per position, as the
 //                  contract says.  After the last chunk a wave folds its 8 positions into the partial sums S0 / S1 of the
 //                  four outputs of every tile, the two waves of a pair exchange halves through LDS and each finishes one
-//                  output row (a = 0 / a = 1) of the tiles.  Persistent workgroups, one per CU, walk the block list.
+//                  output row (a = 0 / a = 1) of the tiles.  Persistent workgroups, one per CU, walk the block list and claim
+//                  their blocks at run time (wino_dynamic_walk.h: a workgroup that starts late takes what is left).
 //   per chunk      raw patch (18 x 18 pixels x 8 channels, 10 KB: replicate-clamped on the global side of the LDS-DMA, stored
 //                  as four parity planes so that the transform's reads are contiguous), fetched ONCE per block and chunk; U
 //                  image (16 positions x 64 channels x 8, 32 KB: aivc_winograd_weights lays it out as it is staged, one
@@ -40,8 +42,12 @@
 //                  multiplied; its V is computed and never read.
 #include <stdlib.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #include "mfma_util.h"
 #include "wino_class_walk.h"
+#include "wino_dynamic_walk.h"
 
 namespace aivc {
 
@@ -61,7 +67,13 @@ constexpr int WINO_U_STAGE = 32 * 1024;    // [16 positions][2 quads][64 channel
 constexpr int WINO_V_QUAD = 1152;          // [64 tiles][4 floats] + 128: the second quad starts 32 banks further
 constexpr int WINO_V_POS = 2 * WINO_V_QUAD;
 constexpr int WINO_V_STAGE = 16 * WINO_V_POS;
-constexpr int WINO_LDS = 2 * (WINO_RAW_STAGE + WINO_U_STAGE + WINO_V_STAGE);
+constexpr int WINO_STAGES = 2 * (WINO_RAW_STAGE + WINO_U_STAGE + WINO_V_STAGE);
+constexpr int WINO_LDS = WINO_STAGES + 16;  // + the word through which the workgroup learns the entry its lane 0 has claimed
+
+// The counters of the block walk (wino_dynamic_walk.h): one slot set per stream that has launched the kernel, all zero between
+// launches (the last workgroup out cleans its set)
+constexpr unsigned WINO_WALK_SETS = 256;
+__device__ uint32_t wino_walk_slots[WINO_WALK_SETS * WINO_WALK_SLOTS];
 
 // 4 KB of zeros: the source of the patch pixels outside the image in the transposed form (zero extension; an LDS-DMA cannot fill)
 __device__ __attribute__((aligned(4096))) float wino_zeros[1024];
@@ -85,23 +97,29 @@ __host__ __device__ constexpr uint32_t wino_pos_mask(int pc, int half) {
   return m;
 }
 
-// The block walk of a persistent workgroup.  The dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (each with
-// a private L2): workgroup b sits on XCD b & 7 and takes blocks of that XCD's contiguous eighth of the block list, interleaved with
-// the other workgroups of the XCD -- they advance through one region together; the channel blocks of a pixel block are neighbours
-// in the list (same raw patch).  Which entries a workgroup takes is decided here; what an entry means is make_desc's business (the
-// transposed form reads it through wino_class_walk.h).
+// The block walk of a persistent workgroup (wino_dynamic_walk.h): workgroup b sits on XCD b & 7 and claims entries of that XCD's
+// contiguous eighth of the block list, one at a time, from the XCD's ticket counter in slot set `set`.  ONE lane of the workgroup
+// claims; the others learn the entry through the LDS word claim_lds.  Which entries a workgroup takes is decided here; what
+// an entry means is make_desc's business (the transposed form reads it through wino_class_walk.h).
 struct WinoWalk {
-  uint32_t x_lo, x_hi, slot, wg_per_xcd;  // this XCD's part of the list, this workgroup's place among the XCD's workgroups
-  __device__ __forceinline__ WinoWalk(uint32_t total, uint32_t nwg, uint32_t wg) {
-    const uint32_t xcd = wg & 7u;
-    slot = wg >> 3;
-    const uint32_t per_xcd = (total + 7u) >> 3;
-    wg_per_xcd = (nwg + 7u - xcd) >> 3;  // workgroups on this XCD
-    x_lo = xcd * per_xcd;
-    x_hi = min(x_lo + per_xcd, total);
+  // (the XCD's range and its counter are worked out at every claim, once per block: nothing of them is kept in registers across
+  // the chunk loop)
+  uint32_t total, set;
+  __device__ __forceinline__ uint32_t claim() const {  // (one lane)
+    const uint32_t xcd = blockIdx.x & 7u;
+    uint32_t *ticket = wino_walk_slots + set * WINO_WALK_SLOTS + xcd;
+    return wino_ticket_entry(wino_xcd_range(total, xcd), __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   }
-  __device__ __forceinline__ uint32_t block_of(uint32_t k) const { return x_lo + slot + k * wg_per_xcd; }  // k-th block of this workgroup
-  __device__ __forceinline__ uint32_t count() const { return x_lo + slot < x_hi ? (x_hi - x_lo - slot + wg_per_xcd - 1u) / wg_per_xcd : 0u; }
+  // one lane, after the workgroup's last claim has returned: count the workgroup out; the last one of the launch zeroes the set.
+  // Every other workgroup's claims returned before it counted itself out, so nothing is added behind the zeroes, and the end of
+  // the kernel orders them before the next launch on the stream
+  __device__ __forceinline__ void leave() const {
+    uint32_t *set0 = wino_walk_slots + set * WINO_WALK_SLOTS;
+    if (wino_last_out(__hip_atomic_fetch_add(set0 + WINO_WALK_EXIT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), gridDim.x)) {
+#pragma unroll
+      for (uint32_t i = 0; i <= WINO_WALK_EXIT; ++i) __hip_atomic_store(set0 + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 };
 
 // MODE 0: stride-1 3x3.  MODE 1 (POLY): the polyphase form of the 5x5 stride-2 convolutions.  MODE 2 (TC): the 5x5 stride-2
@@ -110,7 +128,7 @@ struct WinoWalk {
 // (pyc, pxc) land on pixels (2 y + pyc, 2 x + pxc).
 // Separate instantiations: the stride-1 3x3 kernel pays nothing for the others.
 template <int MODE>
-__global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
+__global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a, uint32_t walk_set) {
   constexpr bool POLY = MODE == 1, TC = MODE == 2;
   extern __shared__ __attribute__((aligned(16))) char wsmem[];
   char *raw = wsmem, *Us = wsmem + 2 * WINO_RAW_STAGE, *Vs = Us + 2 * WINO_U_STAGE;
@@ -129,9 +147,21 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   const int cpp_shift = a.cpp_shift, cpp_mask = (1 << a.cpp_shift) - 1;
 
   // ---- block walk: persistent workgroups (gridDim.x of them: one per CU, or one per block of a short list) ------------------
-  const WinoWalk walk((uint32_t)a.total, gridDim.x, blockIdx.x);
-  const uint32_t n_mine = walk.count();
-  if (n_mine == 0u) return;
+  // Lane 0 of wave 0 claims the first block here and, in the first chunk of every block, the next one: a workgroup never holds
+  // more than ONE block it has not started (with two, the workgroups that come first would take a list of about two blocks per CU
+  // between them, and every launch would end on up to two blocks of imbalance instead of one).  The loader wants the next block
+  // from chunk nch - 2 >= 2 on, so nxt is made behind chunk 1.  blk_nxt == WINO_WALK_END: the block being computed is the
+  // workgroup's last
+  const WinoWalk walk = {(uint32_t)a.total, walk_set};
+  volatile uint32_t *claim_lds = reinterpret_cast<volatile uint32_t *>(wsmem + WINO_STAGES);
+  if (tid == 0) claim_lds[0] = walk.claim();
+  __syncthreads();
+  const uint32_t blk_cur = __builtin_amdgcn_readfirstlane(claim_lds[0]);
+  uint32_t blk_nxt = WINO_WALK_END;
+  if (blk_cur == WINO_WALK_END) {  // (a workgroup that started late, or an empty range)
+    if (tid == 0) walk.leave();
+    return;
+  }
   // descriptor of a block: what the loader needs (image base, chunk images of its channel block, per-lane patch offsets) and
   // what the epilogue needs (coordinates)
   struct Desc {
@@ -203,7 +233,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       iss_addr[k] = in ? a_in : a_z;
     }
   };
-  Desc cur = make_desc(walk.block_of(0)), nxt = n_mine > 1u ? make_desc(walk.block_of(1)) : cur;
+  Desc cur = make_desc(blk_cur), nxt = cur;
 
   const uint32_t r_dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)wave * 1024u);
   const uint32_t u_dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(2 * WINO_RAW_STAGE) + (uint32_t)wave * 4096u);
@@ -245,8 +275,8 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     else if (hi) glds_piece<GLDS_HI>(src, u_off, d);
   };
 
-  // polyphase form: the issue of a chunk in two parts.  prepare(kb, cr, cu), run by every wave at the chunk head, does everything
-  // of the issue of raw chunk cr and U chunk cu (of this workgroup's block kb, possibly beyond its chunks: the next block's first
+  // polyphase form: the issue of a chunk in two parts.  prepare(cr, cu), run by every wave at the chunk head, does everything
+  // of the issue of raw chunk cr and U chunk cu (of this workgroup's current block, possibly beyond its chunks: the next block's first
   // ones) that is no DMA instruction: cur or nxt, the per-lane patch offsets on phase entry, the wave-uniform sources, which
   // pieces are issued.  fire_raw / fire_u hold the DMA instructions alone, under their guards (the LDS stage is the caller's
   // compile-time constant), so that placing them by position half costs no second copy of the address arithmetic.
@@ -254,9 +284,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
     const float *r_src, *u_src;  // wave-uniform sources: the raw chunk, the U chunk image
     uint32_t flags;              // 1: the raw chunk is issued; 2 / 4: the lo / hi pieces of the U image are
   };
-  auto prepare = [&](uint32_t kb, int cr, int cu) -> Prep {
+  auto prepare = [&](int cr, int cu) -> Prep {
     Prep q;
-    const bool more = kb + 1u < n_mine;
+    const bool more = blk_nxt != WINO_WALK_END;
     uint32_t fl = 0u;
     {
       const bool own = cr < nch;
@@ -471,23 +501,23 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   // ---- the reduction, pipelined ACROSS blocks: chunk indices run on through the workgroup's blocks (c_in / 8 is even, so
   // the stage parity of a chunk is its index inside its block) -------------------------------------------------------------
   // (stride-1 and transposed forms; the polyphase form's prepare() does the same choice of cur / nxt)
-  auto issue_raw_at = [&](uint32_t kb, int c) {  // chunk c of this workgroup's block kb, c possibly beyond the block's chunks
+  auto issue_raw_at = [&](int c) {  // chunk c of this workgroup's current block, c possibly beyond the block's chunks
     if (c < nch) issue_raw(cur, c);
-    else if (kb + 1u < n_mine) issue_raw(nxt, c - nch);
+    else if (blk_nxt != WINO_WALK_END) issue_raw(nxt, c - nch);
   };
-  auto issue_u_at = [&](uint32_t kb, int c) {
+  auto issue_u_at = [&](int c) {
     if (c < nch) issue_u(cur, c);
-    else if (kb + 1u < n_mine) issue_u(nxt, c - nch);
+    else if (blk_nxt != WINO_WALK_END) issue_u(nxt, c - nch);
   };
   if constexpr (POLY) {
-    const Prep q0 = prepare(0u, 0, 0);
+    const Prep q0 = prepare(0, 0);
     fire_raw(std::integral_constant<int, 0>{}, q0);
     fire_u(std::integral_constant<int, 0>{}, q0);
-    fire_raw(std::integral_constant<int, 1>{}, prepare(0u, 1, 0));
+    fire_raw(std::integral_constant<int, 1>{}, prepare(1, 0));
   } else {
     issue_raw(cur, 0);
     issue_u(cur, 0);
-    issue_raw_at(0u, 1);
+    issue_raw_at(1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -495,21 +525,21 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   const int act1 = p.act1, act2 = p.act2;
-  for (uint32_t kb = 0; kb < n_mine; ++kb) {
+  for (;;) {
     // two chunks per trip (stage parities 0, 1: compile-time LDS offsets); the block's first chunk starts the accumulators
     auto chunk = [&](auto STAGE, auto FIRST, int c) {
       // here: V(c) complete, U(c) and raw(c + 1) in LDS; raw stage c & 1, U stage (c + 1) & 1 and V stage (c + 1) & 1 are free
       // (chunks beyond this block's are the first ones of the next block): the DMA targets are free from here to the closing
       // s_waitcnt + barrier, wherever in the chunk a wave issues them.  The transform of chunk c + 1 rides along
       Prep q;
-      if constexpr (POLY) q = prepare(kb, c + 2, c + 1);  // every wave, here: fire() is placed by position half
+      if constexpr (POLY) q = prepare(c + 2, c + 1);  // every wave, here: fire() is placed by position half
       auto dma = [&]() {
         if constexpr (POLY) {
           fire_raw(STAGE, q);  // raw(c + 2) -> raw stage c & 1, U(c + 1) -> the other U stage
           fire_u(std::integral_constant<int, 1 - decltype(STAGE)::value>{}, q);
         } else {
-          issue_raw_at(kb, c + 2);
-          issue_u_at(kb, c + 1);
+          issue_raw_at(c + 2);
+          issue_u_at(c + 1);
         }
       };
       // pm: the positions of this wave's half that the chunk's phase / the block's class issues (wino_zero_pos).  Bit 0 of pc
@@ -532,8 +562,19 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       using std::integral_constant;
       using S0 = integral_constant<int, 0>;
       using S1 = integral_constant<int, 1>;
+      // the claim of the next block rides in the block's first chunk: asked for at its head, in hand when the chunk's closing
+      // s_waitcnt has run, published behind its barrier (every wave has read the previous one by then), read behind the
+      // second chunk's barrier.  (Chunks 0 and 1 issue raw chunks 2, 3 and U chunks 1, 2 of THIS block: nch >= 4.)  Nothing of
+      // it stands inside a chunk: with the publication and make_desc at the chunks' ends, under the last pair's MFMAs, or with
+      // the workgroup's first block its own without a claim, the compiler moved the 2-chunk loop and every launch was slower
+      // (experiments/wino_dynamic_walk.md)
+      uint32_t ahead = WINO_WALK_END;
+      if (tid == 0) ahead = walk.claim();
       chunk(S0{}, std::true_type{}, 0);
+      if (tid == 0) claim_lds[0] = ahead;
       chunk(S1{}, std::false_type{}, 1);
+      blk_nxt = __builtin_amdgcn_readfirstlane(claim_lds[0]);
+      if (blk_nxt != WINO_WALK_END) nxt = make_desc(blk_nxt);
       for (int c = 2; c < nch; c += 2) {
         chunk(S0{}, std::false_type{}, c);
         chunk(S1{}, std::false_type{}, c + 1);
@@ -710,9 +751,10 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(WinoArgs a) {
       }
     epilogue_done:;
     }
+    if (blk_nxt == WINO_WALK_END) break;
     cur = nxt;
-    if (kb + 2u < n_mine) nxt = make_desc(walk.block_of(kb + 2u));
   }
+  if (tid == 0) walk.leave();
 }
 
 // U = G g G^T per (c_out, c_in), fp64 in the order of include/aivc_hip.h, rounded once
@@ -816,11 +858,39 @@ bool conv2d_wino_supported(const aivc_conv_params &p) {
 
 int conv2d_wino_variant(const aivc_conv_params &p) { return p.mode == AIVC_MODE_TCONV ? 303 : (p.ksize == 5 ? 302 : 301); }
 
+// The slot set of stream s: launches on one stream run one after the other and share a set (each leaves it zeroed), launches on
+// different streams may run at the same time and get different ones.  The sets are zero from the load of the module on, so a
+// launch costs no memset and no synchronisation.  When all sets are taken, the set of a stream that has nothing pending (or no
+// longer exists) changes hands; -1: WINO_WALK_SETS streams all have work in flight
+static int wino_walk_set(hipStream_t s) {
+  static std::mutex mu;
+  static std::unordered_map<hipStream_t, unsigned> set_of;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto it = set_of.find(s);
+  if (it != set_of.end()) return (int)it->second;
+  unsigned set = (unsigned)set_of.size();
+  if (set >= WINO_WALK_SETS) {
+    auto idle = set_of.begin();
+    while (idle != set_of.end() && hipStreamQuery(idle->first) == hipErrorNotReady) ++idle;
+    (void)hipGetLastError();  // (a destroyed stream's error is not this launch's)
+    if (idle == set_of.end()) return -1;
+    set = idle->second;
+    set_of.erase(idle);
+  }
+  set_of.emplace(s, set);
+  return (int)set;
+}
+
 template <int MODE>
 static int wino_launch(const WinoArgs &a, unsigned grid, hipStream_t s) {
   static LdsOptIn opt_in;
   if (!opt_in.raise(reinterpret_cast<const void *>(conv_wino_kernel<MODE>), WINO_LDS)) return check_launch("conv_wino lds attribute");
-  hipLaunchKernelGGL(conv_wino_kernel<MODE>, dim3(grid), dim3(512), WINO_LDS, s, a);
+  const int set = wino_walk_set(s);
+  if (set < 0) {
+    set_last_error("conv_wino: more streams with launches in flight than block-walk slot sets");
+    return AIVC_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(conv_wino_kernel<MODE>, dim3(grid), dim3(512), WINO_LDS, s, a, (uint32_t)set);
   return check_launch("conv_wino");
 }
 

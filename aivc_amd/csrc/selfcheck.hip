@@ -1,8 +1,10 @@
 // selfcheck.hip -- device-side check of the lean square root / division of the fused GDN epilogues (common.h) against
 // the compiler's full IEEE sequences, and the element-by-element evaluator of the deterministic transcendentals
-// (include/aivc_detmath.h) whose device bits the tests compare with the host's.  Diagnostic entry points: nothing on the
-// coded path calls them.
+// (include/aivc_detmath.h) whose device bits the tests compare with the host's, and a workgroup that holds LDS for a bounded
+// time (include/aivc_hip_diag.h).  Diagnostic entry points: nothing on the coded path calls them.
 #include "common.h"
+
+#include "../../include/aivc_hip_diag.h"
 
 namespace aivc {
 
@@ -102,4 +104,27 @@ AIVC_EXPORT int aivc_detmath_eval(int32_t fn, const void *a, const void *b, size
     hipLaunchKernelGGL(aivc::detmath_eval_kernel<float>, dim3(blocks), dim3(256), 0, s, (int)fn, static_cast<const float *>(a),
                        static_cast<const float *>(b), n, static_cast<float *>(out));
   return aivc::check_launch("detmath_eval");
+}
+
+namespace aivc {
+
+// one workgroup, `words` uint32 of LDS: held[i] = i, then every lane follows held[] for `iterations` dependent reads (each index
+// is reduced below `words` before it is used)
+__global__ __launch_bounds__(64) void hold_lds_kernel(uint32_t words, uint32_t iterations, uint32_t *__restrict__ out) {
+  extern __shared__ uint32_t held[];
+  for (uint32_t i = threadIdx.x; i < words; i += 64u) held[i] = i;
+  __syncthreads();
+  uint32_t at = threadIdx.x % words;
+  for (uint32_t k = 0; k < iterations; ++k) at = (held[at] * 2654435761u + k) % words;
+  out[threadIdx.x] = at;
+}
+
+}  // namespace aivc
+
+AIVC_EXPORT int aivc_diag_hold_lds(uint32_t lds_bytes, uint32_t iterations, uint32_t *out, aivc_stream_t stream) {
+  if (!out || lds_bytes < 256u || lds_bytes > 160u * 1024u || (lds_bytes & 3u) || iterations < 1u || iterations > (1u << 20)) return AIVC_ERR_ARG;
+  static aivc::LdsOptIn opt_in;
+  if (!opt_in.raise(reinterpret_cast<const void *>(aivc::hold_lds_kernel), 160u * 1024u)) return aivc::check_launch("diag_hold_lds lds attribute");
+  hipLaunchKernelGGL(aivc::hold_lds_kernel, dim3(1), dim3(64), lds_bytes, aivc::to_stream(stream), lds_bytes / 4u, iterations, out);
+  return aivc::check_launch("diag_hold_lds");
 }

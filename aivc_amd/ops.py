@@ -334,6 +334,15 @@ def selfcheck_gdn_math(n_div_pairs=1 << 34, seed=1, device=None):
     return tuple(int(v) for v in out.cpu())
 
 
+def diag_hold_lds(lds_bytes, iterations, out=None):
+    """one workgroup that holds lds_bytes of LDS on the current stream for `iterations` dependent LDS reads
+    (aivc_diag_hold_lds, a diagnostic for the tests and tools of the persistent kernels) -> the 64 chain ends, int32"""
+    if out is None:
+        out = torch.empty(64, dtype=torch.int32, device=torch.device('cuda'))
+    call('aivc_diag_hold_lds', int(lds_bytes), int(iterations), _p(out), _stream())
+    return out
+
+
 def detmath_eval(fn, a, b=None):
     """out[i] = fn(a[i]) or fn(a[i], b[i]) for one function of include/aivc_detmath.h on the device (aivc_detmath_eval, a
     diagnostic): fn one of abi.DETMATH_*, a / b / out float64 for the fp64 cores and float32 for everything else"""

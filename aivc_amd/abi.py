@@ -1,5 +1,5 @@
 """ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h,
-include/aivc_hip_rates.h and include/aivc_hip_digest.h (struct layouts, constants, prototypes).
+include/aivc_hip_rates.h, include/aivc_hip_digest.h and include/aivc_hip_scene.h (struct layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -7,7 +7,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -28,6 +28,7 @@ MAX_MAPS = 256
 RC_MAX_STREAMS = 64
 RATE_LANES = 16384
 SSE_BLOCKS = 64  # include/aivc_hip_quality.h: AIVC_SSE_BLOCKS
+SAD_BLOCKS = 128  # include/aivc_hip_scene.h: AIVC_SAD_BLOCKS
 WINO_MIN_PIXELS = 8000  # include/aivc_hip.h: AIVC_WINO_MIN_PIXELS
 WINO_MIN_PIXELS_TCONV = 32768  # ... AIVC_WINO_MIN_PIXELS_TCONV
 
@@ -200,6 +201,11 @@ DIGEST_PROTOTYPES = {
     'aivc_md5_batch': [_f, C.c_int64, _i32, _f],
 }
 
+# include/aivc_hip_scene.h: device only (its statement is numpy: tests/test_gpu_pair_sad.py)
+SCENE_PROTOTYPES = {
+    'aivc_pair_sad_u8': [_f, _i32, C.c_int64, _f, _f],
+}
+
 
 def declare(lib, suffix=''):
     """Attach argtypes/restype for every entry of the header; raises AttributeError when the
@@ -232,7 +238,7 @@ def declare(lib, suffix=''):
         wm.restype = C.c_int
         fns['aivc_warp_modes'] = wm
         for name, args in list(COLOR_PROTOTYPES.items()) + list(QUALITY_PROTOTYPES.items()) + list(RATES_PROTOTYPES.items()) \
-                + list(DIGEST_PROTOTYPES.items()):
+                + list(DIGEST_PROTOTYPES.items()) + list(SCENE_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.argtypes = list(args) + [C.c_void_p]
             fn.restype = C.c_int

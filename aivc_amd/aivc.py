@@ -45,8 +45,10 @@ def parse_args(argv=None):
     from aivc_amd.cli_common import add_contract_flag
     add_contract_flag(p, ('fp32', 'fp32w', 'auto'))
     enc_cli.add_rate_flags(p)
+    enc_cli.add_scene_flag(p)
     a = p.parse_args(argv)
     enc_cli.check_rate_flags(p, a)
+    enc_cli.check_scene_flag(p, a)
     return a
 
 
@@ -64,6 +66,7 @@ def main(argv=None):
                  + (['--idx_rate', str(a.idx_rate)] if a.idx_rate is not None else [])
                  + (['--target_bpp', str(a.target_bpp)] if a.target_bpp > 0 else [])
                  + (['--digests'] if a.digests else [])
+                 + (['--scene_cut', repr(a.scene_cut)] if a.scene_cut is not None else [])
                  + (['--contract', a.contract] if a.contract not in (None, 'auto') else []))  # (auto is the decoder's choice)
     banner(('*' * 80).center(120))
     banner('Starting decoding'.center(120))

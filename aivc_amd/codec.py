@@ -6,12 +6,11 @@ device->host CDF copies.  Frames are dicts {'y','u','v'} of uint8 CUDA planes [1
 references are exact: the reference casts every reconstruction to 8-bit levels, decode.py:575).
 """
 import contextlib
-import math
 import os as _os
 
 import torch
 
-from . import abi, ops, partial, rate_control
+from . import abi, ops, partial, rate_control, scene
 from .func_util.GOP_structure import FRAME_B, FRAME_I, FRAME_P, coding_levels, generate_gop_struct
 from .real_life import cat_binary_files as container
 from .real_life import header as hdr
@@ -462,7 +461,13 @@ class FrameCodec:
         ranks of this process' group; each rank codes `shard.mine(items)` and the new 8-bit reconstructions are
         exchanged once per level (they are the references of the next levels).  Stream scheduling is the
         single-GPU one; the frame bitstreams are gathered once, at the end.  Every rank of the group returns
-        the same blobs -- identical to a single-process run."""
+        the same blobs -- identical to a single-process run.
+        gop_name: one structure for all units, or a list with one name per unit (aivc_amd.scene.plan_units: the units around
+        a scene cut): the units are grouped by structure as _decode_units_gen groups them, each group runs the level loop
+        below on its own (levels of different groups are not merged), and every unit has the bytes it has when coded alone
+        under its structure.  Unit-wise coding only: ValueError with a shard."""
+        if not isinstance(gop_name, str):
+            return self._encode_units_by_structure(units, list(gop_name), idx_rate, shard, recon, stats, stats_units)
         gop = generate_gop_struct(gop_name)
         names = sorted(gop, key=frame_index)
         rec = [dict() for _ in units]
@@ -557,6 +562,31 @@ class FrameCodec:
         heads = [hdr.gop_header_bytes(gop_name, idx_rate if unit_rates is None else unit_rates[u]) for u in range(len(units))]
         blobs = [container.pack_gop(heads[u], [fbytes[u][f] for f in names]) for u in range(len(units))]
         return blobs, [[rec[u][f] for f in names] for u in range(len(units))], data_dim
+
+    def _encode_units_by_structure(self, units, names, idx_rate, shard, recon, stats, stats_units):
+        """encode_units with one structure name per unit: one call of the single-structure path per name, in order of first use"""
+        if shard is not None:
+            raise ValueError('one structure per unit is an option of unit-wise coding (the level-sharded paths spread a unit '
+                             'over ranks)')
+        if len(names) != len(units):
+            raise ValueError('%d structure names for %d units' % (len(names), len(units)))
+        per_unit = rate_control.is_rate_list(idx_rate)
+        if per_unit:
+            if len(idx_rate) != len(units):
+                raise ValueError('%d rate indices for %d units' % (len(idx_rate), len(units)))
+            idx_rate = rate_control.check_unit_rates(idx_rate, rate_control.nb_rates_of(self))
+        stats_units = list(range(len(units))) if stats_units is None else list(stats_units)
+        groups = {}
+        for u, name in enumerate(names):
+            groups.setdefault(name, []).append(u)
+        blobs, recs, data_dim = [None] * len(units), [None] * len(units), None
+        for name, members in groups.items():
+            b, r, data_dim = self.encode_units([units[u] for u in members], name,
+                                               [idx_rate[u] for u in members] if per_unit else idx_rate, recon=recon,
+                                               stats=stats, stats_units=[stats_units[u] for u in members])
+            for u, bu, ru in zip(members, b, r):
+                blobs[u], recs[u] = bu, ru
+        return blobs, recs, data_dim
 
     def decode_units(self, gop_blobs, data_dim, device=None, shard=None, wanted=None):
         """-> [reconstructions (display order) per unit]; see _decode_units_gen."""
@@ -718,31 +748,40 @@ class FrameCodec:
 
     # ------------------------------------------------------------------------------------------
     def encode_video(self, frames, gop_name, idx_starting_frame=0, idx_end_frame=None, idx_rate=0.,
-                     unit_filter=None, recon='all', stats=None):
+                     unit_filter=None, recon='all', stats=None, layout=None):
         """frames[i] is the frame with absolute index idx_starting_frame + i.  The last intra-period
         unit is padded by repeating the last frame (src/model_mngt/model_management.py:142-153).
         unit_filter(u) -> bool selects the units this process codes (multi-GPU sharding); skipped
         units come back as None in the returned list of GOP blobs.
         stats: see encode_units; the rows are recorded under (unit number in the video, display index in the unit).
         idx_rate: a scalar, or one rate per unit of the VIDEO (indexed by the unit's number whatever unit_filter selects;
-        the entries of units filtered out are not looked at)."""
+        the entries of units filtered out are not looked at).
+        layout (aivc_amd.scene.UnitLayout, optional): the units of the video, each with its own structure (scene cuts);
+        default: ceil(n / unit) units of gop_name.  unit_filter, idx_rate lists and the stats rows index ITS units; the layout
+        in use comes back as 'layout'."""
         n = len(frames)
         idx_end_frame = idx_starting_frame + n - 1 if idx_end_frame is None else idx_end_frame
-        unit = len(generate_gop_struct(gop_name))
-        nb_gop = math.ceil(n / unit)
+        uniform = layout is None
+        if uniform:
+            layout = scene.plan_units(n, (), gop_name)
+        elif layout.n_frames != n:
+            raise ValueError('a layout of %d frames for a video of %d' % (layout.n_frames, n))
+        nb_gop = len(layout.names)
         mine = [u for u in range(nb_gop) if unit_filter is None or unit_filter(u)]
         gops, recs, data_dim = [None] * nb_gop, [None] * nb_gop, None
         if mine:
-            units = [[frames[min(u * unit + i, n - 1)] for i in range(unit)] for u in mine]
+            every = layout.units(frames)
+            units = [every[u] for u in mine]
             if rate_control.is_rate_list(idx_rate):
                 if len(idx_rate) != nb_gop:
                     raise ValueError('%d rate indices for the %d units of the video' % (len(idx_rate), nb_gop))
                 idx_rate = rate_control.check_unit_rates([idx_rate[u] for u in mine], rate_control.nb_rates_of(self), mine)
-            blobs, rr, data_dim = self.encode_units(units, gop_name, idx_rate, recon=recon, stats=stats, stats_units=mine)
+            blobs, rr, data_dim = self.encode_units(units, gop_name if uniform else [layout.names[u] for u in mine], idx_rate,
+                                                    recon=recon, stats=stats, stats_units=mine)
             for u, b, r in zip(mine, blobs, rr):
                 gops[u], recs[u] = b, r
         return {'gops': gops, 'recs': recs, 'data_dim': data_dim, 'nb_gop': nb_gop,
-                'idx_starting_frame': idx_starting_frame, 'idx_end_frame': idx_end_frame}
+                'idx_starting_frame': idx_starting_frame, 'idx_end_frame': idx_end_frame, 'layout': layout}
 
     @staticmethod
     def assemble_video(enc):

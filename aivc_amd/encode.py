@@ -32,6 +32,20 @@ def check_rate_flags(p, a):
     return 0 if a.idx_rate is None else a.idx_rate
 
 
+def add_scene_flag(p):
+    """--scene_cut [T] (shared with aivc.py)"""
+    p.add_argument('--scene_cut', nargs='?', const=10.0, default=None, type=float, metavar='T',
+                   help='detect scene cuts on the device and open a new intra-period unit at each: a frame whose mean absolute '
+                        'luma difference to its predecessor stands out over both neighbouring differences by at least T grey '
+                        'levels (default 10, a convention that has not been measured on real material); the units in front of a '
+                        'cut take a shorter coding structure, any decoder of the format reads the stream; off by default')
+
+
+def check_scene_flag(p, a):
+    if a.scene_cut is not None and not a.scene_cut >= 0:
+        p.error('--scene_cut %r: the threshold is a non-negative number of grey levels' % a.scene_cut)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--gop', default='1_GOP_32', type=str)
@@ -50,8 +64,10 @@ def parse_args(argv=None):
                         'computed on the device (decode.py --verify checks a decode against it); the bitstream does not change')
     add_contract_flag(p, ('fp32', 'fp32w'))
     add_rate_flags(p)
+    add_scene_flag(p)
     a = p.parse_args(argv)
     a.idx_rate = check_rate_flags(p, a)
+    check_scene_flag(p, a)
     return a
 
 
@@ -66,7 +82,7 @@ def main(argv=None):
         return encode({'model': model, 'sequence_path': a.i, 'GOP_struct': generate_gop_struct(a.gop),
                        'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
                        'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp,
-                       'rate_step': a.rate_step, 'digests': a.digests})
+                       'rate_step': a.rate_step, 'digests': a.digests, 'scene_cut': a.scene_cut})
 
 
 if __name__ == '__main__':

@@ -105,15 +105,21 @@ def sequence_result_from_rows(rows, nb_gop, unit, idx_starting_frame, nb_frames,
     sequence_result: {'frame_<index in the video>': result dictionary, ..., 'sequence': their average}, the frames in display
     order; the frames past nb_frames are the padding of the last unit (rate counts, distortion does not).
     lambda_tradeoff: one number, or one per unit (units coded at different rate indices: the loss column of a frame uses its
-    unit's; the sequence row averages the frames' columns, so its loss weighs every frame's rate with that frame's lambda)."""
+    unit's; the sequence row averages the frames' columns, so its loss weighs every frame's rate with that frame's lambda).
+    unit: the frames per unit, or the aivc_amd.scene.UnitLayout of a video whose units differ (scene cuts): a frame is named
+    by its position in the layout, and the padding count is the layout's."""
     from ..func_util.result_logging import average_N_frame, frame_result
+    from ..scene import as_layout
+    layout = as_layout(unit, nb_gop, nb_frames)
+    if len(layout.names) != nb_gop or layout.n_frames != nb_frames:
+        raise ValueError('a layout of %d units and %d frames for %d units and %d frames'
+                         % (len(layout.names), layout.n_frames, nb_gop, nb_frames))
     per_unit = isinstance(lambda_tradeoff, (list, tuple))
     seq = {}
-    for u in range(nb_gop):
-        for i in range(unit):
-            seq['frame_%d' % (u * unit + i + idx_starting_frame)] = frame_result(rows[(u, i)],
-                                                                                lambda_tradeoff[u] if per_unit else lambda_tradeoff)
-    seq['sequence'] = average_N_frame(seq, nb_pad_frame=nb_gop * unit - nb_frames)
+    for u, i in layout.keys():
+        seq['frame_%d' % (layout.position(u, i) + idx_starting_frame)] = frame_result(rows[(u, i)],
+                                                                                     lambda_tradeoff[u] if per_unit else lambda_tradeoff)
+    seq['sequence'] = average_N_frame(seq, nb_pad_frame=layout.padding)
     return seq
 
 

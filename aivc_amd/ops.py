@@ -571,6 +571,37 @@ def md5_planes(planes):
     return out
 
 
+def pair_sad_u8(planes):
+    """Sums of absolute differences between consecutive planes (include/aivc_hip_scene.h): the scene-cut detector's input.
+    planes: a list of n contiguous uint8 CUDA tensors of one size (the luma planes of a clip as read_yuv leaves them: separate
+    tensors, any alignment).  -> int64 CUDA tensor [max(n - 1, 0)], entry i the exact sum of |planes[i + 1] - planes[i]|.
+    No synchronisation: the pointer table is one small host-to-device copy, the two launches go on the current stream.
+    n <= 1 launches nothing."""
+    if not isinstance(planes, (list, tuple)):
+        raise ValueError('pair_sad_u8: expected a list of planes, got %s' % type(planes).__name__)
+    planes = [_dev(t, torch.uint8, 'planes[%d]' % i) for i, t in enumerate(planes)]
+    n = len(planes)
+    length = planes[0].numel() if n else 0
+    if any(t.numel() != length for t in planes):
+        raise ValueError('pair_sad_u8: the planes of one call have one size, got %s' % sorted({t.numel() for t in planes}))
+    if len({t.device for t in planes}) > 1:
+        raise ValueError('pair_sad_u8: planes on several devices')
+    device = planes[0].device if n else torch.device('cuda', torch.cuda.current_device())
+    sad = torch.empty((max(n - 1, 0),), dtype=torch.int64, device=device)
+    if n <= 1:
+        return sad
+    if length == 0:
+        raise ValueError('pair_sad_u8: empty planes')
+    host = _pinned_staging(8 * n)  # (pinned staging and an asynchronous copy, as md5_planes)
+    host.numpy().view(np.uint64)[:] = np.asarray([t.data_ptr() for t in planes], np.uint64)
+    table = torch.empty(8 * n, dtype=torch.uint8, device=device)
+    table.copy_(host, non_blocking=True)
+    _pinned_release(host)
+    partials = torch.empty((n - 1, abi.SAD_BLOCKS), dtype=torch.int64, device=device)
+    _hbm_profiled('pair_sad_u8', n * length, lambda: call('aivc_pair_sad_u8', _p(table), n, length, _p(partials), _p(sad), _stream()))
+    return sad
+
+
 def downsample2x(x, ch0, nch):
     """NHWC x -> planar [n, nch, h//2, w//2] 2x2 means of channels ch0..ch0+nch-1 (OutputLayer)."""
     x = _dev(x, torch.float32, 'x')

@@ -146,14 +146,19 @@ def gather_gops(local_gops, dst=0, device=None):
     return [allb[u] for u in keys]
 
 
-def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, idx_rate=0., return_enc=False, stats=None):
+def encode_video_sharded(frame_codec, frames, gop_name, idx_starting_frame=0, idx_rate=0., return_enc=False, stats=None,
+                         layout=None):
     """Every rank passes the same `frames`; returns the full bitstream on rank 0 (None elsewhere); with return_enc also
     this rank's encode_video record (its units' reconstructions, None for the others').
     idx_rate: a scalar, or one rate per unit of the video (FrameCodec.encode_video); every rank passes the same list.
     stats (aivc_amd.quality.QualityStats): every rank scores the frames of ITS units into its own collector
-    (FrameCodec.encode_units); gather_quality_rows brings the rows together."""
+    (FrameCodec.encode_units); gather_quality_rows brings the rows together.
+    layout (aivc_amd.scene.UnitLayout): the units of the video where they differ (scene cuts); every rank passes the same one
+    -- it is integer arithmetic on sums every rank computes itself -- and unit_owner deals ITS units."""
     rank, world = rank_world()
     extra = {} if stats is None else {'stats': stats}  # (any object with FrameCodec's encode_video will do without a log)
+    if layout is not None:
+        extra['layout'] = layout
     enc = frame_codec.encode_video(frames, gop_name, idx_starting_frame, idx_rate=idx_rate,
                                    unit_filter=lambda u: unit_owner(u, world) == rank, **extra)
     dev = getattr(frames[0]['y'], 'device', None)

@@ -135,13 +135,18 @@ def unit_budgets(target_bpp, w, h, nb_frames, unit):
     return [int(math.floor(target_bpp * w * h * min(unit, nb_frames - u * unit) / 8)) for u in range(nb_gop)]
 
 
+def layout_budgets(target_bpp, w, h, layout):
+    """unit_budgets for the units of an aivc_amd.scene.UnitLayout: floor(target_bpp * w * h * real[u] / 8) bytes for unit u"""
+    return [int(math.floor(target_bpp * w * h * r / 8)) for r in layout.real]
+
+
 def nb_rates_of(frame_codec):
     """rate indices of the codec's model (the gain matrices of both networks have the same number)"""
     return len(frame_codec.cod.gain_I.enc_gain_list)
 
 
 def encode_video_budgeted(frame_codec, frames, gop_name, budgets_or_bpp, step=1 / 16, idx_starting_frame=0, stats=None,
-                          unit_filter=None):
+                          unit_filter=None, layout=None):
     """FrameCodec.encode_video with the rate index of every intra-period unit chosen by search_rates so that the unit's GOP
     blob -- len(gops[u]): GOP header and frame length prefixes included, the 18-byte video header not -- fits its budget.
     budgets_or_bpp: a list of bytes per unit of the video, or a number: a target in bit per pixel (unit_budgets).
@@ -150,28 +155,35 @@ def encode_video_budgeted(frame_codec, frames, gop_name, budgets_or_bpp, step=1 
     returned video; its blobs are the bytes the probes priced.  unit_filter: as in encode_video (each rank of a unit-sharded
     job searches its own units; a unit's result does not depend on the others).
     -> encode_video's dict + 'rates' ([rate per unit], None for units filtered out), 'choices' ([UnitChoice or None]) and
-    'budgets'."""
-    from .func_util.GOP_structure import generate_gop_struct
+    'budgets'.
+    layout (aivc_amd.scene.UnitLayout, optional): the units of the video where they are not ceil(n / unit) units of gop_name
+    (scene cuts); budgets, probes and the final pass all speak of ITS units, a target in bit per pixel weighs unit u with its
+    real[u] frames."""
+    from . import scene
     n = len(frames)
-    unit = len(generate_gop_struct(gop_name))
-    nb_gop = int(math.ceil(n / unit))
+    uniform = layout is None
+    if uniform:
+        layout = scene.plan_units(n, (), gop_name)
+    nb_gop = len(layout.names)
     h, w = frames[0]['y'].shape[-2:]
     if isinstance(budgets_or_bpp, (list, tuple)):
         budgets = [int(b) for b in budgets_or_bpp]
         if len(budgets) != nb_gop:
             raise ValueError('%d budgets for the %d units of the video' % (len(budgets), nb_gop))
     else:
-        budgets = unit_budgets(float(budgets_or_bpp), w, h, n, unit)
+        budgets = layout_budgets(float(budgets_or_bpp), w, h, layout)
     grid = rate_grid(nb_rates_of(frame_codec), step)
     mine = [u for u in range(nb_gop) if unit_filter is None or unit_filter(u)]
-    units = [[frames[min(u * unit + i, n - 1)] for i in range(unit)] for u in mine]
+    every = layout.units(frames)
+    units = [every[u] for u in mine]
+    names = gop_name if uniform else [layout.names[u] for u in mine]
     priced = {}  # (local unit, rate) -> the blob a probe priced
 
     def probe(pairs):
         # (the codec's running rate log -- estimated bits against bytes written -- speaks of the stream that is kept)
         log = {k: getattr(frame_codec, k) for k in ('estimated_bits', 'coded_payload_bytes') if hasattr(frame_codec, k)}
-        blobs, _, _ = frame_codec.encode_units([units[k] for k, _ in pairs], gop_name, idx_rate=[r for _, r in pairs],
-                                               recon='refs')
+        blobs, _, _ = frame_codec.encode_units([units[k] for k, _ in pairs], gop_name if uniform else [names[k] for k, _ in pairs],
+                                               idx_rate=[r for _, r in pairs], recon='refs')
         for k in ('estimated_bits', 'coded_payload_bytes'):
             if k in log:
                 setattr(frame_codec, k, log[k])
@@ -185,7 +197,7 @@ def encode_video_budgeted(frame_codec, frames, gop_name, budgets_or_bpp, step=1 
     for u, ch in zip(mine, choices):
         rates[u] = ch.rate
     enc = frame_codec.encode_video(frames, gop_name, idx_starting_frame=idx_starting_frame, idx_rate=rates,
-                                   unit_filter=unit_filter, stats=stats)
+                                   unit_filter=unit_filter, stats=stats, **({} if uniform else {'layout': layout}))
     for k, (u, ch) in enumerate(zip(mine, choices)):
         assert enc['gops'][u] == priced[(k, ch.rate)], 'unit %d: the final pass is not the stream its probe priced' % u
     full = [None] * nb_gop

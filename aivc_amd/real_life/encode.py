@@ -71,10 +71,16 @@ def encode(param):
     gains 'rates'.  Under torch.distributed.run every rank searches the units it codes.
     digests: True -- the sidecar manifest '<final_file>.md5' (aivc_amd/digests.py): the arithmetic contract the encode ran in
     and one MD5 per reconstructed plane, computed on the device where the planes lie (aivc_amd.ops.md5_planes); every rank
-    digests the frames of its units, rank 0 writes the file.  The bitstream is the same with and without it."""
+    digests the frames of its units, rank 0 writes the file.  The bitstream is the same with and without it.
+    scene_cut: None (the default) -- the clip is cut into units by counting, and nothing below runs; a threshold in grey levels
+    -- the sums of absolute differences between consecutive luma planes come from the device (aivc_amd.ops.pair_sad_u8), the
+    frames that stand out over both neighbours by at least the threshold open a new intra-period unit (aivc_amd/scene.py: the
+    units in front of a cut take a shorter structure, which their GOP headers state; any decoder of the format reads the
+    stream), one `[SCENE]` line per cut and an `[INFO] units` line are printed, and the returned dictionary gains 'cuts' and
+    'unit_names'.  Under torch.distributed.run every rank computes the same sums and the same layout."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
-               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False}
+               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False, 'scene_cut': None}
     model = get_value('model', param, default)
     want_digests = get_value('digests', param, default)
     seq = get_value('sequence_path', param, default)
@@ -86,6 +92,7 @@ def encode(param):
     idx_rate = get_value('idx_rate', param, default)
     target_bpp = get_value('target_bpp', param, default)
     rate_step = get_value('rate_step', param, default)
+    scene_cut = get_value('scene_cut', param, default)
     dev = next(model.parameters()).device
     if first > last and last != -1:
         print('ERROR: First frame index bigger than last frame index')
@@ -103,14 +110,20 @@ def encode(param):
         from ..quality import QualityStats
         stats = QualityStats()
     budgeted = None
+    layout, cuts = None, None
+    if scene_cut is not None:
+        layout, cuts = _scene_layout(frames, gop_name, float(scene_cut), first, rank)
+    lay = {} if layout is None else {'layout': layout}
     with torch.no_grad(), bitstream.estimating_rate():  # the reference's in-band rate check (RESULT lines)
         if target_bpp and target_bpp > 0:
-            budgeted = _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev)
+            budgeted = _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev, layout)
             blob, enc, idx_rate = budgeted
         elif world > 1:  # one process per GPU: intra-period units over the ranks, the container on rank 0
-            blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=idx_rate, return_enc=True, stats=stats)
+            blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=idx_rate, return_enc=True, stats=stats,
+                                                      **lay)
         else:
-            enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last, idx_rate=idx_rate, stats=stats)
+            enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last, idx_rate=idx_rate, stats=stats,
+                                  **lay)
             blob = fc.assemble_video(enc)
         n = last - first + 1
         digested = None
@@ -126,17 +139,13 @@ def encode(param):
     # squared error of the frames THIS process reconstructed (all of them on one GPU), summed over the ranks
     se = cnt = 0.0
     mine = []  # (absolute frame index, reconstruction)
-    for u, g in enumerate(enc['recs']):
-        if g is None:
-            continue
-        for i, r in enumerate(g):
-            idx = u * len(g) + i
-            if idx < n:
-                mine.append((first + idx, r))
-                if stats is not None:  # (scored on the device already)
-                    continue
-                se += sum(float(((r[k].float() - frames[idx][k].float()) ** 2).sum()) for k in 'yuv')
-                cnt += sum(frames[idx][k].numel() for k in 'yuv')
+    for idx, r in _own_frames(enc):
+        if idx < n:
+            mine.append((first + idx, r))
+            if stats is not None:  # (scored on the device already)
+                continue
+            se += sum(float(((r[k].float() - frames[idx][k].float()) ** 2).sum()) for k in 'yuv')
+            cnt += sum(frames[idx][k].numel() for k in 'yuv')
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([se, cnt, est_bits, payload], dtype=torch.float64, device=parallel._comm_device(None, dev))
@@ -145,14 +154,12 @@ def encode(param):
     seq_res = None
     if stats is not None:  # every rank scored the frames of its units: the rows travel to rank 0 (to all, in fact)
         from ..model_mngt.model_management import lambda_tradeoff_of, sequence_result_from_rows, write_detailed_log
-        from ..func_util.GOP_structure import generate_gop_struct
-        unit = len(generate_gop_struct(gop_name))
-        keys = [(u, i) for u in range(enc['nb_gop']) for i in range(unit)]
+        keys = enc['layout'].keys()
         rows = parallel.gather_quality_rows(stats.rows(), keys, dev)
         if rank == 0:
             lambdas = [lambda_tradeoff_of(model, r) for r in idx_rate] if isinstance(idx_rate, (list, tuple)) \
                 else lambda_tradeoff_of(model, idx_rate)
-            seq_res = sequence_result_from_rows(rows, enc['nb_gop'], unit, first, n, lambdas)
+            seq_res = sequence_result_from_rows(rows, enc['nb_gop'], enc['layout'], first, n, lambdas)
             name = os.path.basename(os.path.normpath(seq))
             write_detailed_log(working_dir, seq_res, name[:-4] if name.endswith('.yuv') else name)
     if digested is not None:  # 48 bytes per frame travel to rank 0 (to all, in fact), like the quality rows
@@ -211,6 +218,8 @@ def encode(param):
         out.update(ms_ssim_db=avg['ms_ssim_db'], h=avg['h'], w=avg['w'], nb_coded_frames=len(seq_res) - 1)
     if budgeted is not None:
         out['rates'] = list(idx_rate)
+    if layout is not None:
+        out.update(cuts=[first + t for t in cuts], unit_names=list(layout.names))
     return out
 
 
@@ -219,17 +228,35 @@ def _own_frames(enc):
     for u, g in enumerate(enc['recs']):
         if g is not None:
             for i, r in enumerate(g):
-                yield u * len(g) + i, r
+                yield enc['layout'].position(u, i), r
 
 
-def _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev):
+def _scene_layout(frames, gop_name, threshold, first, rank):
+    """The clip's scene cuts and the unit layout they give (aivc_amd/scene.py).  One launch pair over the luma planes and one
+    synchronisation -- the copy of n - 1 sums to the host -- before the encode starts; with 1_GOP_0 every frame is a unit
+    already and nothing is launched.  Rank 0 prints the [SCENE] and [INFO] units lines.  -> (UnitLayout, [cut positions])"""
+    from .. import ops, scene
+    from ..func_util.GOP_structure import generate_gop_struct
+    cuts, sad, npix = [], [], frames[0]['y'].numel()
+    if len(generate_gop_struct(gop_name)) > 1:
+        sad = [int(v) for v in ops.pair_sad_u8([fr['y'] for fr in frames]).cpu()]
+        cuts = scene.scene_cuts(sad, npix, threshold)
+    layout = scene.plan_units(len(frames), cuts, gop_name)
+    if rank == 0:
+        for t, score in zip(cuts, scene.cut_scores(sad, npix, cuts)):
+            print('[SCENE] cut at frame %d: +%.2f over its neighbours' % (first + t, score))
+        print('[INFO] units: %s' % layout.summary())
+    return layout, cuts
+
+
+def _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev, layout=None):
     """encode() under a byte budget per unit: every rank searches and codes the units it owns (a unit's choice depends on
     that unit alone), rank 0 gets the container; the [RATE] / [WARN] lines come from rank 0, for all units.
     -> (bitstream or None, this rank's encode_video record, [rate per unit of the video])"""
     from .. import parallel, rate_control
     mine = (lambda u: parallel.unit_owner(u, world) == rank) if world > 1 else None
     enc = rate_control.encode_video_budgeted(fc, frames, gop_name, target_bpp, step=rate_step, idx_starting_frame=first,
-                                             stats=stats, unit_filter=mine)
+                                             stats=stats, unit_filter=mine, **({} if layout is None else {'layout': layout}))
     report = {u: (ch.rate, ch.nbytes, int(ch.over_budget)) for u, ch in enumerate(enc['choices']) if ch is not None}
     if world > 1:
         import struct

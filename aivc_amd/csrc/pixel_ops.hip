@@ -1,5 +1,5 @@
-// pixel_ops.hip -- HBM-bound frame / latent kernels: 4:2:0 <-> 4:4:4, motion-compensation warp +
-// blend, reconstruction + 8-bit cast, hyper-prior parameter split, gains, (de)quantisation.
+// pixel_ops.hip -- HBM-bound frame kernels: 4:2:0 <-> 4:4:4, motion-compensation warp +
+// blend, reconstruction + 8-bit cast, channel padding (the latent ops: latent.hip).
 // One thread per pixel (channels are innermost, so a pixel's channels sit in one or two
 // cache lines); grids are sized >> 256 CUs for every frame size the codec handles.
 #include "common.h"
@@ -416,64 +416,7 @@ __global__ __launch_bounds__(256) void warp_blend4_kernel(BlendArgs a) {
   if (a.skip) reinterpret_cast<float4 *>(a.skip)[pix] = make_float4(sk[0], sk[1], sk[2], 0.0f);
 }
 
-// ---------------------------------------------------------------- latent ops
-__global__ __launch_bounds__(256) void hyper_params_kernel(const float *__restrict__ hs, int n, int hh, int wh,
-                                                           int c, int h, int w, float *__restrict__ mu,
-                                                           float *__restrict__ sigma) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)n * h * w * c;
-  if (gid >= total) return;
-  const int ch = (int)(gid % c);
-  const size_t pix = gid / c;
-  const int q = (int)(pix % w), r = (int)((pix / w) % h), b = (int)(pix / ((size_t)w * h));
-  const float *src = hs + (((size_t)b * hh + r) * wh + q) * 2 * c;
-  mu[gid] = src[ch];
-  float lv = src[c + ch];
-  lv = lv < -18.4207f ? -18.4207f : lv;
-  lv = lv > 10.0f ? 10.0f : lv;
-  sigma[gid] = aivc_expf_det(0.5f * lv);
-}
-
-__global__ __launch_bounds__(256) void channel_gain_kernel(const float *__restrict__ in, const float *__restrict__ gain,
-                                                           size_t total, int c, float *__restrict__ out) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= total) return;
-  out[gid] = gain ? in[gid] * __builtin_fabsf(gain[gid % c]) : in[gid];
-}
-
-__global__ __launch_bounds__(256) void gain_interp_kernel(const float *__restrict__ g_r, const float *__restrict__ g_t,
-                                                          int c, float l, float *__restrict__ out) {
-  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ch < c) out[ch] = aivc_gain_interp_one(g_r[ch], g_t[ch], l);
-}
-
-__global__ __launch_bounds__(256) void quantize_center_kernel(const float *__restrict__ y, const float *__restrict__ mu,
-                                                              const float *__restrict__ gain, size_t total, int c,
-                                                              int16_t *__restrict__ q, float *__restrict__ y_hat) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= total) return;
-  const float m = mu ? mu[gid] : 0.0f;
-  float r = __builtin_rintf(mu ? y[gid] - m : y[gid]);
-  r = r < -256.0f ? -256.0f : (r > 256.0f ? 256.0f : r);  // the alphabet of the coder: symbols 0 .. 512
-  const float level = r == r ? r : 0.0f;  // in [-256, 256]; a NaN latent: q = 0 (its y_hat stays NaN)
-  if (q) q[gid] = (int16_t)level;
-  if (y_hat) {
-    float v = mu ? r + m : r;
-    if (gain) v = v * __builtin_fabsf(gain[gid % c]);
-    y_hat[gid] = v;
-  }
-}
-
-__global__ __launch_bounds__(256) void dequantize_kernel(const int16_t *__restrict__ q, const float *__restrict__ mu,
-                                                         const float *__restrict__ gain, size_t total, int c,
-                                                         float *__restrict__ y_hat) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= total) return;
-  float v = mu ? (float)q[gid] + mu[gid] : (float)q[gid];
-  if (gain) v = v * __builtin_fabsf(gain[gid % c]);
-  y_hat[gid] = v;
-}
-
+// ---------------------------------------------------------------- channel padding, GDN parameters
 __global__ __launch_bounds__(256) void pad_channels_kernel(const float *__restrict__ in, size_t npix, int c_in,
                                                            float *__restrict__ out, int c_out) {
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -647,46 +590,4 @@ AIVC_EXPORT int aivc_warp_blend(const float *mof, int32_t hm, int32_t wm, int32_
   if (hm < h) return AIVC_ERR_ARG;
   return aivc_warp_blend_rows(mof, hm, wm, cm, prev, next, cr, n, h, w, 0, h, frame_type, pred, skip, x_warp, co,
                               alpha_out, beta_out, stream);
-}
-
-AIVC_EXPORT int aivc_hyper_params(const float *hs, int32_t n, int32_t hh, int32_t wh, int32_t c, int32_t h, int32_t w,
-                                  float *mu, float *sigma, aivc_stream_t stream) {
-  if (!hs || !mu || !sigma || n <= 0 || c <= 0 || h <= 0 || w <= 0 || hh < h || wh < w) return AIVC_ERR_ARG;
-  hipLaunchKernelGGL(hyper_params_kernel, dim3(cdiv((size_t)n * h * w * c, 256)), dim3(256), 0, to_stream(stream), hs,
-                     n, hh, wh, c, h, w, mu, sigma);
-  return check_launch("hyper_params");
-}
-
-AIVC_EXPORT int aivc_channel_gain(const float *in, const float *gain, size_t npix, int32_t c, float *out,
-                                  aivc_stream_t stream) {
-  if (!in || !out || c <= 0) return AIVC_ERR_ARG;
-  if (npix == 0) return AIVC_OK;
-  hipLaunchKernelGGL(channel_gain_kernel, dim3(cdiv(npix * c, 256)), dim3(256), 0, to_stream(stream), in, gain,
-                     npix * c, c, out);
-  return check_launch("channel_gain");
-}
-
-AIVC_EXPORT int aivc_gain_interp(const float *g_r, const float *g_t, int32_t c, float l, float *out,
-                                 aivc_stream_t stream) {
-  if (!g_r || !g_t || !out || c <= 0) return AIVC_ERR_ARG;
-  hipLaunchKernelGGL(gain_interp_kernel, dim3(cdiv(c, 256)), dim3(256), 0, to_stream(stream), g_r, g_t, c, l, out);
-  return check_launch("gain_interp");
-}
-
-AIVC_EXPORT int aivc_quantize_center(const float *y, const float *mu, const float *gain_dec, size_t npix, int32_t c,
-                                     int16_t *q, float *y_hat, aivc_stream_t stream) {
-  if (!y || c <= 0 || (!q && !y_hat)) return AIVC_ERR_ARG;
-  if (npix == 0) return AIVC_OK;
-  hipLaunchKernelGGL(quantize_center_kernel, dim3(cdiv(npix * c, 256)), dim3(256), 0, to_stream(stream), y, mu,
-                     gain_dec, npix * c, c, q, y_hat);
-  return check_launch("quantize_center");
-}
-
-AIVC_EXPORT int aivc_dequantize(const int16_t *q, const float *mu, const float *gain_dec, size_t npix, int32_t c,
-                                float *y_hat, aivc_stream_t stream) {
-  if (!q || !y_hat || c <= 0) return AIVC_ERR_ARG;
-  if (npix == 0) return AIVC_OK;
-  hipLaunchKernelGGL(dequantize_kernel, dim3(cdiv(npix * c, 256)), dim3(256), 0, to_stream(stream), q, mu, gain_dec,
-                     npix * c, c, y_hat);
-  return check_launch("dequantize");
 }

@@ -4,7 +4,7 @@
 // Both are streaming reductions, HBM-bound: every input byte is read once, in 16-byte accesses where the layout allows,
 // consecutive lanes on consecutive addresses; LDS is used for the workgroup's reduction only.  Neither result depends on the
 // grid: the first is integer arithmetic, the second walks the fixed lanes of csrc/rate.hip.
-#include "common.h"
+#include "reduce.h"
 #include "../../include/aivc_hip_quality.h"
 
 namespace aivc {
@@ -24,12 +24,6 @@ __device__ __forceinline__ uint32_t sq_diff4(uint32_t a, uint32_t b) {  // sum o
   return s;
 }
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, s, 64);
-  return v;  // (lane 0 holds the sum)
-}
-
 // grid (AIVC_SSE_BLOCKS, n * 3): workgroup (bx, f * 3 + p) leaves the sum over its share of plane p of frame f
 __global__ void __launch_bounds__(SSE_THREADS) frame_sse_u8_kernel(const uint8_t *sy, const uint8_t *su, const uint8_t *sv,
                                                                    const uint8_t *ry, const uint8_t *ru, const uint8_t *rv,
@@ -39,38 +33,19 @@ __global__ void __launch_bounds__(SSE_THREADS) frame_sse_u8_kernel(const uint8_t
   const uint8_t *a = (p == 0 ? sy : (p == 1 ? su : sv)) + (size_t)f * size;
   const uint8_t *b = (p == 0 ? ry : (p == 1 ? ru : rv)) + (size_t)f * size;
   const size_t t = (size_t)blockIdx.x * SSE_THREADS + threadIdx.x, T = (size_t)AIVC_SSE_BLOCKS * SSE_THREADS;
-  // bytes in front of the first 16-byte boundary; planes that do not share their alignment are read byte by byte
-  size_t head = (size_t)(-(uintptr_t)a & 15);
-  if (((uintptr_t)a & 15) != ((uintptr_t)b & 15) || head > size) head = size;
-  const size_t nvec = (size - head) / 16, tail0 = head + nvec * 16;
+  // planes that do not share their alignment are read byte by byte
+  const ByteSplit sp(a, size, ((uintptr_t)a & 15) != ((uintptr_t)b & 15));
   uint64_t acc = 0;
-  const uint4 *va = reinterpret_cast<const uint4 *>(a + head), *vb = reinterpret_cast<const uint4 *>(b + head);
-  for (size_t i = t; i < nvec; i += T) {
+  const uint4 *va = reinterpret_cast<const uint4 *>(a + sp.head), *vb = reinterpret_cast<const uint4 *>(b + sp.head);
+  for (size_t i = t; i < sp.nvec; i += T) {
     const uint4 x = va[i], y = vb[i];
     acc += sq_diff4(x.x, y.x) + sq_diff4(x.y, y.y) + sq_diff4(x.z, y.z) + sq_diff4(x.w, y.w);  // <= 16 * 65025: no 32-bit overflow
   }
-  const size_t n_scalar = head + (size - tail0);  // the bytes outside the 16-byte part: [0, head) and [tail0, size)
-  for (size_t i = t; i < n_scalar; i += T) {
-    const size_t j = i < head ? i : tail0 + (i - head);
+  sp.outside(t, T, [&](size_t j) {
     const int d = (int)a[j] - (int)b[j];
     acc += (uint32_t)(d * d);
-  }
-  __shared__ uint64_t wave_part[SSE_THREADS / 64];
-  acc = wave_sum_u64(acc);
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t s = 0;
-    for (int k = 0; k < SSE_THREADS / 64; ++k) s += wave_part[k];
-    partials[(size_t)blockIdx.y * AIVC_SSE_BLOCKS + blockIdx.x] = s;
-  }
-}
-
-// one wavefront per (frame, plane): the AIVC_SSE_BLOCKS partials -> sse[f][p]
-__global__ void __launch_bounds__(64) frame_sse_fold_kernel(const uint64_t *partials, uint64_t *sse) {
-  static_assert(AIVC_SSE_BLOCKS == 64, "one partial per lane");
-  const uint64_t s = wave_sum_u64(partials[(size_t)blockIdx.x * AIVC_SSE_BLOCKS + threadIdx.x]);
-  if (threadIdx.x == 0) sse[blockIdx.x] = s;
+  });
+  block_partial_u64<SSE_THREADS>(acc, partials + (size_t)blockIdx.y * AIVC_SSE_BLOCKS + blockIdx.x);
 }
 
 // grid (AIVC_RATE_LANES / 256, n): lane j of frame f adds the terms of its pixels j, j + L, ... into lanes[f][0..2][j]
@@ -107,15 +82,12 @@ __global__ void __launch_bounds__(256) frame_aux_lanes_kernel(const float *alpha
   out[2 * (size_t)AIVC_RATE_LANES + j] = se;
 }
 
-// grid (3, n): lanes[j] += lanes[j + s] for s = L/2, ..., 1 (the tree of rate_tree_kernel), one workgroup per sum
+// grid (3, n): the fixed tree of rate_tree_kernel (reduce.h), one workgroup per sum
 __global__ void __launch_bounds__(1024) frame_aux_tree_kernel(double *lanes, double ones_sum, int alpha_null, int beta_null,
                                                               double *out) {
   const size_t q = (size_t)blockIdx.y * 3 + blockIdx.x;
   double *l = lanes + q * AIVC_RATE_LANES;
-  for (int s = AIVC_RATE_LANES / 2; s >= 1; s >>= 1) {
-    for (int j = threadIdx.x; j < s; j += 1024) l[j] = l[j] + l[j + s];
-    __syncthreads();
-  }
+  fixed_tree_sum(l);
   if (threadIdx.x == 0) {
     const bool ones = (blockIdx.x == 0 && alpha_null) || (blockIdx.x == 1 && beta_null);
     out[q] = ones ? ones_sum : l[0];
@@ -136,7 +108,8 @@ AIVC_EXPORT int aivc_frame_sse_u8(const uint8_t *src_y, const uint8_t *src_u, co
   const size_t size_y = (size_t)h * w, size_c = (size_t)((h + 1) / 2) * ((w + 1) / 2);
   hipLaunchKernelGGL(frame_sse_u8_kernel, dim3(AIVC_SSE_BLOCKS, n * 3), dim3(SSE_THREADS), 0, to_stream(stream), src_y, src_u,
                      src_v, rec_y, rec_u, rec_v, size_y, size_c, partials);
-  hipLaunchKernelGGL(frame_sse_fold_kernel, dim3(n * 3), dim3(64), 0, to_stream(stream), partials, sse);
+  // one wavefront per (frame, plane): the AIVC_SSE_BLOCKS partials -> sse[f][p]
+  hipLaunchKernelGGL(fold_partials_u64_kernel<AIVC_SSE_BLOCKS>, dim3(n * 3), dim3(64), 0, to_stream(stream), partials, sse);
   return check_launch("frame_sse_u8");
 }
 

@@ -2,7 +2,7 @@
 // the real one (src/real_life/bitstream.py:307-329, src/real_life/encode.py:153-170) from the probabilities its entropy
 // models give the coded symbols (src/layers/entropy_coding/entropy_coder.py:18-30, pdf_estimator.py:27-65,185-202).
 // Elementwise kernels + one deterministic fp64 sum (fixed lanes, fixed tree: the same bits on the CPU twin).
-#include "common.h"
+#include "reduce.h"
 
 namespace aivc {
 
@@ -14,12 +14,8 @@ __global__ void __launch_bounds__(256) rate_lanes_kernel(size_t n, double *lanes
   for (size_t i = j; i < n; i += AIVC_RATE_LANES) acc = acc + term(i);
   lanes[j] = acc;
 }
-// lanes[j] += lanes[j + s] for s = L/2, L/4, ..., 1
 __global__ void __launch_bounds__(1024) rate_tree_kernel(double *lanes, double *sum) {
-  for (int s = AIVC_RATE_LANES / 2; s >= 1; s >>= 1) {
-    for (int j = threadIdx.x; j < s; j += 1024) lanes[j] = lanes[j] + lanes[j + s];
-    __syncthreads();
-  }
+  fixed_tree_sum(lanes);
   if (threadIdx.x == 0) *sum = lanes[0];
 }
 

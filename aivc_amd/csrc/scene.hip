@@ -10,7 +10,7 @@
 // range for the whole clip: experiments/scene_cut.md.)
 //
 // Every sum is integer arithmetic, so the result depends on neither the grid nor the path a pair takes.
-#include "common.h"
+#include "reduce.h"
 #include "../../include/aivc_hip_scene.h"
 
 namespace aivc {
@@ -40,12 +40,6 @@ __device__ __forceinline__ sad_chunk_t funnel16(const sad_chunk_t &lo, const sad
   r.z = ws == 0 ? t[2] : ws == 1 ? t[3] : ws == 2 ? t[4] : t[5];
   r.w = ws == 0 ? t[3] : ws == 1 ? t[4] : ws == 2 ? t[5] : t[6];
   return r;
-}
-
-__device__ __forceinline__ uint64_t sad_wave_sum(uint64_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, s, 64);
-  return v;  // (lane 0 holds the sum)
 }
 
 // The 16-byte part of a pair: chunks t, t + T, ... of va against the bytes shift .. of vb's chunks.  FUNNEL: shift != 0.
@@ -79,36 +73,15 @@ __global__ void __launch_bounds__(SAD_THREADS) pair_sad_u8_kernel(const uint8_t 
                                                                   uint64_t *__restrict__ partials) {
   const uint8_t *a = planes[blockIdx.y], *b = planes[blockIdx.y + 1];
   const size_t t = (size_t)blockIdx.x * SAD_THREADS + threadIdx.x, T = (size_t)AIVC_SAD_BLOCKS * SAD_THREADS;
-  size_t head = (size_t)(-(uintptr_t)a & 15);  // bytes in front of a's first 16-byte boundary
-  if (head > len) head = len;
-  const size_t nvec = (len - head) / 16, tail0 = head + nvec * 16;
-  const uint32_t shift = (uint32_t)((uintptr_t)(b + head) & 15);  // where b's bytes lie in ITS aligned chunks: uniform
-  sad_chunk_ptr va = (sad_chunk_ptr)(a + head), vb = (sad_chunk_ptr)(b + head - shift);
-  uint64_t acc = shift == 0 ? sad_chunks<false>(va, vb, nvec, t, T, 0) : sad_chunks<true>(va, vb, nvec, t, T, shift);
-  const size_t n_scalar = head + (len - tail0);  // the bytes outside the 16-byte part: [0, head) and [tail0, len)
-  for (size_t i = t; i < n_scalar; i += T) {
-    const size_t j = i < head ? i : tail0 + (i - head);
+  const ByteSplit sp(a, len);
+  const uint32_t shift = (uint32_t)((uintptr_t)(b + sp.head) & 15);  // where b's bytes lie in ITS aligned chunks: uniform
+  sad_chunk_ptr va = (sad_chunk_ptr)(a + sp.head), vb = (sad_chunk_ptr)(b + sp.head - shift);
+  uint64_t acc = shift == 0 ? sad_chunks<false>(va, vb, sp.nvec, t, T, 0) : sad_chunks<true>(va, vb, sp.nvec, t, T, shift);
+  sp.outside(t, T, [&](size_t j) {
     const int d = (int)a[j] - (int)b[j];
     acc += (uint32_t)(d < 0 ? -d : d);
-  }
-  __shared__ uint64_t wave_part[SAD_THREADS / 64];
-  acc = sad_wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t s = 0;
-    for (int k = 0; k < SAD_THREADS / 64; ++k) s += wave_part[k];
-    partials[(size_t)blockIdx.y * AIVC_SAD_BLOCKS + blockIdx.x] = s;
-  }
-}
-
-// one wavefront per pair: the AIVC_SAD_BLOCKS partials -> sad[p]
-__global__ void __launch_bounds__(64) pair_sad_fold_kernel(const uint64_t *__restrict__ partials, uint64_t *__restrict__ sad) {
-  static_assert(AIVC_SAD_BLOCKS % 64 == 0, "whole rounds of one partial per lane");
-  uint64_t s = 0;
-  for (int k = threadIdx.x; k < AIVC_SAD_BLOCKS; k += 64) s += partials[(size_t)blockIdx.x * AIVC_SAD_BLOCKS + k];
-  s = sad_wave_sum(s);
-  if (threadIdx.x == 0) sad[blockIdx.x] = s;
+  });
+  block_partial_u64<SAD_THREADS>(acc, partials + (size_t)blockIdx.y * AIVC_SAD_BLOCKS + blockIdx.x);
 }
 
 }  // namespace aivc
@@ -123,6 +96,7 @@ AIVC_EXPORT int aivc_pair_sad_u8(const uint8_t *const *planes, int32_t n, int64_
   if (n - 1 > 65535) return AIVC_ERR_UNSUPPORTED;  // grid.y
   hipLaunchKernelGGL(pair_sad_u8_kernel, dim3(AIVC_SAD_BLOCKS, n - 1), dim3(SAD_THREADS), 0, to_stream(stream), planes, (size_t)len,
                      partials);
-  hipLaunchKernelGGL(pair_sad_fold_kernel, dim3(n - 1), dim3(64), 0, to_stream(stream), partials, sad);
+  // one wavefront per pair: the AIVC_SAD_BLOCKS partials -> sad[p]
+  hipLaunchKernelGGL(fold_partials_u64_kernel<AIVC_SAD_BLOCKS>, dim3(n - 1), dim3(64), 0, to_stream(stream), partials, sad);
   return check_launch("pair_sad_u8");
 }

@@ -41,6 +41,15 @@ def batch_rates(idx_rate, n):
     return None, rates
 
 
+def gain_op(name, gm, idx_rate, n, mode, c):
+    """The latent op `name` of a batch of n images and its gain argument -> (ops.<name>, gm's [c] vector) when one rate serves
+    the batch (batch_rates), else (ops.<name>_rows, the [n][c] table of one row per image)."""
+    rate, rates = batch_rates(idx_rate, n)
+    if rates is None:
+        return getattr(ops, name), gm.gain_vector(rate, mode)
+    return getattr(ops, name + '_rows'), gm.gain_rows(rates, mode, c)
+
+
 class ConditionalNet(Module):
     def __init__(self, param):
         super().__init__()
@@ -102,18 +111,13 @@ class ConditionalNet(Module):
         if bands is not None:
             y = bands.gather_full(y)
         n, h_y, w_y, _ = y.shape
-        rate, rates = batch_rates(idx_rate, n)
-        if rates is None:
-            y = ops.channel_gain(y, gm.gain_vector(rate, 'enc').to(dev))
-        else:
-            y = ops.channel_gain_rows(y, gm.gain_rows(rates, 'enc', self.nb_ft_y).to(dev))
+        op, gain = gain_op('channel_gain', gm, idx_rate, n, 'enc', self.nb_ft_y)
+        y = op(y, gain.to(dev))
         z = run_nhwc(self.h_a, y)
         q_z, z_hat = ops.quantize_center(z)
         mu, sigma = ops.hyper_params(run_nhwc(self.h_s, z_hat), self.nb_ft_y, h_y, w_y)
-        if rates is None:
-            q_y, y_hat = ops.quantize_center(y, mu, gm.gain_vector(rate, 'dec').to(dev))
-        else:
-            q_y, y_hat = ops.quantize_center_rows(y, mu, gm.gain_rows(rates, 'dec', self.nb_ft_y).to(dev))
+        op, gain = gain_op('quantize_center', gm, idx_rate, n, 'dec', self.nb_ft_y)
+        q_y, y_hat = op(y, mu, gain.to(dev))
         return {'q_z': q_z, 'q_y': q_y, 'mu': mu, 'sigma': sigma, 'y_hat': y_hat,
                 'dim_y': (h_y, w_y), 'dim_z': tuple(z.shape[1:3])}
 
@@ -124,10 +128,8 @@ class ConditionalNet(Module):
         z_hat = ops.dequantize(q_z)
         mu, sigma = ops.hyper_params(run_nhwc(self.h_s, z_hat), self.nb_ft_y, dim_y[0], dim_y[1])
         q_y = q_y_fn(sigma)
-        rate, rates = batch_rates(idx_rate, q_z.shape[0])
-        if rates is None:
-            return ops.dequantize(q_y, mu, gm.gain_vector(rate, 'dec').to(q_z.device))
-        return ops.dequantize_rows(q_y, mu, gm.gain_rows(rates, 'dec', self.nb_ft_y).to(q_z.device))
+        op, gain = gain_op('dequantize', gm, idx_rate, q_z.shape[0], 'dec', self.nb_ft_y)
+        return op(q_y, mu, gain.to(q_z.device))
 
     def synthesise(self, y_hat, in_shortcut, bands=None):
         """bands: g_a_ref and g_s run in row bands; -> this rank's band of the synthesis output"""

@@ -392,8 +392,14 @@ int aivc_warp(const float *x, const float *flow, int32_t n, int32_t h, int32_t w
 int aivc_hyper_params(const float *hs, int32_t n, int32_t hh, int32_t wh, int32_t c, int32_t h,
                       int32_t w, float *mu, float *sigma, aivc_stream_t stream);
 
-/* out[p][ch] = in[p][ch] * fabsf(gain[ch])   (GainMatrix.forward, integer idx_rate;
- * src/layers/multi_rate/gain_matrix.py:92-157).  gain may be NULL (copy). */
+/* aivc_channel_gain, aivc_quantize_center and aivc_dequantize take ONE [c] gain vector for the whole tensor.  Each is the
+ * one-row case of its `_rows` form (a table of one gain row per image, declared in the header of the per-image rates;
+ * csrc/latent.hip): it launches that form's kernel, the only kernel of the op, on the tensor as one image of npix * c
+ * elements with the vector as the table.
+ * A tensor of more than 0x7fffffff * 256 elements is AIVC_ERR_UNSUPPORTED; npix == 0 is AIVC_OK. */
+
+/* The one-row case of aivc_channel_gain_rows: out[p][ch] = in[p][ch] * fabsf(gain[ch])   (GainMatrix.forward, integer
+ * idx_rate; src/layers/multi_rate/gain_matrix.py:92-157).  gain may be NULL (copy). */
 int aivc_channel_gain(const float *in, const float *gain, size_t npix, int32_t c, float *out,
                       aivc_stream_t stream);
 
@@ -403,13 +409,13 @@ int aivc_channel_gain(const float *in, const float *gain, size_t npix, int32_t c
 int aivc_gain_interp(const float *g_r, const float *g_t, int32_t c, float l, float *out,
                      aivc_stream_t stream);
 
-/* Encoder side: q = clamp(rint(y - mu), -256, 255) (half-to-even); y_hat = (q + mu) * |gain_dec|.
- * mu == NULL means mu = 0 (the z latent); gain_dec == NULL means gain 1.  q (int16) and y_hat
- * may each be NULL.  A NaN y - mu gives q = 0 and a NaN y_hat (+-inf clamp to +-256).  Replaces Quantizer (src/layers/misc/misc_layers.py:162-169) and the
- * centring/gain of src/real_life/decode.py:867-885. */
+/* The one-row case of aivc_quantize_center_rows, encoder side: q = clamp(rint(y - mu), -256, 256) (half-to-even);
+ * y_hat = (q + mu) * |gain_dec|.  mu == NULL means mu = 0 (the z latent); gain_dec == NULL means gain 1.  q (int16) and y_hat
+ * may each be NULL, not both.  A NaN y - mu gives q = 0 and a NaN y_hat (+-inf clamp to +-256).  Replaces Quantizer
+ * (src/layers/misc/misc_layers.py:162-169) and the centring/gain of src/real_life/decode.py:867-885. */
 int aivc_quantize_center(const float *y, const float *mu, const float *gain_dec, size_t npix,
                          int32_t c, int16_t *q, float *y_hat, aivc_stream_t stream);
-/* Decoder side: y_hat = ((float)q + mu) * |gain_dec|. */
+/* The one-row case of aivc_dequantize_rows, decoder side: y_hat = ((float)q + mu) * |gain_dec|. */
 int aivc_dequantize(const int16_t *q, const float *mu, const float *gain_dec, size_t npix,
                     int32_t c, float *y_hat, aivc_stream_t stream);
 

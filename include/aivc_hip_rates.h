@@ -5,21 +5,23 @@
  * The codec pushes the frames of a dependency level of ALL intra-period units through the networks as one batch.  When the
  * units are coded at different rate indices (FrameCodec.encode_units(idx_rate=[...]), aivc_amd/rate_control.py), the images
  * of a batch have different gain vectors; aivc_channel_gain / aivc_quantize_center / aivc_dequantize (aivc_hip.h) take one
- * [c] vector per launch.  These three take a table instead:
+ * [c] vector per call.  These three take a table instead:
  *
  *   tensors  [n][npix][c]   (n images of npix positions, channels innermost)
  *   gains    [n][c]         image i uses row i
  *
- * Per element the arithmetic is that of the single-gain entry points, operation for operation (fabsf of the gain inside the
- * kernel, rintf, the clamp to the coder's alphabet, (r + mu) * |g|): image i comes out with the bits the single-gain entry
- * point gives for that image alone with row i (tests/test_gpu_latent_rows.py).  The same pointers may be NULL, with the
- * same meaning.  The image is a coordinate of the grid (blockIdx.y, like the batch entropy kernels): n > 65535 is
+ * Their kernels (csrc/latent.hip) are the only kernels of the three ops: a single-gain entry point is the one-row call
+ * (n = 1, npix * c elements in the one image, the [c] vector as the table).  So per element there is one statement of the
+ * arithmetic (fabsf of the gain inside the kernel, rintf, the clamp to the coder's alphabet, (r + mu) * |g|), and image i
+ * comes out with the bits the single-gain entry point gives for that image alone with row i by construction
+ * (tests/test_gpu_latent_rows.py).  The same pointers may be NULL, with the same meaning.  The image is a coordinate of the
+ * grid (blockIdx.y, like the batch entropy kernels): n > 65535, or more than 0x7fffffff * 256 elements per image, is
  * AIVC_ERR_UNSUPPORTED; n <= 0, c <= 0 or a NULL required pointer is AIVC_ERR_ARG; npix == 0 is AIVC_OK (nothing to do).
  * Element-wise and HBM-bound: every element is read and written once, consecutive lanes on consecutive addresses.
  *
  * The rows are built by the caller: GainMatrix.gain_rows stacks what GainMatrix.gain_vector gives for every distinct rate of
  * the batch (aivc_gain_interp for a fractional one), so a fractional rate has the bits of the single-rate path.
- * These entry points have no `_ref` twin in the CPU oracle; their statement is the single-gain entry points, which have one.
+ * These entry points have no `_ref` twin in the CPU oracle; the single-gain entry points, which run the same kernels, have one.
  */
 #ifndef AIVC_HIP_RATES_H
 #define AIVC_HIP_RATES_H

@@ -1,7 +1,8 @@
 """aivc_channel_gain_rows / aivc_quantize_center_rows / aivc_dequantize_rows (include/aivc_hip_rates.h): one gain row per image of
 a batch.  Their statement is the single-gain entry point applied image by image with that image's row (those are pinned to the
 CPU oracle, tests/test_gpu_ops.py): the bits must be EQUAL.  Each case runs plain and under the guard-zone and poison harness of
-tests/guarded.py with both fills; the three runs must agree byte for byte.
+tests/guarded.py with both fills; the three runs must agree byte for byte.  The single-gain entry points launch the row kernels
+as their one-row case (csrc/latent.hip); a second test runs them on a whole batch, where that one row spans the images.
 
 Shapes (n, h, w, c):
   (3, 5, 7, 6)    630 elements: 210 per image, less than a block each (three blocks over the grid's image axis), no multiple of
@@ -104,6 +105,41 @@ def test_rows_equal_single_gain_ops_image_by_image(n, h, w, c, cuda):
     plain = run_case(lambda a: torch.from_numpy(a).to(cuda), d)
     plain = {k: v.cpu().numpy().tobytes() for k, v in plain.items()}
     assert both_fills(lambda fill: run_case(lambda a: guarded(a, cuda, fill), d)) == plain
+
+
+def run_whole_batch_case(place, d):
+    """the single-gain ops on the WHOLE batch with one [c] vector (one flat launch: its blocks straddle the images) against the
+    row ops given that vector n times -> the single-gain results"""
+    from aivc_amd import ops
+    t = {k: place(v) for k, v in d.items()}
+    n = t['y'].shape[0]
+    vec, table = place(d['gains'][0].copy()), place(np.repeat(d['gains'][:1], n, axis=0))
+    out = {}
+
+    def same(key, single, rows):
+        assert single.dtype == rows.dtype and torch.equal(single, rows), key
+        out[key] = single
+
+    for tag, g, gs in (('', vec, table), ('_nogain', None, None)):
+        same('gain' + tag, ops.channel_gain(t['y'], g), ops.channel_gain_rows(t['y'], gs))
+        for mtag, mu in (('', t['mu']), ('_nomu', None)):
+            q, yh = ops.quantize_center(t['y'], mu, g)
+            q_rows, yh_rows = ops.quantize_center_rows(t['y'], mu, gs)
+            same('q' + tag + mtag, q, q_rows)
+            same('yh' + tag + mtag, yh, yh_rows)
+            same('deq' + tag + mtag, ops.dequantize(t['q'], mu, g), ops.dequantize_rows(t['q'], mu, gs))
+    return out
+
+
+@pytest.mark.parametrize('n,h,w,c', [(3, 5, 7, 6), (4, 3, 3, 64)])
+def test_single_gain_ops_on_a_whole_batch_equal_the_row_ops_with_one_vector_repeated(n, h, w, c, cuda):
+    """The other tests compare one-image slices.  Here the single-gain entry points take the batch as ONE row of n * h * w * c
+    elements: 256-thread blocks straddle the image boundaries (210 and 576 elements per image, no multiples of 256; c = 6 is no
+    multiple of 4), and every byte must equal the row ops' with the vector repeated n times, NULL gain and NULL mu included."""
+    d = make_data(n, h, w, c)
+    plain = run_whole_batch_case(lambda a: torch.from_numpy(a).to(cuda), d)
+    plain = {k: v.cpu().numpy().tobytes() for k, v in plain.items()}
+    assert both_fills(lambda fill: run_whole_batch_case(lambda a: guarded(a, cuda, fill), d)) == plain
 
 
 def test_wrong_table_shape_is_refused(cuda):

@@ -1,4 +1,4 @@
-"""The pixel, latent, entropy and rate kernels (csrc/pixel_ops.hip, latent_rows.hip, entropy.hip, rate.hip) against the CPU oracle by
+"""The pixel, latent, entropy and rate kernels (csrc/pixel_ops.hip, latent.hip, entropy.hip, rate.hip) against the CPU oracle by
 bits on the regimes of tests/op_regimes.py: NaN, infinite and overflowing flows, axes of size 1, non-finite and subnormal pixels
 and latents, rounding ties, the clamp constants' neighbours, and every kind of sigma -- the edge of hyper_params' range, what the
 API accepts beyond it, and what lies outside the domain of a cdf.  One test id is one builder under one regime.  The oracle itself

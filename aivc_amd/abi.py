@@ -1,5 +1,6 @@
 """ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h,
-include/aivc_hip_rates.h, include/aivc_hip_digest.h and include/aivc_hip_scene.h (struct layouts, constants, prototypes).
+include/aivc_hip_rates.h, include/aivc_hip_digest.h, include/aivc_hip_scene.h and include/aivc_hip_resize.h (struct layouts,
+constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -7,7 +8,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -29,6 +30,7 @@ RC_MAX_STREAMS = 64
 RATE_LANES = 16384
 SSE_BLOCKS = 64  # include/aivc_hip_quality.h: AIVC_SSE_BLOCKS
 SAD_BLOCKS = 128  # include/aivc_hip_scene.h: AIVC_SAD_BLOCKS
+RESIZE_TILE_W, RESIZE_MAX_SPAN = 256, 4064  # include/aivc_hip_resize.h: AIVC_RESIZE_TILE_W, AIVC_RESIZE_MAX_SPAN
 WINO_MIN_PIXELS = 8000  # include/aivc_hip.h: AIVC_WINO_MIN_PIXELS
 WINO_MIN_PIXELS_TCONV = 32768  # ... AIVC_WINO_MIN_PIXELS_TCONV
 
@@ -206,6 +208,11 @@ SCENE_PROTOTYPES = {
     'aivc_pair_sad_u8': [_f, _i32, C.c_int64, _f, _f],
 }
 
+# include/aivc_hip_resize.h: device only (its statement is Pillow: tests/resize_cases.py, tests/test_gpu_resize.py)
+RESIZE_PROTOTYPES = {
+    'aivc_resize_u8': [_f, _i32, _i32, _i32, _i32, _i32, _f, _f, _i32, _i32, _f, _f, _f, _f],
+}
+
 
 def declare(lib, suffix=''):
     """Attach argtypes/restype for every entry of the header; raises AttributeError when the
@@ -238,7 +245,7 @@ def declare(lib, suffix=''):
         wm.restype = C.c_int
         fns['aivc_warp_modes'] = wm
         for name, args in list(COLOR_PROTOTYPES.items()) + list(QUALITY_PROTOTYPES.items()) + list(RATES_PROTOTYPES.items()) \
-                + list(DIGEST_PROTOTYPES.items()) + list(SCENE_PROTOTYPES.items()):
+                + list(DIGEST_PROTOTYPES.items()) + list(SCENE_PROTOTYPES.items()) + list(RESIZE_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.argtypes = list(args) + [C.c_void_p]
             fn.restype = C.c_int

@@ -46,10 +46,18 @@ def parse_args(argv=None):
     add_contract_flag(p, ('fp32', 'fp32w', 'auto'))
     enc_cli.add_rate_flags(p)
     enc_cli.add_scene_flag(p)
+    from aivc_amd.resize import add_resize_flags, check_resize_flags
+    add_resize_flags(p, {'--size': enc_cli.SIZE_HELP, '--out_size': dec_cli.OUT_SIZE_HELP})
     a = p.parse_args(argv)
     enc_cli.check_rate_flags(p, a)
     enc_cli.check_scene_flag(p, a)
+    a.resample = check_resize_flags(p, a, ('--size', '--out_size'))
+    dec_cli.check_out_size(p, a, a.o)
     return a
+
+
+def size_text(size):
+    return '%dx%d' % size
 
 
 def main(argv=None):
@@ -67,18 +75,26 @@ def main(argv=None):
                  + (['--target_bpp', str(a.target_bpp)] if a.target_bpp > 0 else [])
                  + (['--digests'] if a.digests else [])
                  + (['--scene_cut', repr(a.scene_cut)] if a.scene_cut is not None else [])
+                 + (['--size', size_text(a.size), '--resample', a.resample] if a.size is not None else [])
                  + (['--contract', a.contract] if a.contract not in (None, 'auto') else []))  # (auto is the decoder's choice)
     banner(('*' * 80).center(120))
     banner('Starting decoding'.center(120))
     verify = a.verify if a.verify else bool(a.digests)  # --digests verifies its own decode
     status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common
                           + ([] if not verify else ['--verify'] if verify is True else ['--verify', verify])
+                          + (['--out_size', size_text(a.out_size), '--resample', a.resample] if a.out_size is not None else [])
                           + (['--contract', a.contract] if a.contract else []))
     from aivc_amd import parallel
     if parallel.rank_world()[0] != 0:  # multi-rank job: rank 0 evaluates
         return status
     if os.path.isdir(a.i) or dec_cli.is_png_folder(a.o):  # (evaluate.py scores planar files)
         print('[INFO] evaluation skipped: it compares two planar .yuv files, -i / -o name picture folders')
+        return status
+    from aivc_amd.real_life.encode import parse_yuv_name
+    written = a.out_size if a.out_size is not None else a.size  # the size of the frames in -o, where it was chosen here
+    if written is not None and written != parse_yuv_name(a.i):
+        print('[INFO] evaluation skipped: -o holds %dx%d frames, -i %dx%d ones (evaluate.py compares frames of one size; '
+              '--out_size with the size of -i brings them back)' % (written + parse_yuv_name(a.i)))
         return status
     print(('*' * 80).center(120))
     print('Starting evaluation'.center(120))

@@ -6,6 +6,19 @@ from aivc_amd.cli_common import add_contract_flag, contract_scope, get_model, re
 from aivc_amd.real_life.decode import Decoder, decode_one_video, is_png_folder
 
 
+OUT_SIZE_HELP = ('write the decoded frames at this size: resized on the device just before they are written, .yuv or pictures (y to '
+                 'H x W, u and v to the ceil half size); --verify keeps digesting the planes at coded size, --frames / --max_level '
+                 'resize only what they write.  The name of a .yuv output is the caller\'s business')
+
+
+def check_out_size(p, a, out):
+    """an argparse error for an odd --out_size with RGB pictures as output: their chroma would not be the ceil-sized planes the
+    encoder takes back (real_life.encode.read_png_folder refuses such a folder)"""
+    from aivc_amd.real_life.decode import is_png_folder
+    if a.out_size is not None and is_png_folder(out) and (a.out_size[0] % 2 or a.out_size[1] % 2):
+        p.error('--out_size %dx%d with RGB pictures as output (-o %s): RGB pictures need even sides' % (a.out_size + (out,)))
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--cpu', action='store_true')
@@ -21,9 +34,13 @@ def parse_args(argv=None):
     p.add_argument('--max_level', default=None, type=int, metavar='L',
                    help='partial decode: only frames of temporal level <= L (the dependency depth inside an intra-period unit: '
                         '0 the I frame, 1 the P frame; 1_GOP_32 has levels 0 ... 6, each one less halves the frame count)')
+    from aivc_amd.resize import add_resize_flags, check_resize_flags
+    add_resize_flags(p, {'--out_size': OUT_SIZE_HELP})
     a = p.parse_args(argv)
     if a.max_level is not None and a.max_level < 0:
         p.error('--max_level %d: temporal levels count from 0' % a.max_level)
+    a.resample = check_resize_flags(p, a, ('--out_size',))
+    check_out_size(p, a, a.o)
     return a
 
 
@@ -52,7 +69,8 @@ def main(argv=None):
     try:
         with contract_scope(a.contract):
             decode_one_video({'decoder': dec, 'bitstream_path': a.i, 'device': str(dev), 'out_file': out, 'verify': a.verify,
-                              'contract': 'auto' if a.contract == 'auto' else '', 'frames': a.frames, 'max_level': a.max_level})
+                              'contract': 'auto' if a.contract == 'auto' else '', 'frames': a.frames, 'max_level': a.max_level,
+                              'out_size': a.out_size, 'resample': a.resample})
     except ContainerError as e:  # a truncated / damaged file: say so and stop (exit status 2), no frames are written
         print('[ERROR] %s is not a complete bitstream: %s' % (a.i, e))
         raise SystemExit(2)

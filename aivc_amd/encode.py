@@ -46,6 +46,18 @@ def check_scene_flag(p, a):
         p.error('--scene_cut %r: the threshold is a non-negative number of grey levels' % a.scene_cut)
 
 
+SIZE_HELP = ('code the clip at this size: every plane is resized on the device right after it has been read (y to H x W, u and v to '
+             'the ceil half size, each on its own; RGB pictures are converted to 4:2:0 first); header, scene cuts, digests, the '
+             'byte budget of --target_bpp and the --log_dir table (which scores against the RESIZED source) see the coded size.  '
+             'The stream has no display-size field: decode.py --out_size writes another size')
+
+
+def add_size_flag(p):
+    """--size WxH and --resample (aivc.py adds --out_size to the same call)"""
+    from aivc_amd.resize import add_resize_flags
+    add_resize_flags(p, {'--size': SIZE_HELP})
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--gop', default='1_GOP_32', type=str)
@@ -58,16 +70,19 @@ def parse_args(argv=None):
     p.add_argument('--cpu', action='store_true')
     p.add_argument('--log_dir', default='', type=str,
                    help='write the per-frame table <log_dir>/detailed.txt (PSNR, rates, alpha, beta, loss, MS-SSIM) and print '
-                        'the Estimated MS-SSIM line; off by default')
+                        'the Estimated MS-SSIM line; off by default.  With --size the scores are against the resized source')
     p.add_argument('--digests', action='store_true',
                    help='write the sidecar manifest <bitstream>.md5: the arithmetic contract and one MD5 per reconstructed plane, '
                         'computed on the device (decode.py --verify checks a decode against it); the bitstream does not change')
     add_contract_flag(p, ('fp32', 'fp32w'))
     add_rate_flags(p)
     add_scene_flag(p)
+    add_size_flag(p)
     a = p.parse_args(argv)
     a.idx_rate = check_rate_flags(p, a)
     check_scene_flag(p, a)
+    from aivc_amd.resize import check_resize_flags
+    a.resample = check_resize_flags(p, a, ('--size',))
     return a
 
 
@@ -82,7 +97,8 @@ def main(argv=None):
         return encode({'model': model, 'sequence_path': a.i, 'GOP_struct': generate_gop_struct(a.gop),
                        'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
                        'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp,
-                       'rate_step': a.rate_step, 'digests': a.digests, 'scene_cut': a.scene_cut})
+                       'rate_step': a.rate_step, 'digests': a.digests, 'scene_cut': a.scene_cut, 'size': a.size,
+                       'resample': a.resample})
 
 
 if __name__ == '__main__':

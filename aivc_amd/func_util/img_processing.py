@@ -194,6 +194,30 @@ def save_yuv_separately(x, path_img):
         _save_png(_to_u8(_chw(x[key]))[0], path_img + '_' + key + '.png', 'L')
 
 
+def resize_frames(frames, w, h, filter='bicubic', device=None):
+    """A list of 4:2:0 frames, dicts of uint8 planes {'y','u','v'} of [1, h0, w0] (device tensors, or host tensors / arrays: those
+    are copied to `device`), resized to w x h on the device: y to h x w, u and v to ceil(h / 2) x ceil(w / 2), every plane on its
+    own with Pillow's Image.resize arithmetic (ops.resize_u8) -- exactly what resizing each picture of a PNG triplet with Pillow
+    gives.  Chroma siting is ignored, as Pillow ignores it there: a chroma plane is resized like any grey picture, its samples
+    taken to sit at the centres of its own grid.  Two calls of the op for a clip, one over the y planes and one over u and v
+    together.  -> a new list of dicts of [1, h', w'] uint8 device tensors (views into the two results); frames that have the
+    size already come back as they are."""
+    if not frames:
+        return []
+
+    def planes(k):
+        got = [torch.as_tensor(fr[k]) for fr in frames]
+        return [t if device is None else t.to(device) for t in got]
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    y, u, v = planes('y'), planes('u'), planes('v')
+    if all(tuple(t.shape[-2:]) == (h, w) for t in y) and all(tuple(t.shape[-2:]) == (hc, wc) for t in u + v):
+        return [{'y': a.reshape(1, h, w), 'u': b.reshape(1, hc, wc), 'v': c.reshape(1, hc, wc)} for a, b, c in zip(y, u, v)]
+    ry = ops.resize_u8(y, h, w, filter)
+    rc = ops.resize_u8(u + v, hc, wc, filter)
+    n = len(frames)
+    return [{'y': ry[i:i + 1], 'u': rc[i:i + 1], 'v': rc[n + i:n + i + 1]} for i in range(n)]
+
+
 # ---- a folder of such pictures as the encoder's input -------------------------------------------------------------------
 def detect_folder_layout(sequence_path):
     """-> (loading_mode, rgb, [frame indices present, ascending]) from the file names of the folder:

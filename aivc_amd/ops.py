@@ -602,6 +602,80 @@ def pair_sad_u8(planes):
     return sad
 
 
+def resize_u8(planes, h_out, w_out, filter='bicubic'):
+    """Pillow's Image.resize of 8-bit single-channel planes, byte for byte (include/aivc_hip_resize.h; filter: box, bilinear,
+    hamming, bicubic or lanczos).  planes: a list of n contiguous uint8 CUDA tensors of one size, [h, w] or [1, h, w] (the planes
+    of a clip as read_yuv leaves them: separate tensors, any alignment), or one uint8 CUDA tensor [n, h, w].
+    -> uint8 CUDA tensor [n, h_out, w_out].  The coefficient tables come from the host (aivc_amd/resize.py, cached per axis and
+    filter) in the same small host-to-device copy as the pointer table; the launches go on the current stream, no synchronisation.
+    A shape the kernels cannot take raises ValueError with the sizes named, before anything is allocated."""
+    from . import resize as rs
+    rs.check_filter(filter)
+    if isinstance(planes, (list, tuple)):
+        planes = [_dev(t, torch.uint8, 'planes[%d]' % i) for i, t in enumerate(planes)]
+        if not planes:
+            raise ValueError('resize_u8: no planes')
+        shape = tuple(planes[0].shape)
+        if any(tuple(t.shape) != shape for t in planes):
+            raise ValueError('resize_u8: the planes of one call have one size, got %s' % sorted({tuple(t.shape) for t in planes}))
+        if len({t.device for t in planes}) > 1:
+            raise ValueError('resize_u8: planes on several devices')
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 1):
+            raise ValueError('resize_u8: expected planes [h, w] or [1, h, w], got %s' % (shape,))
+        ptrs = [t.data_ptr() for t in planes]
+        device = planes[0].device
+    else:
+        planes = _dev(planes, torch.uint8, 'planes')
+        if planes.dim() != 3 or planes.shape[0] < 1:
+            raise ValueError('resize_u8: expected [n, h, w], got %s' % (tuple(planes.shape),))
+        shape = tuple(planes.shape[1:])
+        ptrs = [planes.data_ptr() + i * shape[0] * shape[1] for i in range(planes.shape[0])]
+        device = planes.device
+    n, (h_in, w_in), h_out, w_out = len(ptrs), shape[-2:], int(h_out), int(w_out)
+    if min(h_in, w_in, h_out, w_out) < 1:
+        raise ValueError('resize_u8: %d x %d -> %d x %d (w x h): every side must be at least 1' % (w_in, h_in, w_out, h_out))
+    what = '%d planes of %d x %d -> %d x %d (w x h, %s)' % (n, w_in, h_in, w_out, h_out, filter)
+    tiles = -(-w_out // abi.RESIZE_TILE_W)
+    if tiles > 65535 or -(-n * h_in // 16) > 0x7fffffff or n * -(-h_out // 16) > 0x7fffffff \
+            or ((h_in, w_in) == (h_out, w_out) and n > 65535):
+        raise ValueError('resize_u8: %s is more than one launch can express (65535 tiles of %d columns, 2^31 - 1 tiles of 16 rows; '
+                         '65535 planes where nothing changes size)' % (what, abi.RESIZE_TILE_W))
+    xt = rs.device_tables(w_in, w_out, filter, abi.RESIZE_TILE_W) if w_out != w_in else None
+    yt = rs.device_tables(h_in, h_out, filter, 16) if h_out != h_in else None
+    if xt is not None and xt[2] > abi.RESIZE_MAX_SPAN:
+        raise ValueError('resize_u8: %s: a tile of %d output columns reads %d input columns with %d taps, the horizontal pass holds '
+                         'at most %d per row' % (what, abi.RESIZE_TILE_W, xt[2], xt[1].shape[0], abi.RESIZE_MAX_SPAN))
+    # one staging buffer: the pointer table, then the tables of the passes, each on a 16-byte boundary
+    parts = [np.asarray(ptrs, np.uint64).view(np.uint8)]
+    for t in (xt, yt):
+        parts += [] if t is None else [np.ascontiguousarray(t[0]).view(np.uint8).reshape(-1), t[1].view(np.uint8).reshape(-1)]
+    offs, total = [], 0
+    for a in parts:
+        offs.append(total)
+        total += -(-a.size // 16) * 16
+    host = _pinned_staging(total)
+    view = host.numpy()
+    for o, a in zip(offs, parts):
+        view[o:o + a.size] = a
+    blob = torch.empty(total, dtype=torch.uint8, device=device)
+    blob.copy_(host, non_blocking=True)
+    _pinned_release(host)
+    base = blob.data_ptr()
+    at = iter(offs[1:])
+    xb, xk = (base + next(at), base + next(at)) if xt is not None else (None, None)
+    yb, yk = (base + next(at), base + next(at)) if yt is not None else (None, None)
+    out = torch.empty((n, h_out, w_out), dtype=torch.uint8, device=device)
+    tmp = None
+    if xt is not None and yt is not None:  # the horizontal pass's result, rows padded to 4 bytes
+        tmp = torch.empty(n * h_in * (-(-w_out // 4) * 4), dtype=torch.uint8, device=device)
+
+    def launch():
+        call('aivc_resize_u8', base, n, h_in, w_in, h_out, w_out, xb, xk, 0 if xt is None else xt[1].shape[0],
+             0 if xt is None else xt[2], yb, yk, _p(tmp), _p(out), _stream())
+    _hbm_profiled('resize_u8', n * (h_in * w_in + h_out * w_out), launch)
+    return out
+
+
 def downsample2x(x, ch0, nch):
     """NHWC x -> planar [n, nch, h//2, w//2] 2x2 means of channels ch0..ch0+nch-1 (OutputLayer)."""
     x = _dev(x, torch.float32, 'x')

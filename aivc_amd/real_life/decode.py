@@ -145,9 +145,15 @@ def decode_one_video(param):
     reference closure of the request is decoded, and the frames asked for are written in ascending order (pictures
     under their absolute index), counted by `Number of frames` and compared with their rows of the manifest.  One line more
     is printed: `[INFO] partial decode: <K> frames written, <D> of <C> coded frames decoded`.  A request outside the stream
-    is an aivc_amd.partial.FrameSelectionError.  Without either it is the same decode with the request for everything."""
+    is an aivc_amd.partial.FrameSelectionError.  Without either it is the same decode with the request for everything.
+    out_size: None (the default), or (w, h): the frames that are returned and written -- the .yuv file or the pictures -- are
+    resized to it on the device just before (func_util.img_processing.resize_frames: Pillow's Image.resize byte for byte,
+    filter `resample`, default bicubic; each plane on its own, chroma to the ceil half size, chroma siting ignored).  The
+    stream has no display-size field, so the size is the caller's to give, and so is a .yuv file name that states it.
+    Verification and flag_bitstream_debug look at the planes at CODED size, before the resize; a partial decode resizes only
+    the frames it returns."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
-               'verify': '', 'contract': '', 'frames': None, 'max_level': None}
+               'verify': '', 'contract': '', 'frames': None, 'max_level': None, 'out_size': None, 'resample': 'bicubic'}
     decoder = get_value('decoder', param, default).eval()
     path = get_value('bitstream_path', param, default)
     dev = torch.device(get_value('device', param, default))
@@ -158,6 +164,8 @@ def decode_one_video(param):
     plan = read_plan(path, get_value('frames', param, default), get_value('max_level', param, default))
     from .. import digests, ops, parallel
     _VERIFY_BAD[0] = 0
+    out_size = get_value('out_size', param, default)
+    resize = None if out_size is None else (int(out_size[0]), int(out_size[1]), get_value('resample', param, default))
     manifest = None
     manifest_file = verify if isinstance(verify, str) and verify else digests.manifest_path(path)
     if verify or (contract == 'auto' and os.path.exists(manifest_file)):
@@ -173,7 +181,8 @@ def decode_one_video(param):
             ops.set_precision(choice)
         elif contract:
             ops.set_precision(contract)
-        return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default))
+        return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default),
+                                 resize)
     finally:
         ops.set_precision(prev_precision)
 
@@ -192,7 +201,7 @@ def read_plan(path, span, max_level):
     return plan._replace(video=video._replace(gops=gops))
 
 
-def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug):
+def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize=None):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel, partial
@@ -229,6 +238,10 @@ def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstre
     found = None
     if manifest is not None:  # (queued now, read after the frames have been written)
         found = digest_frames(frames, dev)
+    coded = frames
+    if resize is not None:  # (after the digests: they are the coded planes')
+        from ..func_util.img_processing import resize_frames
+        frames = resize_frames(frames, resize[0], resize[1], resize[2], dev)
     if is_png_folder(out_file):
         write_png_folder(frames, out_file, dev, shown)
     elif out_file:
@@ -242,7 +255,7 @@ def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstre
         for line in digests.verify_lines(len(rows), differing):
             print(line)
     if flag_bitstream_debug:
-        for idx, fr in zip(shown, frames):
+        for idx, fr in zip(shown, coded):
             check_debug_md5([fr], idx, debug_dir(path))
     return frames
 

@@ -77,10 +77,18 @@ def encode(param):
     frames that stand out over both neighbours by at least the threshold open a new intra-period unit (aivc_amd/scene.py: the
     units in front of a cut take a shorter structure, which their GOP headers state; any decoder of the format reads the
     stream), one `[SCENE]` line per cut and an `[INFO] units` line are printed, and the returned dictionary gains 'cuts' and
-    'unit_names'.  Under torch.distributed.run every rank computes the same sums and the same layout."""
+    'unit_names'.  Under torch.distributed.run every rank computes the same sums and the same layout.
+    size: None (the default) -- the clip is coded at the size it arrives in, and nothing below runs; (w, h) -- every plane is
+    resized on the device right after it has been read (func_util.img_processing.resize_frames: Pillow's Image.resize byte for
+    byte, filter `resample`, one of aivc_amd.resize.FILTERS, default bicubic; y to h x w, u and v to the ceil half size, each plane
+    on its own, chroma siting ignored; RGB pictures are converted to 4:2:0 first).  Everything from there on sees the coded
+    size: the header, the scene cuts, the digests, the w x h of the byte budget, the sharding -- and the quality log, whose
+    PSNR and MS-SSIM score the reconstruction against the RESIZED source.  The stream has no display-size field: the decoder
+    is told the size to write (decode_one_video: out_size).  Every rank resizes the clip it read."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
-               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False, 'scene_cut': None}
+               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False, 'scene_cut': None,
+               'size': None, 'resample': 'bicubic'}
     model = get_value('model', param, default)
     want_digests = get_value('digests', param, default)
     seq = get_value('sequence_path', param, default)
@@ -98,6 +106,10 @@ def encode(param):
         print('ERROR: First frame index bigger than last frame index')
         return
     frames, first, last = (read_png_folder if os.path.isdir(seq) else read_yuv)(seq, first, last, dev)
+    size = get_value('size', param, default)
+    if size is not None:
+        from ..func_util.img_processing import resize_frames
+        frames = resize_frames(frames, int(size[0]), int(size[1]), get_value('resample', param, default), dev)
     print_log_msg('INFO', 'Start encoding', '', '')
     t0 = time.time()
     fc = FrameCodec(model)

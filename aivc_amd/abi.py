@@ -214,50 +214,35 @@ RESIZE_PROTOTYPES = {
 }
 
 
+# Everything declare() binds: (name, argtypes, restype, whether the stream argument is appended, whether the CPU oracle has a
+# `_ref` twin).  The diagnostics, aivc_warp_modes (include/aivc_hip_diag.h, include/aivc_hip_warp.h) and the *_PROTOTYPES of the
+# headers above are device only.
+_BINDINGS = [(name, args, C.c_int, True, True) for name, args in PROTOTYPES.items()]
+_BINDINGS += [
+    ('aivc_conv2d_variant', [_P(ConvParams)], C.c_int, False, False),
+    ('aivc_selfcheck_gdn_math', [C.c_uint64, C.c_uint32, _f], C.c_int, True, False),  # the device arithmetic against IEEE
+    ('aivc_detmath_eval', DETMATH_EVAL_ARGS, C.c_int, True, False),  # the deterministic transcendentals, element by element
+    ('aivc_diag_hold_lds', [C.c_uint32, C.c_uint32, _f], C.c_int, True, False),  # a workgroup that holds LDS for a bounded time
+    ('aivc_warp_modes', [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f], C.c_int, True, False),
+]
+for _protos in (COLOR_PROTOTYPES, QUALITY_PROTOTYPES, RATES_PROTOTYPES, DIGEST_PROTOTYPES, SCENE_PROTOTYPES, RESIZE_PROTOTYPES):
+    _BINDINGS += [(name, args, C.c_int, True, False) for name, args in _protos.items()]
+_BINDINGS += [
+    ('aivc_metrics_workspace', [_i32, _i32, _i32], C.c_size_t, False, True),
+    ('aivc_abi_version', [], C.c_int, False, True),
+]
+
+
 def declare(lib, suffix=''):
     """Attach argtypes/restype for every entry of the header; raises AttributeError when the
     library does not export one of them."""
     fns = {}
-    for name, args in PROTOTYPES.items():
-        fn = getattr(lib, name + suffix)
-        fn.argtypes = list(args) + [C.c_void_p]
-        fn.restype = C.c_int
-        fns[name] = fn
-    if not suffix:
-        var = lib.aivc_conv2d_variant
-        var.argtypes = [_P(ConvParams)]
-        var.restype = C.c_int
-        fns['aivc_conv2d_variant'] = var
-        chk = lib.aivc_selfcheck_gdn_math  # diagnostic of the device arithmetic: no host twin
-        chk.argtypes = [C.c_uint64, C.c_uint32, _f, C.c_void_p]
-        chk.restype = C.c_int
-        fns['aivc_selfcheck_gdn_math'] = chk
-        ev = lib.aivc_detmath_eval  # the deterministic transcendentals, element by element
-        ev.argtypes = list(DETMATH_EVAL_ARGS) + [C.c_void_p]
-        ev.restype = C.c_int
-        fns['aivc_detmath_eval'] = ev
-        hold = lib.aivc_diag_hold_lds  # include/aivc_hip_diag.h: a workgroup that holds LDS for a bounded time
-        hold.argtypes = [C.c_uint32, C.c_uint32, _f, C.c_void_p]
-        hold.restype = C.c_int
-        fns['aivc_diag_hold_lds'] = hold
-        wm = lib.aivc_warp_modes  # include/aivc_hip_warp.h: the warp in every sampling mode, no host twin either
-        wm.argtypes = [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, C.c_void_p]
-        wm.restype = C.c_int
-        fns['aivc_warp_modes'] = wm
-        for name, args in list(COLOR_PROTOTYPES.items()) + list(QUALITY_PROTOTYPES.items()) + list(RATES_PROTOTYPES.items()) \
-                + list(DIGEST_PROTOTYPES.items()) + list(SCENE_PROTOTYPES.items()) + list(RESIZE_PROTOTYPES.items()):
-            fn = getattr(lib, name)
-            fn.argtypes = list(args) + [C.c_void_p]
-            fn.restype = C.c_int
+    for name, args, restype, stream, twin in _BINDINGS:
+        if twin or not suffix:
+            fn = getattr(lib, name + suffix)
+            fn.argtypes = list(args) + ([C.c_void_p] if stream else [])
+            fn.restype = restype
             fns[name] = fn
-    mws = getattr(lib, 'aivc_metrics_workspace' + suffix)
-    mws.argtypes = [_i32, _i32, _i32]
-    mws.restype = C.c_size_t
-    fns['aivc_metrics_workspace'] = mws
-    ver = getattr(lib, 'aivc_abi_version' + suffix)
-    ver.argtypes = []
-    ver.restype = C.c_int
-    fns['aivc_abi_version'] = ver
     return fns
 
 

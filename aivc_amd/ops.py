@@ -103,7 +103,8 @@ def pack_weight(w, c_store=None, transposed=False):
 # that matters (HIP == CPU oracle bit for bit, bitstreams reproducible on every GPU), closer to the reference's outputs on the
 # layer fixtures, and 1.4 ... 1.6x faster on the layers it covers.  AIVC_CONTRACT=fp32 in the environment selects version 1
 # (an encoder and a decoder must run the same version: their bits differ).
-_CONTRACT_NAMES = {'fp32': abi.PREC_FP32, 'fp32w': abi.PREC_FP32_WINO}
+_PRECISION_NAMES = {'fp32': abi.PREC_FP32, 'bf16x3': abi.PREC_BF16X3, 'fp32w': abi.PREC_FP32_WINO}  # what set_precision() takes
+_CONTRACT_NAMES = {k: _PRECISION_NAMES[k] for k in ('fp32', 'fp32w')}  # ... of which the versions of the contract
 DEFAULT_CONTRACT = os.environ.get('AIVC_CONTRACT', 'fp32w')
 if DEFAULT_CONTRACT not in _CONTRACT_NAMES:
     raise ValueError('AIVC_CONTRACT=%r: expected fp32 or fp32w' % DEFAULT_CONTRACT)
@@ -112,7 +113,7 @@ PRECISION = _CONTRACT_NAMES[DEFAULT_CONTRACT]
 
 def precision_name():
     """the name set_precision() knows the current mode by"""
-    return {abi.PREC_FP32: 'fp32', abi.PREC_BF16X3: 'bf16x3', abi.PREC_FP32_WINO: 'fp32w'}[PRECISION]
+    return next(k for k, v in _PRECISION_NAMES.items() if v == PRECISION)
 
 
 def set_precision(mode):
@@ -125,11 +126,10 @@ def set_precision(mode):
     everything else as 'fp32'.  HIP == CPU oracle bit for bit in this version too; its bits are not version 1's.
     -> the previous mode's name.  Process-wide (the codec's side streams read it too)."""
     global PRECISION
-    names = {'fp32': abi.PREC_FP32, 'bf16x3': abi.PREC_BF16X3, 'fp32w': abi.PREC_FP32_WINO}
-    if mode not in names:
-        raise ValueError('precision %r: expected one of %s' % (mode, sorted(names)))
-    prev = [k for k, v in names.items() if v == PRECISION][0]
-    PRECISION = names[mode]
+    if mode not in _PRECISION_NAMES:
+        raise ValueError('precision %r: expected one of %s' % (mode, sorted(_PRECISION_NAMES)))
+    prev = precision_name()
+    PRECISION = _PRECISION_NAMES[mode]
     return prev
 
 
@@ -533,41 +533,96 @@ def yuv8_to_rgb8(y, u, v, chroma_shift=1):
     return rgb
 
 
+def _plane_batch(planes, op, dims=None, stack=True, empty=True):
+    """The planes of one call of `op`: a list of contiguous uint8 CUDA tensors of one size on one device (views into a larger
+    tensor as they are: a plane may start at any byte) or, with stack, one tensor [n, ...] whose rows are the planes.
+    dims: the names of a plane's axes, ('h', 'w'): a plane of a list has that rank, or a leading 1 more, a stack [n, h, w];
+    None: any shape, the planes of a list then only share their byte count.  empty: whether n = 0 is a batch.
+    -> (tensors to keep alive, [address of each plane], shape of a plane, its bytes, device)"""
+    if isinstance(planes, (list, tuple)):
+        keep = [_dev(t, torch.uint8, 'planes[%d]' % i) for i, t in enumerate(planes)]
+        sizes = sorted({t.numel() if dims is None else tuple(t.shape) for t in keep})
+        if len(sizes) > 1:
+            raise ValueError('%s: the planes of one call have one size, got %s' % (op, sizes))
+        if len({t.device for t in keep}) > 1:
+            raise ValueError('%s: planes on several devices' % op)
+        shape = (tuple(keep[0].shape) if dims is not None else (keep[0].numel(),)) if keep else (0,)
+        if dims is not None and keep and not (len(shape) == len(dims) or (len(shape) == len(dims) + 1 and shape[0] == 1)):
+            raise ValueError('%s: expected planes [%s] or [1, %s], got %s' % (op, ', '.join(dims), ', '.join(dims), shape))
+        ptrs, device = [t.data_ptr() for t in keep], keep[0].device if keep else None
+    elif not stack:
+        raise ValueError('%s: expected a list of planes, got %s' % (op, type(planes).__name__))
+    else:
+        planes = _dev(planes, torch.uint8, 'planes')
+        if planes.dim() < 1 or (dims is not None and planes.dim() != len(dims) + 1):
+            raise ValueError('%s: expected [n, %s], got %s' % (op, '...' if dims is None else ', '.join(dims), tuple(planes.shape) or 'a scalar'))
+        n = planes.shape[0]
+        shape = tuple(planes.shape[1:]) if dims is not None else (planes.numel() // n if n else 0,)
+        keep, device = [planes], planes.device
+        ptrs = [planes.data_ptr() + i * (planes.numel() // n) for i in range(n)]
+    if not ptrs:
+        if not empty:
+            raise ValueError('%s: no planes' % op)
+        device = device or torch.device('cuda', torch.cuda.current_device())
+    return keep, ptrs, shape, int(np.prod(shape, dtype=np.int64)), device
+
+
+def _stage_layout(sizes, align=16, slack=0):
+    """where _stage puts arrays of these byte sizes: each on an `align` boundary with `slack` spare bytes behind its padded end
+    -> ([offset of each], bytes of the blob: never none, at least `align`)"""
+    offs, total = [], 0
+    for s in sizes:
+        offs.append(total)
+        total += -(-s // align) * align + slack
+    return offs, max(total, align)
+
+
+_STAGING = []  # [(event recorded behind a pinned buffer's last copy, the buffer: a pinned uint8 tensor)]
+
+
+def _stage(device, arrays, align=16, slack=0):
+    """Small host tables (flat uint8 numpy arrays; range_decode hands in thousands of them a step, so nothing is done per array
+    beyond the copy) -> (uint8 CUDA tensor holding their bytes laid out by _stage_layout and zeros everywhere else, [byte offset of
+    each]).  One pinned staging buffer and one asynchronous copy on the device's current
+    stream: the host never waits.
+    THE RULE OF THE POOL: a pinned buffer goes back to _STAGING only behind an event recorded AFTER its copy, ON THE STREAM the
+    copy was issued on, and is handed out again only once that event has completed.  Released any earlier, or behind an event of
+    another stream, the next call would fill the buffer while the copy still reads it.  Both halves are here and nowhere else."""
+    offs, total = _stage_layout([a.size for a in arrays], align, slack)
+    for i, (ev, buf) in enumerate(_STAGING):
+        if buf.numel() >= total and ev.query():
+            _STAGING.pop(i)
+            break
+    else:
+        buf = torch.empty(max(1 << 20, 1 << (total - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
+    host = buf.numpy()[:total]
+    host[:] = 0
+    for o, a in zip(offs, arrays):
+        host[o:o + a.size] = a
+    blob = torch.empty(total, dtype=torch.uint8, device=device)
+    blob.copy_(buf[:total], non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(blob.device))
+    _STAGING.append((ev, buf))
+    return blob, offs
+
+
 def md5_planes(planes):
     """MD5 of n equal-sized uint8 buffers on the device (include/aivc_hip_digest.h): one message per lane, one launch.
     planes: a contiguous uint8 CUDA tensor [n, ...] (message i is planes[i]), or a list of n contiguous uint8 CUDA tensors of one
     size (views into a batch stack as they are: a message may start at any byte).  -> uint8 [n, 16] on the device, row i the
     digest of message i in RFC 1321 byte order (bytes(row).hex() == hashlib.md5(message).hexdigest()).  No synchronisation: the
     pointer table is one small host-to-device copy, the launch goes on the current stream."""
-    if isinstance(planes, (list, tuple)):
-        planes = [_dev(t, torch.uint8, 'planes[%d]' % i) for i, t in enumerate(planes)]
-        n = len(planes)
-        length = planes[0].numel() if n else 0
-        if any(t.numel() != length for t in planes):
-            raise ValueError('md5_planes: the planes of one call have one size, got %s' % sorted({t.numel() for t in planes}))
-        if len({t.device for t in planes}) > 1:
-            raise ValueError('md5_planes: planes on several devices')
-        device = planes[0].device if n else torch.device('cuda', torch.cuda.current_device())
-        ptrs = [t.data_ptr() for t in planes]
-    else:
-        planes = _dev(planes, torch.uint8, 'planes')
-        if planes.dim() < 1:
-            raise ValueError('md5_planes: expected [n, ...], got a scalar')
-        n = planes.shape[0]
-        length = planes.numel() // n if n else 0
-        device = planes.device
-        ptrs = [planes.data_ptr() + i * length for i in range(n)]
+    keep, ptrs, _, length, device = _plane_batch(planes, 'md5_planes')
+    n = len(ptrs)
     if length >= 1 << 31:
         raise ValueError('md5_planes: %d bytes per plane, the kernel takes less than 2^31' % length)
     out = torch.empty((n, 16), dtype=torch.uint8, device=device)
     if n == 0:
         return out
-    host = _pinned_staging(8 * n)  # (pinned staging and an asynchronous copy, as frame_maps_to_device)
-    host.numpy().view(np.uint64)[:] = np.asarray(ptrs, np.uint64)
-    table = torch.empty(8 * n, dtype=torch.uint8, device=device)
-    table.copy_(host, non_blocking=True)
-    _pinned_release(host)
+    table, _ = _stage(device, [np.asarray(ptrs, np.uint64).view(np.uint8)])
     _hbm_profiled('md5_planes', n * (length + 16), lambda: call('aivc_md5_batch', _p(table), length, n, _p(out), _stream()))
+    del keep
     return out
 
 
@@ -577,28 +632,17 @@ def pair_sad_u8(planes):
     tensors, any alignment).  -> int64 CUDA tensor [max(n - 1, 0)], entry i the exact sum of |planes[i + 1] - planes[i]|.
     No synchronisation: the pointer table is one small host-to-device copy, the two launches go on the current stream.
     n <= 1 launches nothing."""
-    if not isinstance(planes, (list, tuple)):
-        raise ValueError('pair_sad_u8: expected a list of planes, got %s' % type(planes).__name__)
-    planes = [_dev(t, torch.uint8, 'planes[%d]' % i) for i, t in enumerate(planes)]
-    n = len(planes)
-    length = planes[0].numel() if n else 0
-    if any(t.numel() != length for t in planes):
-        raise ValueError('pair_sad_u8: the planes of one call have one size, got %s' % sorted({t.numel() for t in planes}))
-    if len({t.device for t in planes}) > 1:
-        raise ValueError('pair_sad_u8: planes on several devices')
-    device = planes[0].device if n else torch.device('cuda', torch.cuda.current_device())
+    keep, ptrs, _, length, device = _plane_batch(planes, 'pair_sad_u8', stack=False)
+    n = len(ptrs)
     sad = torch.empty((max(n - 1, 0),), dtype=torch.int64, device=device)
     if n <= 1:
         return sad
     if length == 0:
         raise ValueError('pair_sad_u8: empty planes')
-    host = _pinned_staging(8 * n)  # (pinned staging and an asynchronous copy, as md5_planes)
-    host.numpy().view(np.uint64)[:] = np.asarray([t.data_ptr() for t in planes], np.uint64)
-    table = torch.empty(8 * n, dtype=torch.uint8, device=device)
-    table.copy_(host, non_blocking=True)
-    _pinned_release(host)
+    table, _ = _stage(device, [np.asarray(ptrs, np.uint64).view(np.uint8)])
     partials = torch.empty((n - 1, abi.SAD_BLOCKS), dtype=torch.int64, device=device)
     _hbm_profiled('pair_sad_u8', n * length, lambda: call('aivc_pair_sad_u8', _p(table), n, length, _p(partials), _p(sad), _stream()))
+    del keep
     return sad
 
 
@@ -611,26 +655,7 @@ def resize_u8(planes, h_out, w_out, filter='bicubic'):
     A shape the kernels cannot take raises ValueError with the sizes named, before anything is allocated."""
     from . import resize as rs
     rs.check_filter(filter)
-    if isinstance(planes, (list, tuple)):
-        planes = [_dev(t, torch.uint8, 'planes[%d]' % i) for i, t in enumerate(planes)]
-        if not planes:
-            raise ValueError('resize_u8: no planes')
-        shape = tuple(planes[0].shape)
-        if any(tuple(t.shape) != shape for t in planes):
-            raise ValueError('resize_u8: the planes of one call have one size, got %s' % sorted({tuple(t.shape) for t in planes}))
-        if len({t.device for t in planes}) > 1:
-            raise ValueError('resize_u8: planes on several devices')
-        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 1):
-            raise ValueError('resize_u8: expected planes [h, w] or [1, h, w], got %s' % (shape,))
-        ptrs = [t.data_ptr() for t in planes]
-        device = planes[0].device
-    else:
-        planes = _dev(planes, torch.uint8, 'planes')
-        if planes.dim() != 3 or planes.shape[0] < 1:
-            raise ValueError('resize_u8: expected [n, h, w], got %s' % (tuple(planes.shape),))
-        shape = tuple(planes.shape[1:])
-        ptrs = [planes.data_ptr() + i * shape[0] * shape[1] for i in range(planes.shape[0])]
-        device = planes.device
+    keep, ptrs, shape, _, device = _plane_batch(planes, 'resize_u8', ('h', 'w'), empty=False)
     n, (h_in, w_in), h_out, w_out = len(ptrs), shape[-2:], int(h_out), int(w_out)
     if min(h_in, w_in, h_out, w_out) < 1:
         raise ValueError('resize_u8: %d x %d -> %d x %d (w x h): every side must be at least 1' % (w_in, h_in, w_out, h_out))
@@ -645,21 +670,9 @@ def resize_u8(planes, h_out, w_out, filter='bicubic'):
     if xt is not None and xt[2] > abi.RESIZE_MAX_SPAN:
         raise ValueError('resize_u8: %s: a tile of %d output columns reads %d input columns with %d taps, the horizontal pass holds '
                          'at most %d per row' % (what, abi.RESIZE_TILE_W, xt[2], xt[1].shape[0], abi.RESIZE_MAX_SPAN))
-    # one staging buffer: the pointer table, then the tables of the passes, each on a 16-byte boundary
-    parts = [np.asarray(ptrs, np.uint64).view(np.uint8)]
-    for t in (xt, yt):
-        parts += [] if t is None else [np.ascontiguousarray(t[0]).view(np.uint8).reshape(-1), t[1].view(np.uint8).reshape(-1)]
-    offs, total = [], 0
-    for a in parts:
-        offs.append(total)
-        total += -(-a.size // 16) * 16
-    host = _pinned_staging(total)
-    view = host.numpy()
-    for o, a in zip(offs, parts):
-        view[o:o + a.size] = a
-    blob = torch.empty(total, dtype=torch.uint8, device=device)
-    blob.copy_(host, non_blocking=True)
-    _pinned_release(host)
+    # one blob: the pointer table, then the tables of the passes, each on a 16-byte boundary
+    blob, offs = _stage(device, [np.asarray(ptrs, np.uint64).view(np.uint8)]
+                         + [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for t in (xt, yt) if t is not None for a in t[:2]])
     base = blob.data_ptr()
     at = iter(offs[1:])
     xb, xk = (base + next(at), base + next(at)) if xt is not None else (None, None)
@@ -673,6 +686,7 @@ def resize_u8(planes, h_out, w_out, filter='bicubic'):
         call('aivc_resize_u8', base, n, h_in, w_in, h_out, w_out, xb, xk, 0 if xt is None else xt[1].shape[0],
              0 if xt is None else xt[2], yb, yk, _p(tmp), _p(out), _stream())
     _hbm_profiled('resize_u8', n * (h_in * w_in + h_out * w_out), launch)
+    del keep
     return out
 
 
@@ -796,8 +810,9 @@ def _gain_rows(gains, n, c):
 
 
 def _rows_dims(t):
+    """a batch [n, ..., c] -> (n, positions per image, c)"""
     if t.dim() < 2:
-        raise AivcNativeError('a batch with gain rows is [n, ..., c], got %s' % list(t.shape))
+        raise AivcNativeError('a batch is [n, ..., c] (with gain rows: one per image), got %s' % list(t.shape))
     n, c = t.shape[0], t.shape[-1]
     return n, (t.numel() // (n * c) if n * c else 0), c
 
@@ -845,8 +860,7 @@ def balle_cdf_table(params, want_float=False):
 def nonzero_flags(q):
     """q [n,h,w,c] int16 -> device uint8 [n, c] flags, one row per image (no host sync)"""
     q = _dev(q, torch.int16, 'q')
-    n, c = q.shape[0], q.shape[-1]
-    npix = q.numel() // (n * c)
+    n, npix, c = _rows_dims(q)
     flags = torch.empty((n, c), dtype=torch.uint8, device=q.device)
     for i0 in range(0, n, 65535):  # one launch for the whole batch (grid.y = image)
         m = min(65535, n - i0)
@@ -893,20 +907,15 @@ def frame_maps_to_device(maps_list, npix, device):
     """device image of the aivc_frame_maps table of a frame batch (pinned staging, asynchronous copy)
     -> (uint8 CUDA tensor [n, 272], [pos_off per frame], total coded positions)"""
     tab, offs, total = abi.frame_maps_table(maps_list, npix)
-    host = _pinned_staging(tab.size)
-    host.numpy()[:] = tab.reshape(-1)
-    dev = torch.empty(tab.size, dtype=torch.uint8, device=device)
-    dev.copy_(host, non_blocking=True)
-    _pinned_release(host)
-    return dev, offs, total
+    # a frame's 272 bytes are a multiple of 16, so the blob is the table; of no frames it is _stage's least blob, 16 zero bytes
+    return _stage(device, [tab.reshape(-1)])[0], offs, total
 
 
 def laplace_cdf_windows_batch(sigma, maps_list, out, table=None):
     """the windows + sigma of every coded position of a frame batch in ONE launch: sigma [n,h,w,c], maps_list[f] the coded
     channels of frame f, out = (win [>= total, CDF_WIN] int16, sigma_pos [>= total]) -> ([pos_off per frame], table)"""
     sigma = _dev(sigma, torch.float32, 'sigma')
-    n, c = sigma.shape[0], sigma.shape[-1]
-    npix = sigma.numel() // (n * c)
+    n, npix, c = _rows_dims(sigma)
     table = table or frame_maps_to_device(maps_list, npix, sigma.device)
     dev, offs, total = table
     win, sp = out
@@ -921,8 +930,7 @@ def laplace_cdf_windows_batch(sigma, maps_list, out, table=None):
 def laplace_bounds_batch(sigma, q, maps_list):
     """-> (bounds int32 [total], [pos_off per frame]) of a frame batch in one launch"""
     sigma, q = _dev(sigma, torch.float32, 'sigma'), _dev(q, torch.int16, 'q')
-    n, c = sigma.shape[0], sigma.shape[-1]
-    npix = sigma.numel() // (n * c)
+    n, npix, c = _rows_dims(sigma)
     dev, offs, total = frame_maps_to_device(maps_list, npix, sigma.device)
     bounds = torch.empty(max(total, 1), dtype=torch.int32, device=sigma.device)
     mx = max((len(m) for m in maps_list), default=0)
@@ -934,8 +942,7 @@ def laplace_bounds_batch(sigma, q, maps_list):
 def table_bounds_batch(table, q):
     """q [n,h,w,c] -> bounds int32 [n, c * npix] (every channel of every frame, pmf mode) in one launch"""
     q = _dev(q, torch.int16, 'q')
-    n, c = q.shape[0], q.shape[-1]
-    npix = q.numel() // (n * c)
+    n, npix, c = _rows_dims(q)
     bounds = torch.empty((n, c * npix), dtype=torch.int32, device=q.device)
     call('aivc_table_bounds_batch', _p(table), _p(q), n, npix, c, _p(bounds), _stream())
     return bounds
@@ -1024,23 +1031,15 @@ def table_prob(x, cdf_f32):
     return prob
 
 
-_STAGING = []  # [(event or None, pinned uint8 tensor)]
-
-
-def _pinned_staging(n):
-    """pinned host buffer of >= n bytes whose previous H2D copy (if any) has completed"""
-    for i, (ev, buf) in enumerate(_STAGING):
-        if buf.numel() >= n and (ev is None or ev.query()):
-            _STAGING.pop(i)
-            return buf[:n]
-    return torch.empty(max(1 << 20, 1 << (int(n) - 1).bit_length()), dtype=torch.uint8, pin_memory=True)[:n]
-
-
-def _pinned_release(view):
-    ev = torch.cuda.Event()
-    ev.record()
-    base = view._base if view._base is not None else view
-    _STAGING.append((ev, base))
+def _rc_batches(n, fill):
+    """n range-coder streams, abi.RC_MAX_STREAMS to a launch -> (index of its first stream, aivc_rc_batch) per launch;
+    fill(s, i) sets the aivc_rc_stream s of stream i"""
+    for start in range(0, n, abi.RC_MAX_STREAMS):
+        batch = abi.RcBatch()
+        batch.n_streams = min(n - start, abi.RC_MAX_STREAMS)
+        for k in range(batch.n_streams):
+            fill(batch.s[k], start + k)
+        yield start, batch
 
 
 def range_encode(bounds_list, streams=None):
@@ -1079,14 +1078,10 @@ def range_encode(bounds_list, streams=None):
         for t in (allb, out, lens):
             for st in streams:
                 t.record_stream(st)
-    for gi, start in enumerate(range(0, n, abi.RC_MAX_STREAMS)):
-        batch = abi.RcBatch()
-        cnt = 0
-        for i in range(start, min(n, start + abi.RC_MAX_STREAMS)):
-            s_ = batch.s[cnt]
-            s_.in_off, s_.out_off, s_.n_sym, s_.out_cap = in_offs[i], out_offs[i][0], bounds_list[i].numel(), out_offs[i][1]
-            cnt += 1
-        batch.n_streams = cnt
+
+    def fill(s_, i):
+        s_.in_off, s_.out_off, s_.n_sym, s_.out_cap = in_offs[i], out_offs[i][0], bounds_list[i].numel(), out_offs[i][1]
+    for gi, (start, batch) in enumerate(_rc_batches(n, fill)):
         if fork:
             st = streams[gi % len(streams)]
             st.wait_event(ev0)
@@ -1109,35 +1104,21 @@ def range_decode(payloads, rows, row_offs, n_syms, planes, sigma_pos=None, want_
     of the bits each stream consumed (include/aivc_hip.h: len(payload) == (bits + 2 + 7) // 8 for an intact stream)."""
     n = len(payloads)
     dev = rows.device
-    offs, total = [], 0
-    for pl in payloads:
-        offs.append(total)
-        total += len(pl) + (-len(pl)) % 4 + 8
-    host = _pinned_staging(max(total, 4))
-    hv = host.numpy()
-    hv[:] = 0
-    for pl, o in zip(payloads, offs):
-        if len(pl):
-            hv[o:o + len(pl)] = np.frombuffer(pl, np.uint8)
-    dbytes = torch.empty(host.shape, dtype=torch.uint8, device=dev)
-    dbytes.copy_(host, non_blocking=True)  # pinned source: truly asynchronous, the host never waits
-    _pinned_release(host)
-    sym_total = int(sum(n_syms))
-    sym = torch.empty(max(sym_total, 1), dtype=torch.int16, device=dev)
-    outs, so = [], 0
+    # the decoder kernels read past a payload's end by design: every payload is padded to 4 bytes and followed by 8 spare ones,
+    # zeros everywhere outside the payloads, at least 4 bytes in all
+    dbytes, offs = _stage(dev, [np.frombuffer(pl, np.uint8) for pl in payloads], align=4, slack=8)
+    sym_offs = [0]
+    for k in n_syms:
+        sym_offs.append(sym_offs[-1] + k)
+    sym = torch.empty(max(sym_offs[-1], 1), dtype=torch.int16, device=dev)
+    outs = [sym[sym_offs[i]:sym_offs[i + 1]] for i in range(n)]
     bits = torch.empty(n, dtype=torch.int32, device=dev) if want_bits else None
-    for start in range(0, n, abi.RC_MAX_STREAMS):
+
+    def fill(s_, i):
+        s_.in_off, s_.out_off, s_.row_off = offs[i], sym_offs[i], row_offs[i]
+        s_.n_sym, s_.in_len, s_.plane = n_syms[i], len(payloads[i]), planes[i]
+    for start, batch in _rc_batches(n, fill):
         bp = None if bits is None else bits.data_ptr() + 4 * start
-        batch = abi.RcBatch()
-        cnt = 0
-        for i in range(start, min(n, start + abi.RC_MAX_STREAMS)):
-            s_ = batch.s[cnt]
-            s_.in_off, s_.out_off, s_.row_off = offs[i], so, row_offs[i]
-            s_.n_sym, s_.in_len, s_.plane = n_syms[i], len(payloads[i]), planes[i]
-            outs.append(sym[so:so + n_syms[i]])
-            so += n_syms[i]
-            cnt += 1
-        batch.n_streams = cnt
         if sigma_pos is None:
             call('aivc_range_decode', _p(dbytes), _p(rows), C.byref(batch), _p(sym), bp, _stream())
         else:

@@ -557,3 +557,70 @@ def test_estimating_rate_restores_the_flag_when_the_body_raises():
             assert bitstream.ESTIMATE_RATE is previous
     finally:
         bitstream.ESTIMATE_RATE = before
+
+
+@pytest.mark.parametrize('sizes, align, slack', [([0, 1, 15, 16, 17], 16, 0), ([0, 3, 4, 5], 4, 8)])
+def test_stage_layout(sizes, align, slack):
+    """where ops._stage puts its arrays: each on an `align` boundary, `slack` spare bytes behind each, nothing overlapping.  The
+    second case is the layout the range decoder's kernels were written against (they read past a payload's end): each payload
+    padded to 4 bytes plus 8 spare ones, stated here with the formula range_decode used before it called the helper"""
+    from aivc_amd import ops
+    offs, total = ops._stage_layout(sizes, align, slack)
+    if (align, slack) == (16, 0):
+        assert offs == [0, 0, 16, 32, 48] and total == 80
+    else:
+        want, pos = [], 0
+        for n in sizes:
+            want.append(pos)
+            pos += n + (-n) % 4 + 8
+        assert offs == want == [0, 8, 20, 32] and total == max(pos, 4) == 48
+    assert all(o % align == 0 for o in offs)
+    ends = [o + n for o, n in zip(offs, sizes)]
+    assert all(e + slack <= nxt for e, nxt in zip(ends, offs[1:] + [total]))  # in order, so: no two ranges share a byte
+    assert ops._stage_layout([], 4, 8) == ([], 4)  # (range_decode of no stream still hands the kernels a buffer)
+
+
+DECLARED_WITH_A_REF_TWIN = [
+    'aivc_ssim_means', 'aivc_pool2x2', 'aivc_sq_err', 'aivc_conv2d', 'aivc_gdn_reparam', 'aivc_split_weights_bf16x3',
+    'aivc_winograd_weights', 'aivc_winograd_weights_poly5', 'aivc_winograd_weights_tconv5', 'aivc_pad_channels',
+    'aivc_yuv420_to_444', 'aivc_yuv420u8_to_444', 'aivc_pack_images', 'aivc_conv_images', 'aivc_frame_to_yuv420',
+    'aivc_downsample2x', 'aivc_warp_blend', 'aivc_warp_blend_rows', 'aivc_warp', 'aivc_hyper_params', 'aivc_channel_gain',
+    'aivc_gain_interp', 'aivc_quantize_center', 'aivc_dequantize', 'aivc_balle_cdf_table', 'aivc_nonzero_maps',
+    'aivc_nonzero_maps_batch', 'aivc_laplace_cdf_rows', 'aivc_laplace_cdf_windows', 'aivc_laplace_bounds', 'aivc_table_bounds',
+    'aivc_range_encode', 'aivc_range_decode', 'aivc_range_decode_windows', 'aivc_scatter_symbols',
+    'aivc_laplace_cdf_windows_batch', 'aivc_laplace_bounds_batch', 'aivc_table_bounds_batch', 'aivc_scatter_symbols_batch',
+    'aivc_bounds_rate', 'aivc_rate_bits', 'aivc_laplace_prob', 'aivc_table_prob', 'aivc_metrics_workspace', 'aivc_abi_version']
+DECLARED_ON_THE_DEVICE_ONLY = [
+    'aivc_conv2d_variant', 'aivc_selfcheck_gdn_math', 'aivc_detmath_eval', 'aivc_diag_hold_lds', 'aivc_warp_modes',
+    'aivc_rgb8_to_yuv420u8', 'aivc_yuv8_to_rgb8', 'aivc_frame_sse_u8', 'aivc_frame_aux_stats', 'aivc_channel_gain_rows',
+    'aivc_quantize_center_rows', 'aivc_dequantize_rows', 'aivc_md5_batch', 'aivc_pair_sad_u8', 'aivc_resize_u8']
+
+
+def test_declare_binds_these_names_and_no_others():
+    """abi.declare on a stand-in library that records what is looked up: the device library is asked for every name of the two
+    lists, the oracle ('_ref') for the first list's twins only, and each bound entry carries its stream argument"""
+    from aivc_amd import abi
+
+    class Fn:
+        pass
+
+    class Lib:
+        def __init__(self):
+            self.asked = {}
+
+        def __getattr__(self, name):
+            return self.asked.setdefault(name, Fn())
+
+    for suffix, names in (('', DECLARED_WITH_A_REF_TWIN + DECLARED_ON_THE_DEVICE_ONLY), ('_ref', DECLARED_WITH_A_REF_TWIN)):
+        lib = Lib()
+        fns = abi.declare(lib, suffix)
+        assert sorted(fns) == sorted(names) and len(set(names)) == len(names)
+        assert sorted(lib.asked) == sorted(n + suffix for n in names)
+        assert all(fns[n] is lib.asked[n + suffix] for n in names)
+    assert fns['aivc_conv2d'].argtypes == [ctypes.POINTER(abi.ConvParams), ctypes.c_void_p] and fns['aivc_conv2d'].restype is ctypes.c_int
+    assert fns['aivc_metrics_workspace'].argtypes == [ctypes.c_int32] * 3 and fns['aivc_metrics_workspace'].restype is ctypes.c_size_t
+    assert fns['aivc_abi_version'].argtypes == []
+    dev = abi.declare(Lib())
+    assert dev['aivc_conv2d_variant'].argtypes == [ctypes.POINTER(abi.ConvParams)]  # (no stream: nothing is launched)
+    assert dev['aivc_detmath_eval'].argtypes == abi.DETMATH_EVAL_ARGS + [ctypes.c_void_p]
+    assert dev['aivc_md5_batch'].argtypes == abi.DIGEST_PROTOTYPES['aivc_md5_batch'] + [ctypes.c_void_p]

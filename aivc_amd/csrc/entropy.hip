@@ -11,18 +11,15 @@
 //   scatter_symbols      one thread per (pixel, 8 channels)   decoder: symbols back into the latent
 //   The last four run per frame BATCH (blockIdx.y = frame) and exist once: a single-frame entry point launches the
 //   same kernel as the one-frame batch, with the map list passed by value instead of read from the device table.
-// Range coder (format-mandated: ONE serial stream per latent section):
-//   one 64-lane wavefront per stream, streams of a batch run concurrently on different CUs.
-//   All coder state is wave-uniform, so it lives in SGPRs / the scalar ALU; the vector lanes are
-//   used for what is parallel inside one symbol step:
-//     encode: lanes fetch 64 packed (c_lo,c_hi) pairs at once (coalesced), v_readlane feeds the
-//             scalar update; E1/E2/E3 renormalisation loops are collapsed into clz-based closed
-//             forms (s_flbit), bits are packed MSB-first through a 64-bit shifter.
-//     decode: each lane owns 8 consecutive CDF entries of the symbol's row (one 16-byte load,
-//             prefetched two groups ahead because the row address never depends on coder state);
-//             "largest m with cdf[m] <= count" is a ballot + popcount instead of torchac's
-//             10-step binary search.
-#include <stdlib.h>
+// Range coder (format-mandated: ONE serial stream per latent section); E1/E2/E3 renormalisation loops are collapsed
+// into clz-based closed forms, bits are packed MSB-first through a 64-bit shifter:
+//   encode: one stream per LANE, a batch of up to 64 streams is one workgroup of three wavefronts
+//           (range_encode_lanes_kernel); all coder state is per-lane VGPR data.
+//   decode: one 64-lane wavefront per stream (+ a prefetching one), streams of a batch run concurrently on
+//           different CUs.  All coder state is wave-uniform, so it lives in SGPRs / the scalar ALU; each lane owns
+//           one CDF entry of the 64-entry window of the symbol's row (prefetched by LDS-DMA because the row address
+//           never depends on coder state); "largest m with cdf[m] <= count" is a ballot + popcount instead of
+//           torchac's 10-step binary search.
 #include <string.h>
 
 #include "common.h"
@@ -249,7 +246,7 @@ __global__ __launch_bounds__(256) void table_bounds_batch_kernel(const uint16_t 
   bounds[(size_t)blockIdx.y * c * npix + pos] = (uint32_t)row[sym] | (sym == AIVC_MAX_SYMBOL ? 0u : (uint32_t)row[sym + 1] << 16);
 }
 
-// ------------------------------------------------------------------ range encoder
+// ------------------------------------------------------------------ range coder: what both directions use
 __device__ __forceinline__ uint32_t rl(uint32_t v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
 // t = (span * e) >> 16 with span = hl + 1 (up to 2^32): e * hl + e < 2^48, exact in ONE v_mad_u64_u32 (written out:
@@ -263,118 +260,13 @@ __device__ __forceinline__ uint32_t scaled(uint32_t e, uint32_t hl) {
   return t;
 }
 
-// MSB-first bit packer.  All state is wave-uniform (SGPRs); a 32-bit word is stored (every lane issues the same
-// store: one transaction) only when it is complete -- at the ~1 bit per symbol of these latents that is one store
-// per ~30 symbols instead of one per call -- behind a wave-uniform branch.  finish() writes the partial last word.
-struct BitSink {
-  uint32_t *out;       // 4-byte aligned
-  uint32_t cap_words;  // capacity in 32-bit words (>= 1)
-  uint32_t n_words;
-  uint64_t acc;        // the low `nbits` bits are pending output
-  uint32_t nbits;      // < 32 between calls
-  uint32_t overflow;
-  __device__ __forceinline__ void put(uint32_t bits, uint32_t nb) {  // nb in [0, 32]
-    acc = (acc << nb) | (uint64_t)bits;
-    nbits += nb;
-    if (nbits >= 32) {
-      nbits -= 32;
-      const uint32_t w = (uint32_t)(acc >> nbits);
-      if (n_words < cap_words) out[n_words] = __builtin_bswap32(w);
-      else overflow = 1;
-      n_words++;
-    }
-  }
-  __device__ __forceinline__ void put_run(uint32_t bit, uint32_t count) {
-    while (count > 0) {
-      const uint32_t r = count > 32 ? 32 : count;
-      const uint32_t ones = r == 32 ? 0xFFFFFFFFu : ((1u << r) - 1u);
-      put(bit ? ones : 0u, r);
-      count -= r;
-    }
-  }
-  __device__ __forceinline__ void finish() {  // bits left over after the last complete word: MSB aligned, zero padded
-    if (nbits > 0) {
-      const uint32_t w = (uint32_t)(acc << (32 - nbits));
-      if (n_words < cap_words) out[n_words] = __builtin_bswap32(w);
-      else overflow = 1;
-    }
-  }
-};
-
-__global__ __launch_bounds__(64) void range_encode_kernel(const uint32_t *__restrict__ bounds, aivc_rc_batch batch,
-                                                          uint8_t *__restrict__ out, uint32_t *__restrict__ out_len) {
-  const aivc_rc_stream st = batch.s[blockIdx.x];
-  const int lane = threadIdx.x;
-  // latency-critical serial wave: win the issue arbitration against co-resident conv waves
-  __builtin_amdgcn_s_setprio(3);
-  BitSink sink{reinterpret_cast<uint32_t *>(out + st.out_off), st.out_cap / 4, 0, 0, 0, 0};
-  uint32_t low = 0, high = 0xFFFFFFFFu, pending = 0;
-  const uint32_t *src = bounds + st.in_off;
-  // 64 symbols per block, lane j holds the bounds of symbol base + j.  Per symbol both interval ends
-  // t = (span * c) >> 16 are one v_mad_u64_u32 each over the whole block (lane j's result is the one read back):
-  // 6 instructions instead of the ~18 of two 33 x 16 bit products on the scalar unit.  The next block's bounds are
-  // in flight while this one is coded.
-  uint32_t nxt = lane < (int)st.n_sym ? src[lane] : 0u;
-#pragma unroll 1
-  for (uint32_t base = 0; base < st.n_sym; base += 64) {
-    const uint32_t mine = nxt;
-    nxt = (base + 64u + lane < st.n_sym) ? src[base + 64u + lane] : 0u;
-    const uint32_t vlo = mine & 0xFFFFu, vhi = (mine >> 16) ? (mine >> 16) : 0x10000u;  // 0 = 2^16: symbol 512
-    const uint32_t cnt = min(64u, st.n_sym - base);
-#pragma unroll 1
-    for (uint32_t j = 0; j < cnt; ++j) {
-      const uint32_t hl = high - low;  // span - 1
-      const uint32_t t_lo = rl(scaled(vlo, hl), (int)j), t_hi = rl(scaled(vhi, hl), (int)j);
-      high = low + t_hi - 1u;
-      low = low + t_lo;
-      // E1 / E2: the n leading bits on which low and high agree are final (low < high: n <= 31); nothing to do
-      // for the many symbols that settle no bit
-      const uint32_t x = low ^ high;
-      if ((int32_t)x >= 0) {
-        const uint32_t n = (uint32_t)__builtin_clz(x | 1u);
-        const uint32_t top = (uint32_t)(((uint64_t)low << n) >> 32);  // the n leading bits of low
-        uint32_t bits = top, nb = n;
-        if (pending != 0) {  // the first settled bit releases the pending straddle bits (its complement)
-          const uint32_t b0 = low >> 31;
-          sink.put(b0, 1);
-          sink.put_run(b0 ^ 1u, pending);
-          pending = 0;
-          nb = n - 1u;
-          bits = top & ((1u << nb) - 1u);
-        }
-        sink.put(bits, nb);
-        low <<= n;
-        high = (high << n) | ~(0xFFFFFFFFu << n);
-      }
-      asm volatile("" : "+s"(high));  // keeps the test below on the scalar unit
-      // E3: now low = 0..., high = 1...; every further position with (low,high) = (1,0) straddles
-      const uint32_t yy = low & ~high;
-      if (yy & 0x40000000u) {
-        const uint32_t m = (uint32_t)__builtin_clz(~(yy << 1));  // leading ones (1..31)
-        pending += m;
-        low = (low << m) & 0x7FFFFFFFu;
-        high = (high << m) | 0x80000000u | ((1u << m) - 1u);
-      }
-    }
-  }
-  pending += 1;
-  const uint32_t fb = low < 0x40000000u ? 0u : 1u;
-  sink.put(fb, 1);
-  sink.put_run(fb ^ 1u, pending);
-  sink.finish();
-  // count the bytes of the partial last word
-  const uint32_t total = sink.n_words * 4u + (sink.nbits + 7u) / 8u;
-  if (total > st.out_cap) sink.overflow = 1;
-  if (lane == 0) out_len[blockIdx.x] = sink.overflow ? 0xFFFFFFFFu : total;
-}
-
 // ------------------------------------------------------------------ range encoder, one stream per LANE (round 5)
 // What a lone wavefront pays (tools/lat_probe.hip, profiles/r05_lat_probe.txt): 4 cycles per instruction of any kind,
 // dependent or not; +10 for a branch not taken, +24 taken, +25 when it tests a VALU compare; +16..20 for every
-// VALU -> SGPR -> SALU crossing; 18 for v_mad_u64_u32 + shift in a chain.  The wave-per-stream encoder above pays two
-// crossings and two to four branches per symbol: 0.09 us per symbol when nothing settles, 0.16-0.18 at 2-6 bit per
-// symbol -- and a launch of 64 streams occupies 64 wavefronts on 64 CUs for as long as its longest stream, next to the
-// convolutions.  Here a stream is a LANE: all state is per-lane VGPR data, every step is straight-line VALU code
+// VALU -> SGPR -> SALU crossing; 18 for v_mad_u64_u32 + shift in a chain.  A wave-per-stream encoder (round 4, state in
+// SGPRs) paid two crossings and two to four branches per symbol: 0.09 us per symbol when nothing settles, 0.16-0.18 at
+// 2-6 bit per symbol -- and a launch of 64 streams occupied 64 wavefronts on 64 CUs for as long as its longest stream,
+// next to the convolutions.  Here a stream is a LANE: all state is per-lane VGPR data, every step is straight-line VALU code
 // (selects, no branch per symbol, so the cost does not depend on the bit rate), no cross-lane traffic, and the serial
 // chain is split over TWO wavefronts of one workgroup that run on different SIMDs:
 //   wave A  the interval arithmetic, the chain that is serial by format (30 instructions per symbol):
@@ -847,10 +739,21 @@ __device__ __forceinline__ void decode_prefetcher(const uint16_t *__restrict__ r
   }
 }
 
-__global__ __launch_bounds__(128) void range_decode_kernel(const uint8_t *__restrict__ bytes,
-                                                           const uint16_t *__restrict__ rows, aivc_rc_batch batch,
+// One workgroup per stream: wave 0 decodes, wave 1 prefetches.  WINDOWED: `rows` holds the 64-entry windows and
+// `sigma_pos` the sigma of every position; else `rows` holds full rows and the stream's `plane` chooses PLANE at run time.
+// SIGMA_POS is (const float *) when WINDOWED and nothing otherwise: the full-row form has no such kernel argument (an
+// unused one moves the offsets of those behind it).
+template <bool WINDOWED, class... SIGMA_POS>
+__global__ __launch_bounds__(128) void range_decode_kernel(const uint8_t *__restrict__ bytes, const uint16_t *__restrict__ rows,
+                                                           SIGMA_POS... sigma_pos, aivc_rc_batch batch,
                                                            uint16_t *__restrict__ sym, uint32_t *__restrict__ consumed) {
+  static_assert(sizeof...(SIGMA_POS) == (WINDOWED ? 1 : 0), "sigma_pos goes with the windows");
   __shared__ uint32_t ring[DEC_SLOTS * 64];  // the DMA writes one dword per lane (a ushort load lands zero-extended at lane * 4)
+  float *sigma_ring = nullptr;
+  if constexpr (WINDOWED) {
+    __shared__ float sigmas[2 * DEC_HALF];
+    sigma_ring = sigmas;
+  }
   const aivc_rc_stream st = batch.s[blockIdx.x];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -858,37 +761,19 @@ __global__ __launch_bounds__(128) void range_decode_kernel(const uint8_t *__rest
     if (consumed && threadIdx.x == 0) consumed[blockIdx.x] = 0;
     return;
   }
-  __builtin_amdgcn_s_setprio(3);  // latency-critical serial wave (see range_encode_kernel)
+  // latency-critical serial wave: win the issue arbitration against co-resident conv waves (the convolutions' priority
+  // instead measured the same: 74.3 vs 74.0 fps at high rate)
+  __builtin_amdgcn_s_setprio(3);
   if (wave == 1) {
-    if (st.plane) decode_prefetcher<true>(rows, st, ring, lane);
+    if constexpr (WINDOWED) decode_prefetcher<false, true>(rows, st, ring, lane, sigma_pos..., sigma_ring);
+    else if (st.plane) decode_prefetcher<true>(rows, st, ring, lane);
     else decode_prefetcher<false>(rows, st, ring, lane);
     return;
   }
   uint32_t bits;
-  if (st.plane) bits = decode_stream<true>(bytes, rows, st, sym, ring, lane);
+  if constexpr (WINDOWED) bits = decode_stream<false, true>(bytes, rows, st, sym, ring, lane, sigma_ring);
+  else if (st.plane) bits = decode_stream<true>(bytes, rows, st, sym, ring, lane);
   else bits = decode_stream<false>(bytes, rows, st, sym, ring, lane);
-  if (consumed && lane == 0) consumed[blockIdx.x] = bits;
-}
-
-__global__ __launch_bounds__(128) void range_decode_windows_kernel(const uint8_t *__restrict__ bytes,
-                                                                   const uint16_t *__restrict__ win,
-                                                                   const float *__restrict__ sigma_pos, aivc_rc_batch batch,
-                                                                   uint16_t *__restrict__ sym, uint32_t *__restrict__ consumed) {
-  __shared__ uint32_t ring[DEC_SLOTS * 64];
-  __shared__ float sigma_ring[2 * DEC_HALF];
-  const aivc_rc_stream st = batch.s[blockIdx.x];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (st.n_sym == 0) {
-    if (consumed && threadIdx.x == 0) consumed[blockIdx.x] = 0;
-    return;
-  }
-  __builtin_amdgcn_s_setprio(3);  // (the convolutions' priority instead measured the same: 74.3 vs 74.0 fps at high rate)
-  if (wave == 1) {
-    decode_prefetcher<false, true>(win, st, ring, lane, sigma_pos, sigma_ring);
-    return;
-  }
-  const uint32_t bits = decode_stream<false, true>(bytes, win, st, sym, ring, lane, sigma_ring);
   if (consumed && lane == 0) consumed[blockIdx.x] = bits;
 }
 
@@ -945,32 +830,26 @@ AIVC_EXPORT int aivc_laplace_cdf_rows(const float *sigma, size_t npix, int32_t c
   return check_launch("laplace_cdf_rows");
 }
 
-AIVC_EXPORT int aivc_laplace_bounds(const float *sigma, const int16_t *q, size_t npix, int32_t c,
-                                    const aivc_map_list *maps, uint32_t *bounds, aivc_stream_t stream) {
-  if (!sigma || !q || !bounds || c <= 0) return AIVC_ERR_ARG;
-  if (int rc = check_maps(maps, c)) return rc;
-  const size_t total = (size_t)maps->n_maps * npix;
-  if (total == 0) return AIVC_OK;
-  hipLaunchKernelGGL(laplace_bounds_batch_kernel<aivc_frame_maps>, dim3(cdiv(total, 256)), dim3(256), 0, to_stream(stream),
-                     sigma, q, npix, c, one_frame(maps), bounds);
-  return check_launch("laplace_bounds");
+// ---- the per-batch steps: each launch written once, for both frame sources -----------------------------------------
+// FRAMES = FrameTable with `n` frames, or one (checked) aivc_frame_maps by value with n = 1.  grid.x covers `max_maps`,
+// the batch's longest map list; `what` is the entry point's name in the error report.
+template <class FRAMES>
+static int launch_cdf_windows(const char *what, const float *sigma, int32_t n, size_t npix, int32_t c, const FRAMES frames,
+                              int32_t max_maps, uint16_t *win, float *sigma_pos, aivc_stream_t stream) {
+  const size_t n_pos = (size_t)max_maps * npix;
+  if (n_pos == 0) return AIVC_OK;
+  const size_t total = ((n_pos + 63) / 64) * (CDF_WIN / 8) * 64;  // a wavefront per (64 positions, chunk)
+  hipLaunchKernelGGL(laplace_cdf_windows_batch_kernel<FRAMES>, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream),
+                     sigma, npix, c, frames, win, sigma_pos);
+  return check_launch(what);
 }
 
-AIVC_EXPORT int aivc_table_bounds(const uint16_t *table, const int16_t *q, size_t npix, int32_t c, uint32_t *bounds,
-                                  aivc_stream_t stream) {
-  return aivc_table_bounds_batch(table, q, 1, npix, c, bounds, stream);
-}
-
-AIVC_EXPORT int aivc_scatter_symbols(const uint16_t *sym, size_t npix, int32_t c, const aivc_map_list *maps,
-                                     int16_t *q, aivc_stream_t stream) {
-  if (!q || c <= 0) return AIVC_ERR_ARG;
+AIVC_EXPORT int aivc_laplace_cdf_windows(const float *sigma, size_t npix, int32_t c, const aivc_map_list *maps,
+                                         uint16_t *win, float *sigma_pos, aivc_stream_t stream) {
+  if (!sigma || !win || !sigma_pos || c <= 0) return AIVC_ERR_ARG;
   if (int rc = check_maps(maps, c)) return rc;
-  if (maps->n_maps > 0 && !sym) return AIVC_ERR_ARG;
-  if (npix == 0) return AIVC_OK;
-  const int vec = (c & 7) == 0 && ((uintptr_t)q & 15) == 0;
-  hipLaunchKernelGGL(scatter_symbols_batch_kernel<aivc_frame_maps>, dim3(cdiv(npix * ((c + 7) / 8), 256)), dim3(256), 0,
-                     to_stream(stream), sym, npix, c, one_frame(maps), q, vec);
-  return check_launch("scatter_symbols");
+  return launch_cdf_windows<aivc_frame_maps>("laplace_cdf_windows", sigma, 1, npix, c, one_frame(maps), maps->n_maps, win, sigma_pos,
+                                             stream);
 }
 
 AIVC_EXPORT int aivc_laplace_cdf_windows_batch(const float *sigma, int32_t n, size_t npix, int32_t c,
@@ -978,12 +857,24 @@ AIVC_EXPORT int aivc_laplace_cdf_windows_batch(const float *sigma, int32_t n, si
                                                float *sigma_pos, aivc_stream_t stream) {
   if (!sigma || !frames || !win || !sigma_pos || c <= 0 || c > AIVC_MAX_MAPS || n <= 0 || n > 65535 || max_maps < 0 || max_maps > c)
     return AIVC_ERR_ARG;
-  const size_t n_pos = (size_t)max_maps * npix;
-  if (n_pos == 0) return AIVC_OK;
-  const size_t total = ((n_pos + 63) / 64) * (CDF_WIN / 8) * 64;
-  hipLaunchKernelGGL(laplace_cdf_windows_batch_kernel<FrameTable>, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream),
-                     sigma, npix, c, frames, win, sigma_pos);
-  return check_launch("laplace_cdf_windows_batch");
+  return launch_cdf_windows<FrameTable>("laplace_cdf_windows_batch", sigma, n, npix, c, frames, max_maps, win, sigma_pos, stream);
+}
+
+template <class FRAMES>
+static int launch_laplace_bounds(const char *what, const float *sigma, const int16_t *q, int32_t n, size_t npix, int32_t c,
+                                 const FRAMES frames, int32_t max_maps, uint32_t *bounds, aivc_stream_t stream) {
+  const size_t total = (size_t)max_maps * npix;
+  if (total == 0) return AIVC_OK;
+  hipLaunchKernelGGL(laplace_bounds_batch_kernel<FRAMES>, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream), sigma, q,
+                     npix, c, frames, bounds);
+  return check_launch(what);
+}
+
+AIVC_EXPORT int aivc_laplace_bounds(const float *sigma, const int16_t *q, size_t npix, int32_t c,
+                                    const aivc_map_list *maps, uint32_t *bounds, aivc_stream_t stream) {
+  if (!sigma || !q || !bounds || c <= 0) return AIVC_ERR_ARG;
+  if (int rc = check_maps(maps, c)) return rc;
+  return launch_laplace_bounds<aivc_frame_maps>("laplace_bounds", sigma, q, 1, npix, c, one_frame(maps), maps->n_maps, bounds, stream);
 }
 
 AIVC_EXPORT int aivc_laplace_bounds_batch(const float *sigma, const int16_t *q, int32_t n, size_t npix, int32_t c,
@@ -991,11 +882,7 @@ AIVC_EXPORT int aivc_laplace_bounds_batch(const float *sigma, const int16_t *q, 
                                           aivc_stream_t stream) {
   if (!sigma || !q || !frames || !bounds || c <= 0 || c > AIVC_MAX_MAPS || n <= 0 || n > 65535 || max_maps < 0 || max_maps > c)
     return AIVC_ERR_ARG;
-  const size_t total = (size_t)max_maps * npix;
-  if (total == 0) return AIVC_OK;
-  hipLaunchKernelGGL(laplace_bounds_batch_kernel<FrameTable>, dim3(cdiv(total, 256), (unsigned)n), dim3(256), 0, to_stream(stream), sigma, q,
-                     npix, c, frames, bounds);
-  return check_launch("laplace_bounds_batch");
+  return launch_laplace_bounds<FrameTable>("laplace_bounds_batch", sigma, q, n, npix, c, frames, max_maps, bounds, stream);
 }
 
 AIVC_EXPORT int aivc_table_bounds_batch(const uint16_t *table, const int16_t *q, int32_t n, size_t npix, int32_t c,
@@ -1007,16 +894,36 @@ AIVC_EXPORT int aivc_table_bounds_batch(const uint16_t *table, const int16_t *q,
   return check_launch("table_bounds_batch");
 }
 
+AIVC_EXPORT int aivc_table_bounds(const uint16_t *table, const int16_t *q, size_t npix, int32_t c, uint32_t *bounds,
+                                  aivc_stream_t stream) {
+  return aivc_table_bounds_batch(table, q, 1, npix, c, bounds, stream);
+}
+
+template <class FRAMES>
+static int launch_scatter(const char *what, const uint16_t *sym, int32_t n, size_t npix, int32_t c, const FRAMES frames, int16_t *q,
+                          aivc_stream_t stream) {
+  if (npix == 0) return AIVC_OK;
+  const int vec = (c & 7) == 0 && ((uintptr_t)q & 15) == 0;
+  hipLaunchKernelGGL(scatter_symbols_batch_kernel<FRAMES>, dim3(cdiv(npix * ((c + 7) / 8), 256), (unsigned)n), dim3(256), 0,
+                     to_stream(stream), sym, npix, c, frames, q, vec);
+  return check_launch(what);
+}
+
+AIVC_EXPORT int aivc_scatter_symbols(const uint16_t *sym, size_t npix, int32_t c, const aivc_map_list *maps,
+                                     int16_t *q, aivc_stream_t stream) {
+  if (!q || c <= 0) return AIVC_ERR_ARG;
+  if (int rc = check_maps(maps, c)) return rc;
+  if (maps->n_maps > 0 && !sym) return AIVC_ERR_ARG;
+  return launch_scatter<aivc_frame_maps>("scatter_symbols", sym, 1, npix, c, one_frame(maps), q, stream);
+}
+
 AIVC_EXPORT int aivc_scatter_symbols_batch(const uint16_t *sym, int32_t n, size_t npix, int32_t c,
                                            const aivc_frame_maps *frames, int16_t *q, aivc_stream_t stream) {
   if (!q || !frames || !sym || c <= 0 || c > AIVC_MAX_MAPS || n <= 0 || n > 65535) return AIVC_ERR_ARG;
-  if (npix == 0) return AIVC_OK;
-  const int vec = (c & 7) == 0 && ((uintptr_t)q & 15) == 0;
-  hipLaunchKernelGGL(scatter_symbols_batch_kernel<FrameTable>, dim3(cdiv(npix * ((c + 7) / 8), 256), (unsigned)n), dim3(256), 0,
-                     to_stream(stream), sym, npix, c, frames, q, vec);
-  return check_launch("scatter_symbols_batch");
+  return launch_scatter<FrameTable>("scatter_symbols_batch", sym, n, npix, c, frames, q, stream);
 }
 
+// ---- range coder ------------------------------------------------------------------------------------------------------
 static int check_batch(const aivc_rc_batch *b) {
   if (!b || b->n_streams < 0 || b->n_streams > AIVC_RC_MAX_STREAMS) return AIVC_ERR_ARG;
   return AIVC_OK;
@@ -1027,76 +934,66 @@ AIVC_EXPORT int aivc_range_encode(const uint32_t *bounds, const aivc_rc_batch *b
   if (!out || !out_len) return AIVC_ERR_ARG;
   if (int rc = check_batch(batch)) return rc;
   if (batch->n_streams == 0) return AIVC_OK;
+  uint32_t longest = 0;
   for (int i = 0; i < batch->n_streams; ++i) {
     if (batch->s[i].out_off % 4) return AIVC_ERR_ARG;
-    // whole 32-bit words only (both encoders store words), and at least one: the lane packer's last-word clamp is
-    // out_cap / 4 - 1
+    // whole 32-bit words only (the packer stores words), and at least one: its last-word clamp is out_cap / 4 - 1
     if (batch->s[i].out_cap < 4 || batch->s[i].out_cap % 4) return AIVC_ERR_ARG;
     if (batch->s[i].n_sym && !bounds) return AIVC_ERR_ARG;
+    longest = batch->s[i].n_sym > longest ? batch->s[i].n_sym : longest;
   }
-  // one stream per lane (one wavefront for the whole batch) unless AIVC_RC_ENCODE=wave asks for the wave-per-stream kernel
-  const char *mode = getenv("AIVC_RC_ENCODE");  // (read per call: the tests run both kernels in one process)
-  if (mode && !strcmp(mode, "wave"))
-    hipLaunchKernelGGL(range_encode_kernel, dim3(batch->n_streams), dim3(64), 0, to_stream(stream), bounds, *batch, out, out_len);
-  else {
-    // A long launch asks for LDS it does not use, so that no convolution workgroup (16-100 KB of ring each) fits beside it
-    // on its CU: a coder wave that shares its SIMD with matrix-pipe waves runs 3.5-4x slower (every one of its dependent
-    // instructions waits for the issue port: tools/bench_rangecoder.py LOAD=1, 0.07 -> 0.29 us per symbol), and at high
-    // rate the last level's streams are the encoder's tail.  One CU of 256 for the duration of the launch; short launches
-    // (hidden under the transforms anyway) take what is free.
-    static const int own_cu = getenv("AIVC_RC_OWN_CU") ? atoi(getenv("AIVC_RC_OWN_CU")) : 1;  // tuning aid: 0 = never
-    uint32_t longest = 0;
-    for (int i = 0; i < batch->n_streams; ++i) longest = batch->s[i].n_sym > longest ? batch->s[i].n_sym : longest;
-    size_t pad_lds = 0;
-    if (own_cu && longest >= 65536u) {
-      static LdsOptIn opt_in;
-      pad_lds = 100 * 1024;  // + 48.5 KB of its own: 11 KB of the CU's 160 left
-      if (!opt_in.raise(reinterpret_cast<const void *>(range_encode_lanes_kernel), pad_lds)) pad_lds = 0;
-    }
-    hipLaunchKernelGGL(range_encode_lanes_kernel, dim3(1), dim3(192), pad_lds, to_stream(stream), bounds, *batch, out, out_len);
+  // A long launch asks for LDS it does not use, so that no convolution workgroup (16-100 KB of ring each) fits beside it
+  // on its CU: a coder wave that shares its SIMD with matrix-pipe waves runs 3.5-4x slower (every one of its dependent
+  // instructions waits for the issue port: tools/bench_rangecoder.py LOAD=1, 0.07 -> 0.29 us per symbol), and at high
+  // rate the last level's streams are the encoder's tail.  One CU of 256 for the duration of the launch; short launches
+  // (hidden under the transforms anyway) take what is free.  (Measured: experiments/r05.md.)
+  size_t pad_lds = 0;
+  if (longest >= 65536u) {
+    static LdsOptIn opt_in;
+    pad_lds = 100 * 1024;  // + 48.5 KB of its own: 11 KB of the CU's 160 left
+    if (!opt_in.raise(reinterpret_cast<const void *>(range_encode_lanes_kernel), pad_lds)) pad_lds = 0;
   }
+  // one stream per lane: one workgroup for the whole batch
+  hipLaunchKernelGGL(range_encode_lanes_kernel, dim3(1), dim3(192), pad_lds, to_stream(stream), bounds, *batch, out, out_len);
   return check_launch("range_encode");
 }
 
-AIVC_EXPORT int aivc_laplace_cdf_windows(const float *sigma, size_t npix, int32_t c, const aivc_map_list *maps,
-                                         uint16_t *win, float *sigma_pos, aivc_stream_t stream) {
-  if (!sigma || !win || !sigma_pos || c <= 0) return AIVC_ERR_ARG;
-  if (int rc = check_maps(maps, c)) return rc;
-  const size_t n_pos = (size_t)maps->n_maps * npix;
-  if (n_pos == 0) return AIVC_OK;
-  const size_t total = ((n_pos + 63) / 64) * (CDF_WIN / 8) * 64;  // a wavefront per (64 positions, chunk)
-  hipLaunchKernelGGL(laplace_cdf_windows_batch_kernel<aivc_frame_maps>, dim3(cdiv(total, 256)), dim3(256), 0, to_stream(stream),
-                     sigma, npix, c, one_frame(maps), win, sigma_pos);
-  return check_launch("laplace_cdf_windows");
+// What both decode entry points check before their own.  -> false: nothing to launch, return *rc (an error, or AIVC_OK
+// for the empty batch)
+static bool decode_batch(const void *bytes, const void *rows, const void *sym, const aivc_rc_batch *batch, int *rc) {
+  *rc = !bytes || !rows || !sym ? AIVC_ERR_ARG : check_batch(batch);
+  if (*rc || batch->n_streams == 0) return false;
+  for (int i = 0; i < batch->n_streams; ++i)
+    if (batch->s[i].in_off % 4) *rc = AIVC_ERR_ARG;
+  return *rc == AIVC_OK;
 }
 
 AIVC_EXPORT int aivc_range_decode_windows(const uint8_t *bytes, const uint16_t *win, const float *sigma_pos,
                                           const aivc_rc_batch *batch, uint16_t *sym, uint32_t *consumed_bits,
                                           aivc_stream_t stream) {
-  if (!bytes || !win || !sigma_pos || !sym) return AIVC_ERR_ARG;
-  if (int rc = check_batch(batch)) return rc;
-  if (batch->n_streams == 0) return AIVC_OK;
+  int rc;
+  if (!sigma_pos) return AIVC_ERR_ARG;
+  if (!decode_batch(bytes, win, sym, batch, &rc)) return rc;
   for (int i = 0; i < batch->n_streams; ++i) {
-    if (batch->s[i].in_off % 4 || batch->s[i].plane != 0) return AIVC_ERR_ARG;
+    if (batch->s[i].plane != 0) return AIVC_ERR_ARG;
     if (((uint64_t)batch->s[i].n_sym + 1) * (uint64_t)(CDF_WIN * 2) >= 0x100000000ull) return AIVC_ERR_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(range_decode_windows_kernel, dim3(batch->n_streams), dim3(128), 0, to_stream(stream), bytes, win,
+  hipLaunchKernelGGL((range_decode_kernel<true, const float *__restrict__>), dim3(batch->n_streams), dim3(128), 0, to_stream(stream), bytes, win,
                      sigma_pos, *batch, sym, consumed_bits);
   return check_launch("range_decode_windows");
 }
 
 AIVC_EXPORT int aivc_range_decode(const uint8_t *bytes, const uint16_t *rows, const aivc_rc_batch *batch,
                                   uint16_t *sym, uint32_t *consumed_bits, aivc_stream_t stream) {
-  if (!bytes || !rows || !sym) return AIVC_ERR_ARG;
-  if (int rc = check_batch(batch)) return rc;
-  if (batch->n_streams == 0) return AIVC_OK;
+  int rc;
+  if (!decode_batch(bytes, rows, sym, batch, &rc)) return rc;
   for (int i = 0; i < batch->n_streams; ++i) {
-    if (batch->s[i].in_off % 4) return AIVC_ERR_ARG;
     // the window prefetcher addresses a stream's rows with 32-bit byte offsets
     const uint64_t n_rows = batch->s[i].plane ? (batch->s[i].n_sym + batch->s[i].plane - 1) / batch->s[i].plane : batch->s[i].n_sym;
     if ((n_rows + 1) * (uint64_t)(AIVC_CDF_ROW * 2) >= 0x100000000ull) return AIVC_ERR_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(range_decode_kernel, dim3(batch->n_streams), dim3(128), 0, to_stream(stream), bytes, rows,
+  hipLaunchKernelGGL(range_decode_kernel<false>, dim3(batch->n_streams), dim3(128), 0, to_stream(stream), bytes, rows,
                      *batch, sym, consumed_bits);
   return check_launch("range_decode");
 }
+

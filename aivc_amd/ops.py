@@ -1044,7 +1044,7 @@ def _rc_batches(n, fill):
 
 def range_encode(bounds_list, streams=None):
     """bounds_list: int32 CUDA tensors, one independent stream each (any number; launched 64 at a
-    time, one wavefront per stream).  Returns (out uint8 tensor, lens int32 tensor [n], [(offset,
+    time: one workgroup per launch, one stream per lane).  Returns (out uint8 tensor, lens int32 tensor [n], [(offset,
     capacity)]) -- all on device, no sync.
     streams: optional HIP streams; the launches (a kernel lasts as long as its longest stream) then
     run concurrently on them, forked from / joined back into the current stream with events."""

@@ -84,23 +84,52 @@ def _rows_workspace(n_rows, device):
     return ws[0][:n_rows], ws[1][:n_rows]
 
 
-_PIN_POOL = {}
+class Readback:
+    """Device tensors on their way to the host: pinned buffers from a small free-list (hipHostMalloc per level is slow),
+    asynchronous copies on the current stream and ONE event behind them.  The tensors are held until release(), so
+    they outlive their copies.  The rule of this direction (ops._stage states the opposite one): a pinned buffer goes
+    back to the pool only once the event behind its copy has completed -- until then the copy may still write into
+    it, under the next taker's data.  `floor`: smallest buffer handed out (entries), one value or one per tensor: the
+    big default keeps the byte / flag buffers of a level in ONE size class, per-stream counts ask for 64."""
+    _pool = {}  # (dtype, capacity) -> free buffers
+    allocated = allocated_bytes = lent = 0  # buffers (bytes) ever taken from hipHostMalloc; buffers now out of the pool
 
+    def __init__(self, *tensors, floor=1 << 16):
+        cls = Readback
+        floors = floor if isinstance(floor, (tuple, list)) else [floor] * len(tensors)
+        self._tensors, self._bufs = tensors, []
+        for t, fl in zip(tensors, floors):
+            key = (t.dtype, max(int(fl), 1 << (max(t.numel(), 1) - 1).bit_length()))
+            free = cls._pool.setdefault(key, [])
+            if not free:
+                free.append(torch.empty(key[1], dtype=t.dtype, pin_memory=True))
+                cls.allocated += 1
+                cls.allocated_bytes += key[1] * t.element_size()
+            self._bufs.append(free.pop())
+            cls.lent += 1
+            self._bufs[-1][:t.numel()].copy_(t.reshape(-1), non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
 
-def _pinned(n, dtype, floor=1 << 16):
-    """pinned host staging buffer from a small free-list (hipHostMalloc per level is slow); the
-    buffer goes back to the pool when its EntropyJob has been collected.  `floor`: smallest buffer handed out
-    (entries): the big default keeps the byte / flag buffers of a level in ONE size class, the 4-byte-per-stream
-    counts of the length check ask for 64"""
-    key = (dtype, max(int(floor), 1 << (max(int(n), 1) - 1).bit_length()))
-    lst = _PIN_POOL.setdefault(key, [])
-    t = lst.pop() if lst else torch.empty(key[1], dtype=dtype, pin_memory=True)
-    return t[:n]
+    def ready(self):
+        return self.event.query()
 
+    def arrays(self, wait=True):
+        """-> numpy views of the buffers, shaped like the tensors (valid until release()); with wait=False None while
+        the copies are still running"""
+        if wait:
+            self.event.synchronize()
+        elif not self.ready():
+            return None
+        return [b[:t.numel()].numpy().reshape(tuple(t.shape)) for t, b in zip(self._tensors, self._bufs)]
 
-def _unpin(t):
-    base = t._base if t._base is not None else t
-    _PIN_POOL.setdefault((base.dtype, base.numel()), []).append(base)
+    def release(self):
+        if not self.ready():
+            raise RuntimeError('Readback.release() before the event behind its copies has completed')
+        for b in self._bufs:
+            Readback._pool[(b.dtype, b.numel())].append(b)
+        Readback.lent -= len(self._bufs)
+        self._tensors, self._bufs = (), []
 
 
 # In-band rate check of the reference (src/real_life/bitstream.py:307-329, RESULT lines of src/real_life/encode.py:
@@ -124,26 +153,26 @@ def estimating_rate(on=True):
 class EntropyJob:
     """Range-encode launches of a set of frames, possibly still running on a side stream."""
 
-    def __init__(self, n_frames, present, heads, jobs, out_h, lens_h, offs, event, keep, est_h=None):
-        self.n_frames, self.present, self.heads, self.jobs = n_frames, present, heads, jobs
-        self.out_h, self.lens_h, self.offs, self.event, self.keep = out_h, lens_h, offs, event, keep
-        self.est_h, self.est_bits, self.real_bytes = est_h, 0.0, 0
+    def __init__(self, present, heads, jobs, offs, readback, keep):
+        """readback: the encoder's bytes, lengths and (under ESTIMATE_RATE) rate estimates; None without jobs"""
+        self.n_frames, self.present, self.heads, self.jobs = len(present), present, heads, jobs
+        self.offs, self.readback, self.keep = offs, readback, keep
+        self.est_bits, self.real_bytes = 0.0, 0
 
     def collect(self):
         """-> list of frame byte strings (waits for the side stream)."""
         payload = [[b''] * 4 for _ in range(self.n_frames)]
         if self.jobs:
-            self.event.synchronize()
-            out_h, lens_h = self.out_h.numpy(), self.lens_h.numpy()
+            out_h, lens_h, *est_h = self.readback.arrays()
             for (fi, si), (off, _cap), ln in zip(self.jobs, self.offs, lens_h):
                 if int(ln) < 0:
                     raise RuntimeError('range encoder output buffer overflow')
                 payload[fi][si] = out_h[off:off + int(ln)].tobytes()
-            if self.est_h is not None:
-                self.est_bits = float(self.est_h.numpy().sum())
+            if est_h:
+                self.est_bits = float(est_h[0].sum())
                 self.real_bytes = int(lens_h.sum())
-                _unpin(self.est_h)
-                self.est_h = None
+            self.readback.release()
+            self.readback = None
         frames = []
         for fi in range(self.n_frames):
             blob = b''
@@ -155,19 +184,15 @@ class EntropyJob:
                     blob += len(body).to_bytes(4, 'big') + body
             frames.append(blob)
         self.keep = None
-        if self.jobs:
-            _unpin(self.out_h)
-            _unpin(self.lens_h)
-            self.out_h = self.lens_h = None
         return frames
 
 
 class PreparedFlags:
-    """Non-zero-map flags of a set of frames on their way to the host (async D2H + event on the stream that
-    produced the latents)."""
+    """Non-zero-map flags of a set of frames on their way to the host: a Readback on the stream that produced the
+    latents (of no tensor when no frame has a Laplace section: its event still marks the latents)."""
 
-    def __init__(self, lap, flags_h, event):
-        self.lap, self.flags_h, self.event = lap, flags_h, event
+    def __init__(self, lap, flags):
+        self.lap, self.flags = lap, flags
 
 
 def prepare_finalize(frames_sections):
@@ -177,15 +202,7 @@ def prepare_finalize(frames_sections):
     phase 2 overlaps with it instead of draining the main stream."""
     lap = [(fi, si, s) for fi, secs in enumerate(frames_sections) for si, s in enumerate(secs)
            if s is not None and s.mode == 'laplace']
-    flags_h = None
-    if lap:
-        flags_d = torch.stack([s.flags for _, _, s in lap])
-        flags_h = _pinned(flags_d.numel(), torch.uint8)
-        flags_h.copy_(flags_d.reshape(-1), non_blocking=True)
-        flags_h = (flags_h, tuple(flags_d.shape), flags_d)
-    event = torch.cuda.Event()
-    event.record()
-    return PreparedFlags(lap, flags_h, event)
+    return PreparedFlags(lap, Readback(*([torch.stack([s.flags for _, _, s in lap])] if lap else [])))
 
 
 def _by_batch(sections):
@@ -200,25 +217,20 @@ def _by_batch(sections):
 def launch_finalize(frames_sections, side_stream=None, prepared=None, fork_streams=None):
     """frames_sections: list (one entry per frame) of 4-lists of PendingSection / None.
     One host wait for all non-zero-map flags (C bytes per latent), then the CDF-bound kernels and ONE
-    batched range-encode launch per 64 streams (a wavefront per stream, all concurrent) and an async
+    batched range-encode launch per 64 streams (a stream per lane) and an async
     D2H -- on `side_stream` when given, so the transforms of the next frames overlap with it; with
     `fork_streams` the 64-stream launches of a big set run side by side instead of back to back."""
     if prepared is None:
         prepared = prepare_finalize(frames_sections)
     lap = prepared.lap
-    prepared.event.synchronize()  # the one host wait
-    flags_h = None
-    if lap:
-        buf, shape, _ = prepared.flags_h
-        flags_h = buf.numpy().reshape(shape).copy()
-        _unpin(buf)
+    flags_h = prepared.flags.arrays()  # the one host wait
+    flags_h = flags_h[0].copy() if lap else None
+    prepared.flags.release()
     present = [[s is not None for s in secs] for secs in frames_sections]
     heads = [[b''] * 4 for _ in frames_sections]
-    ctx = torch.cuda.stream(side_stream) if side_stream is not None else None
-    if ctx is not None:
-        side_stream.wait_event(prepared.event)  # the latents of THESE frames, not whatever was issued since
-        ctx.__enter__()
-    try:
+    if side_stream is not None:
+        side_stream.wait_event(prepared.flags.event)  # the latents of THESE frames, not whatever was issued since
+    with torch.cuda.stream(side_stream) if side_stream is not None else contextlib.nullcontext():
         # jobs / bounds in ops.range_encode's stream order, the byte layout collect() reads back: the y batches, then the z
         # batches.  y sections: one bounds launch per frame batch; a frame with no coded map has a head but no stream
         jobs, bounds, y = [], [], []
@@ -244,28 +256,17 @@ def launch_finalize(frames_sections, side_stream=None, prepared=None, fork_strea
                 heads[fi][si] = s.md5
                 jobs.append((fi, si))
                 bounds.append(zb[s.batch[2]])
-        out_h = lens_h = offs = event = est_h = None
+        offs = readback = None
         keep = [frames_sections, bounds]
         if jobs:
+            est = []
             if ESTIMATE_RATE:
-                est = torch.empty(len(bounds), dtype=torch.float64, device=bounds[0].device)
+                est = [torch.empty(len(bounds), dtype=torch.float64, device=bounds[0].device)]
                 for j, b in enumerate(bounds):
-                    ops.bounds_rate(b, out=est[j:j + 1])
-                est_h = _pinned(est.numel(), torch.float64, floor=64)
-                est_h.copy_(est, non_blocking=True)
-                keep.append(est)
+                    ops.bounds_rate(b, out=est[0][j:j + 1])
             out, lens, offs = ops.range_encode(bounds, streams=fork_streams)
-            out_h = _pinned(out.numel(), torch.uint8)
-            lens_h = _pinned(lens.numel(), torch.int32)
-            out_h.copy_(out, non_blocking=True)
-            lens_h.copy_(lens, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-            keep += [out, lens]
-    finally:
-        if ctx is not None:
-            ctx.__exit__(None, None, None)
-    return EntropyJob(len(frames_sections), present, heads, jobs, out_h, lens_h, offs, event, keep, est_h)
+            readback = Readback(out, lens, *est, floor=(1 << 16, 1 << 16, 64))
+    return EntropyJob(present, heads, jobs, offs, readback, keep)
 
 
 def finalize_frames(frames_sections):
@@ -283,8 +284,8 @@ class ArithmeticCoder():
         # debug: prepend / verify the reference's feature-wise md5 on every section (bitstream.py:26-49)
         self.flag_md5sum = get_value('flag_md5sum', param, default)
         self.md5_errors = []
-        # desynchronisation detector: (what, bits consumed per stream on their way to the host, event, payload lengths)
-        # of every range-decode launch since the last stream_errors() call
+        # desynchronisation detector: (what, Readback of the bits consumed per stream, payload lengths) of every
+        # range-decode launch since the last stream_errors() call
         self.flag_check_lengths = True
         self._length_checks = []
         self._length_errors = []  # mismatches found while draining completed checks (see _watch)
@@ -347,16 +348,15 @@ class ArithmeticCoder():
     def _judge(self, entry, wait):
         """one queued check -> its mismatches (None if its decode has not finished and wait is False); the pinned
         counts go back to the pool"""
-        what, host, ev, lens, _ = entry
-        if wait:
-            ev.synchronize()
-        elif not ev.query():
+        what, counts, lens = entry
+        host = counts.arrays(wait)
+        if host is None:
             return None
         bad = []
-        for i, (b, ln) in enumerate(zip(host.numpy().tolist(), lens)):
+        for i, (b, ln) in enumerate(zip(host[0].tolist(), lens)):
             if (int(b) + 2 + 7) // 8 != ln:
                 bad.append((what, i, ln, (int(b) + 2 + 7) // 8))
-        _unpin(host)
+        counts.release()
         return bad
 
     def _drain(self, wait=False):
@@ -378,7 +378,7 @@ class ArithmeticCoder():
     def _watch(self, what, bits, lens):
         """queue the check `len(payload) == (bits + 2 + 7) // 8` of a decode launch (include/aivc_hip.h,
         aivc_range_decode): an async copy of 4 bytes per stream + an event on the decoding stream, no host wait.
-        Completed checks are judged on the way (ev.query()), so the queue stays as short as the decodes in flight."""
+        Completed checks are judged on the way (Readback.ready()), so the queue stays as short as the decodes in flight."""
         if not self.flag_check_lengths or bits is None:
             return
         self._drain()
@@ -386,11 +386,7 @@ class ArithmeticCoder():
             for e in self._length_checks[:self.MAX_PENDING_CHECKS // 2]:
                 self._length_errors += self._judge(e, True)
             del self._length_checks[:self.MAX_PENDING_CHECKS // 2]
-        host = _pinned(bits.numel(), torch.int32, floor=64)
-        host.copy_(bits, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._length_checks.append((what, host, ev, list(lens), bits))
+        self._length_checks.append((what, Readback(bits, floor=64), list(lens)))
 
     def stream_errors(self):
         """-> [(what, index of the stream in its launch, payload bytes, bytes its decode accounts for)] of every range

@@ -175,11 +175,58 @@ def test_length_checks_stay_bounded_and_models_stay_picklable(cuda):
             torch.cuda.synchronize()
     acs = [net.ac for net in (fc.mof, fc.cod)]
     assert all(len(ac._length_checks) <= 8 for ac in acs), [len(ac._length_checks) for ac in acs]
-    small = [k for k in bitstream._PIN_POOL if k[0] == torch.int32 and k[1] <= 64]
-    assert small and sum(len(bitstream._PIN_POOL[k]) for k in small) <= 64
+    pool = bitstream.Readback._pool
+    small = [k for k in pool if k[0] == torch.int32 and k[1] <= 64]
+    assert small and sum(len(pool[k]) for k in small) <= 64
     buf = io.BytesIO()
     torch.save(model, buf)  # pending checks (events, pinned buffers) are not part of the model
     assert fc.stream_errors() == []
+
+
+def test_readback_buffers_return_to_the_pool_only_behind_their_event(cuda):
+    """bitstream.Readback: the pinned buffers of the encoder's flags / bytes / lengths are reused from round to round
+    (nothing new is allocated after the first round, none is missing after the last collect()), and a buffer cannot go
+    back to the pool while the event behind its copy is pending -- made pending here by a stream that waits for a
+    word of memory the test writes only afterwards (no race against a kernel)."""
+    import ctypes as C
+    from aivc_amd import _lib, synth
+    from aivc_amd.codec import FrameCodec
+    from aivc_amd.models import arch
+    from aivc_amd.real_life.bitstream import Readback
+    model = synth.make_model(arch.TINY_WIDTHS, seed=11, device=cuda)
+    frames = synth.to_device_frames(synth.synthetic_video(64, 48, 5, noise=2.0), cuda)
+    fc = FrameCodec(model)
+    lent = Readback.lent
+    with torch.no_grad():
+        first = fc.assemble_video(fc.encode_video(frames, '1_GOP_4'))
+        allocated = (Readback.allocated, Readback.allocated_bytes)
+        for _ in range(19):
+            assert fc.assemble_video(fc.encode_video(frames, '1_GOP_4')) == first
+    assert (Readback.allocated, Readback.allocated_bytes) == allocated and allocated[0] > 0
+    assert Readback.lent == lent
+    # A stream that stands still until the host says so.  (Not a wait for an event recorded later: HIP treats a wait
+    # for an event that has not been recorded as already satisfied, and torch does not even issue it.)  The stream
+    # waits for a word of pinned memory to become 1, which the host writes: hipStreamWaitValue32 of the HIP runtime
+    # the library is linked to.
+    hip = C.CDLL(_lib.LIB_PATH)
+    hip.hipStreamWaitValue32.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint, C.c_uint32]
+    gate = torch.zeros(1, dtype=torch.int32).pin_memory()
+    side = torch.cuda.Stream()
+    src = torch.arange(7, dtype=torch.int32, device=cuda)
+    torch.cuda.synchronize()
+    try:
+        assert hip.hipStreamWaitValue32(side.cuda_stream, gate.data_ptr(), 1, 1, 0xFFFFFFFF) == 0  # 1: wait until equal
+        with torch.cuda.stream(side):
+            rb = Readback(src, floor=64)
+        assert not rb.ready() and rb.arrays(wait=False) is None
+        with pytest.raises(RuntimeError):
+            rb.release()
+        assert Readback.lent == lent + 1
+    finally:
+        gate[0] = 1
+    assert rb.arrays()[0].tolist() == list(range(7))
+    rb.release()
+    assert Readback.lent == lent
 
 
 def test_decode_cli_status_is_returned_by_main(cuda, tmp_path, monkeypatch):

@@ -385,12 +385,10 @@ def test_frames_that_code_nothing(oracle, cuda):
     both_fills(run)
 
 
-@pytest.mark.parametrize('kernel', ['lanes', 'wave'])
-def test_range_encode(kernel, oracle, cuda, monkeypatch):
+def test_range_encode(oracle, cuda):
     """plain inputs (the product's back-to-back detection runs on _base / storage_offset as ever), guarded outputs: separate
     tensors (concatenated), slices of one tensor (taken as they sit), more than 64 streams (two launches), ragged lengths"""
     from aivc_amd import ops
-    monkeypatch.setenv('AIVC_RC_ENCODE', kernel)
     case = range_encode_case(oracle, 77, [1, 7, 8, 9, 63, 64, 65, 500], 62, 400, straddle=False)
     separate = case.place(on(cuda))['streams']
     one = T(np.concatenate(case.inputs['streams']), cuda)

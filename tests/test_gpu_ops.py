@@ -109,27 +109,23 @@ def test_range_coder_bit_exact(n_sym, scale, oracle, cuda):
     c.check(c.run(ops, on(cuda)))
 
 
-@pytest.mark.parametrize('kernel', ['lanes', 'wave'])
-def test_range_encoder_batches_ragged_streams_and_long_straddle_runs(kernel, oracle, cuda, monkeypatch):
-    """A batch of streams in ONE launch (the stream-per-lane encoder codes them side by side in one wavefront, the
-    wave-per-stream encoder one wavefront each): ragged lengths incl. empty, 1, 7, 8, 9 symbols (chunk edges), more than
-    64 streams (two launches), ordinary Laplace symbols and adversarial straddle runs (pending count up to hundreds: the
-    output of one symbol is longer than a word) -- every stream's bytes == the oracle's."""
+def test_range_encoder_batches_ragged_streams_and_long_straddle_runs(oracle, cuda):
+    """A batch of streams in ONE launch (the stream-per-lane encoder codes them side by side in one wavefront): ragged
+    lengths incl. empty, 1, 7, 8, 9 symbols (chunk edges), more than 64 streams (two launches), ordinary Laplace symbols
+    and adversarial straddle runs (pending count up to hundreds: the output of one symbol is longer than a word) -- every
+    stream's bytes == the oracle's."""
     from aivc_amd import ops
-    monkeypatch.setenv('AIVC_RC_ENCODE', kernel)
     c = range_encode_case(oracle, 77, [0, 1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 500, 2049], 60, 3000, straddle=True)
     c.check(c.run(ops, on(cuda)))
 
 
-@pytest.mark.parametrize('kernel', ['lanes', 'wave'])
-def test_range_encoder_output_capacity_contract(kernel, oracle, cuda, monkeypatch):
+def test_range_encoder_output_capacity_contract(oracle, cuda):
     """include/aivc_hip.h aivc_rc_stream.out_cap: whole 32-bit words, at least one -- anything else is AIVC_ERR_ARG at the
     entry point (the stream-per-lane packer clamps its stores to word out_cap / 4 - 1); a capacity the stream does not
     fit reports out_len 0xFFFFFFFF and writes nothing beyond it"""
     import ctypes as C
     from aivc_amd import abi, ops
     from aivc_amd._lib import AivcNativeError, call
-    monkeypatch.setenv('AIVC_RC_ENCODE', kernel)
     rng = np.random.default_rng(5)
     bounds = straddle_stream(rng, 400, burst=3)
     want = oracle.range_encode(bounds)

@@ -1,6 +1,6 @@
 """ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h,
-include/aivc_hip_rates.h, include/aivc_hip_digest.h, include/aivc_hip_scene.h and include/aivc_hip_resize.h (struct layouts,
-constants, prototypes).
+include/aivc_hip_rates.h, include/aivc_hip_digest.h, include/aivc_hip_scene.h, include/aivc_hip_resize.h and
+include/aivc_hip_rawvideo.h (struct layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -8,7 +8,7 @@ oracle/oracle.py (tests only).
 """
 import ctypes as C
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 PREC_FP32, PREC_BF16X3, PREC_FP32_WINO = 0, 1, 2  # aivc_conv_params.precision
 
 AIVC_OK = 0
@@ -213,6 +213,22 @@ RESIZE_PROTOTYPES = {
     'aivc_resize_u8': [_f, _i32, _i32, _i32, _i32, _i32, _f, _f, _i32, _i32, _f, _f, _f, _f],
 }
 
+# include/aivc_hip_rawvideo.h: aivc_rawvideo_chroma
+CHROMA_NONE, CHROMA_PLANAR, CHROMA_UV, CHROMA_VU = 0, 1, 2, 3
+
+
+class RawVideoFmt(C.Structure):
+    _fields_ = [('w', C.c_int32), ('h', C.c_int32), ('bytes_per_sample', C.c_int32), ('depth', C.c_int32),
+                ('msb_aligned', C.c_int32), ('shift_x', C.c_int32), ('shift_y', C.c_int32), ('chroma', C.c_int32),
+                ('offset', C.c_int64 * 3), ('pitch', C.c_int64 * 3)]
+
+
+# include/aivc_hip_rawvideo.h: device only (their statement is numpy: tests/rawvideo_cases.py, tests/test_gpu_rawvideo.py)
+RAWVIDEO_PROTOTYPES = {
+    'aivc_rawvideo_to_yuv420u8': [_f, _i32, _P(RawVideoFmt), _f, _f, _f],
+    'aivc_yuv420u8_to_rawvideo': [_f, _f, _f, _i32, _P(RawVideoFmt), _f],
+}
+
 
 # Everything declare() binds: (name, argtypes, restype, whether the stream argument is appended, whether the CPU oracle has a
 # `_ref` twin).  The diagnostics, aivc_warp_modes (include/aivc_hip_diag.h, include/aivc_hip_warp.h) and the *_PROTOTYPES of the
@@ -243,6 +259,21 @@ def declare(lib, suffix=''):
             fn.argtypes = list(args) + ([C.c_void_p] if stream else [])
             fn.restype = restype
             fns[name] = fn
+    return fns
+
+
+# RAWVIDEO_PROTOTYPES is bound by declare_rawvideo, not by the loop above: what declare() binds is pinned name by name
+# (tests/test_host_logic.py: test_declare_binds_these_names_and_no_others), and that list stays as it is.  aivc_amd/_lib.py calls
+# both on the device library, and a library that lacks either entry fails to load like one that lacks any other.
+def declare_rawvideo(lib):
+    """Attach argtypes/restype for the entries of include/aivc_hip_rawvideo.h (device library only); raises AttributeError when
+    the library does not export one of them."""
+    fns = {}
+    for name, args in RAWVIDEO_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = list(args) + [C.c_void_p]
+        fn.restype = C.c_int
+        fns[name] = fn
     return fns
 
 

@@ -46,6 +46,8 @@ def parse_args(argv=None):
     add_contract_flag(p, ('fp32', 'fp32w', 'auto'))
     enc_cli.add_rate_flags(p)
     enc_cli.add_scene_flag(p)
+    enc_cli.add_pix_fmt_flag(p)
+    dec_cli.add_out_format_flags(p)
     from aivc_amd.resize import add_resize_flags, check_resize_flags
     add_resize_flags(p, {'--size': enc_cli.SIZE_HELP, '--out_size': dec_cli.OUT_SIZE_HELP})
     a = p.parse_args(argv)
@@ -53,7 +55,19 @@ def parse_args(argv=None):
     enc_cli.check_scene_flag(p, a)
     a.resample = check_resize_flags(p, a, ('--size', '--out_size'))
     dec_cli.check_out_size(p, a, a.o)
+    dec_cli.check_out_format(p, a, a.o)
     return a
+
+
+def input_size(path, pix_fmt=None):
+    """(w, h) of the frames in -i: a .y4m header's, else the name's"""
+    from aivc_amd import rawvideo
+    if not rawvideo.needs_conversion(path, pix_fmt):
+        from aivc_amd.real_life.encode import parse_yuv_name
+        return parse_yuv_name(path)
+    reader = rawvideo.open_raw(path, pix_fmt)
+    reader.close()
+    return reader.w, reader.h
 
 
 def size_text(size):
@@ -75,6 +89,7 @@ def main(argv=None):
                  + (['--target_bpp', str(a.target_bpp)] if a.target_bpp > 0 else [])
                  + (['--digests'] if a.digests else [])
                  + (['--scene_cut', repr(a.scene_cut)] if a.scene_cut is not None else [])
+                 + (['--pix_fmt', a.pix_fmt] if a.pix_fmt is not None else [])
                  + (['--size', size_text(a.size), '--resample', a.resample] if a.size is not None else [])
                  + (['--contract', a.contract] if a.contract not in (None, 'auto') else []))  # (auto is the decoder's choice)
     banner(('*' * 80).center(120))
@@ -83,6 +98,8 @@ def main(argv=None):
     status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common
                           + ([] if not verify else ['--verify'] if verify is True else ['--verify', verify])
                           + (['--out_size', size_text(a.out_size), '--resample', a.resample] if a.out_size is not None else [])
+                          + (['--out_pix_fmt', a.out_pix_fmt] if a.out_pix_fmt != 'yuv420p' else [])
+                          + (['--fps', '%d:%d' % a.fps] if a.fps != (25, 1) else [])
                           + (['--contract', a.contract] if a.contract else []))
     from aivc_amd import parallel
     if parallel.rank_world()[0] != 0:  # multi-rank job: rank 0 evaluates
@@ -90,15 +107,17 @@ def main(argv=None):
     if os.path.isdir(a.i) or dec_cli.is_png_folder(a.o):  # (evaluate.py scores planar files)
         print('[INFO] evaluation skipped: it compares two planar .yuv files, -i / -o name picture folders')
         return status
-    from aivc_amd.real_life.encode import parse_yuv_name
+    source = input_size(a.i, a.pix_fmt)
     written = a.out_size if a.out_size is not None else a.size  # the size of the frames in -o, where it was chosen here
-    if written is not None and written != parse_yuv_name(a.i):
+    if written is not None and written != source:
         print('[INFO] evaluation skipped: -o holds %dx%d frames, -i %dx%d ones (evaluate.py compares frames of one size; '
-              '--out_size with the size of -i brings them back)' % (written + parse_yuv_name(a.i)))
+              '--out_size with the size of -i brings them back)' % (written + source))
         return status
     print(('*' * 80).center(120))
     print('Starting evaluation'.center(120))
-    eval_cli.main(['--raw', a.i, '--compressed', a.o, '--bitstream', a.bitstream_out, '--start_frame', str(a.start_frame)])
+    eval_cli.main(['--raw', a.i, '--compressed', a.o, '--bitstream', a.bitstream_out, '--start_frame', str(a.start_frame)]
+                  + (['--pix_fmt', a.pix_fmt] if a.pix_fmt is not None else [])
+                  + (['--compressed_pix_fmt', a.out_pix_fmt] if a.out_pix_fmt != 'yuv420p' and not a.o.endswith('.y4m') else []))
     return status  # 3: decoded and evaluated, but the stream did not decode cleanly (real_life/decode.py)
 
 

@@ -1,6 +1,6 @@
-// reduce.h -- device helpers of the streaming sums (quality.hip, scene.hip, rate.hip): exact 64-bit integer sums over a wave,
-// a workgroup and a row of per-workgroup partials, the split of a byte range around its 16-byte aligned part, and the fixed
-// fp64 tree of the rate and quality logs.  Integer sums do not depend on their grouping; the fp64 tree's order is part of the
+// reduce.h -- device helpers of the streaming passes (quality.hip, scene.hip, rate.hip, rawvideo.hip): exact 64-bit integer sums
+// over a wave, a workgroup and a row of per-workgroup partials, the split of a byte range around its 16-byte aligned part, the
+// byte funnel that reads 16 bytes at any address out of two aligned chunks, and the fixed fp64 tree of the rate and quality logs.  Integer sums do not depend on their grouping; the fp64 tree's order is part of the
 // result (the CPU oracle walks the same one).
 #pragma once
 #include "common.h"
@@ -55,6 +55,24 @@ struct ByteSplit {
     for (size_t i = t; i < n_scalar; i += T) f(i < head ? i : tail0 + (i - head));
   }
 };
+
+typedef uint32_t chunk16_t __attribute__((ext_vector_type(4)));            // one aligned 16-byte chunk
+typedef const chunk16_t __attribute__((address_space(1))) *chunk16_ptr;    // in global memory: global_load, not flat_load
+
+// bytes s .. s + 15 of the 32 bytes {lo, hi}, 0 <= s < 16 (ws = s / 4, bs = s % 4; scene.hip: uniform over
+// the workgroup, rawvideo.hip: the lane's own).  s = 0 gives lo.
+__device__ __forceinline__ chunk16_t funnel16(const chunk16_t &lo, const chunk16_t &hi, uint32_t ws, uint32_t bs) {
+  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  uint32_t t[7];
+#pragma unroll
+  for (int j = 0; j < 7; ++j) t[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], bs);  // ({hi, lo} >> 8 bs), low word
+  chunk16_t r;
+  r.x = ws == 0 ? t[0] : ws == 1 ? t[1] : ws == 2 ? t[2] : t[3];
+  r.y = ws == 0 ? t[1] : ws == 1 ? t[2] : ws == 2 ? t[3] : t[4];
+  r.z = ws == 0 ? t[2] : ws == 1 ? t[3] : ws == 2 ? t[4] : t[5];
+  r.w = ws == 0 ? t[3] : ws == 1 ? t[4] : ws == 2 ? t[5] : t[6];
+  return r;
+}
 
 // lanes[j] += lanes[j + s] for s = L/2, L/4, ..., 1 over the L = AIVC_RATE_LANES fixed lanes, by a workgroup of 1024: the sum
 // is left in lanes[0] for every thread to read

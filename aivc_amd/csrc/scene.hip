@@ -18,42 +18,25 @@ namespace aivc {
 constexpr int SAD_THREADS = 256;
 constexpr int SAD_UNROLL = 4;  // 16-byte chunks of each plane a thread has in flight: 1080p luma is one such round per thread
 
-typedef uint32_t sad_chunk_t __attribute__((ext_vector_type(4)));                  // one aligned 16-byte chunk
-typedef const sad_chunk_t __attribute__((address_space(1))) *sad_chunk_ptr;        // in global memory: global_load, not flat_load
-
-__device__ __forceinline__ uint32_t sad16(const sad_chunk_t &x, const sad_chunk_t &y, uint32_t acc) {  // adds <= 16 * 255
+__device__ __forceinline__ uint32_t sad16(const chunk16_t &x, const chunk16_t &y, uint32_t acc) {  // adds <= 16 * 255
   acc = __builtin_amdgcn_sad_u8(x.x, y.x, acc);
   acc = __builtin_amdgcn_sad_u8(x.y, y.y, acc);
   acc = __builtin_amdgcn_sad_u8(x.z, y.z, acc);
   return __builtin_amdgcn_sad_u8(x.w, y.w, acc);
 }
 
-// bytes s .. s + 15 of the 32 bytes {lo, hi}, 0 < s < 16 uniform over the workgroup (ws = s / 4, bs = s % 4)
-__device__ __forceinline__ sad_chunk_t funnel16(const sad_chunk_t &lo, const sad_chunk_t &hi, uint32_t ws, uint32_t bs) {
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  uint32_t t[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) t[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], bs);  // ({hi, lo} >> 8 bs), low word
-  sad_chunk_t r;
-  r.x = ws == 0 ? t[0] : ws == 1 ? t[1] : ws == 2 ? t[2] : t[3];
-  r.y = ws == 0 ? t[1] : ws == 1 ? t[2] : ws == 2 ? t[3] : t[4];
-  r.z = ws == 0 ? t[2] : ws == 1 ? t[3] : ws == 2 ? t[4] : t[5];
-  r.w = ws == 0 ? t[3] : ws == 1 ? t[4] : ws == 2 ? t[5] : t[6];
-  return r;
-}
-
 // The 16-byte part of a pair: chunks t, t + T, ... of va against the bytes shift .. of vb's chunks.  FUNNEL: shift != 0.
 template <bool FUNNEL>
-__device__ __forceinline__ uint64_t sad_chunks(sad_chunk_ptr va, sad_chunk_ptr vb, size_t nvec, size_t t, size_t T, uint32_t shift) {
+__device__ __forceinline__ uint64_t sad_chunks(chunk16_ptr va, chunk16_ptr vb, size_t nvec, size_t t, size_t T, uint32_t shift) {
   uint64_t acc = 0;
   const uint32_t ws = shift >> 2, bs = shift & 3u;
   for (size_t i0 = t; i0 < nvec; i0 += (size_t)SAD_UNROLL * T) {
-    sad_chunk_t x[SAD_UNROLL], y[SAD_UNROLL], z[SAD_UNROLL];
+    chunk16_t x[SAD_UNROLL], y[SAD_UNROLL], z[SAD_UNROLL];
 #pragma unroll
     for (int k = 0; k < SAD_UNROLL; ++k) {  // every load of the round is issued before the first sum
       const size_t i = i0 + (size_t)k * T;
       const bool in = i < nvec;
-      x[k] = y[k] = z[k] = sad_chunk_t{0u, 0u, 0u, 0u};
+      x[k] = y[k] = z[k] = chunk16_t{0u, 0u, 0u, 0u};
       if (in) {
         x[k] = va[i];
         y[k] = vb[i];
@@ -75,7 +58,7 @@ __global__ void __launch_bounds__(SAD_THREADS) pair_sad_u8_kernel(const uint8_t 
   const size_t t = (size_t)blockIdx.x * SAD_THREADS + threadIdx.x, T = (size_t)AIVC_SAD_BLOCKS * SAD_THREADS;
   const ByteSplit sp(a, len);
   const uint32_t shift = (uint32_t)((uintptr_t)(b + sp.head) & 15);  // where b's bytes lie in ITS aligned chunks: uniform
-  sad_chunk_ptr va = (sad_chunk_ptr)(a + sp.head), vb = (sad_chunk_ptr)(b + sp.head - shift);
+  chunk16_ptr va = (chunk16_ptr)(a + sp.head), vb = (chunk16_ptr)(b + sp.head - shift);
   uint64_t acc = shift == 0 ? sad_chunks<false>(va, vb, sp.nvec, t, T, 0) : sad_chunks<true>(va, vb, sp.nvec, t, T, shift);
   sp.outside(t, T, [&](size_t j) {
     const int d = (int)a[j] - (int)b[j];

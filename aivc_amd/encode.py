@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """encode.py CLI (flags of src/encode.py:27-66).  python -m aivc_amd.encode -i clip_WxH_fps_420.yuv ...
--i may also name a folder of the reference's pictures: PNG triplets (<idx>_{y,u,v}.png, or the CLIC layout) or <idx>.png RGB."""
+-i may also name a .y4m file, a headerless file in another layout (--pix_fmt, or _422 / _444 / _10b ... tokens in its name), or a folder of the reference's pictures: PNG triplets (<idx>_{y,u,v}.png, or the CLIC layout) or <idx>.png RGB."""
 import argparse
 
 from aivc_amd.cli_common import add_contract_flag, contract_scope, get_model, resolve_device
@@ -58,6 +58,34 @@ def add_size_flag(p):
     add_resize_flags(p, {'--size': SIZE_HELP})
 
 
+def add_pix_fmt_flag(p):
+    """--pix_fmt NAME (shared with aivc.py)"""
+    from aivc_amd.rawvideo import PIX_FMTS
+    p.add_argument('--pix_fmt', default=None, choices=PIX_FMTS, metavar='NAME',
+                   help='layout of a headerless -i file, under ffmpeg\'s names (%s); unset: the _420 / _422 / _444 and _10b / _12b / '
+                        '_16b / _<n>bit tokens of its name, default yuv420p.  A .y4m file says what it holds.  Anything but planar '
+                        '8-bit 4:2:0 is converted to it on the device before everything else (--size included): what is coded, '
+                        'digested and scored by --log_dir are the converted planes' % ', '.join(PIX_FMTS))
+
+
+def check_input_range(a):
+    """a .y4m or converted -i: exit status 2 with the file's range for --start_frame / --end_frame outside it, before a device is
+    looked for (like a partial decode's request outside the stream)"""
+    import os
+    from aivc_amd import rawvideo
+    if os.path.isdir(a.i) or not os.path.exists(a.i) or not rawvideo.needs_conversion(a.i, a.pix_fmt):
+        return
+    try:
+        reader = rawvideo.open_raw(a.i, a.pix_fmt)
+        try:
+            reader.frame_range(a.start_frame, a.end_frame)
+        finally:
+            reader.close()
+    except rawvideo.RawVideoError as e:
+        print('[ERROR] %s: %s' % (a.i, e))
+        raise SystemExit(2)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--gop', default='1_GOP_32', type=str)
@@ -74,6 +102,7 @@ def parse_args(argv=None):
     p.add_argument('--digests', action='store_true',
                    help='write the sidecar manifest <bitstream>.md5: the arithmetic contract and one MD5 per reconstructed plane, '
                         'computed on the device (decode.py --verify checks a decode against it); the bitstream does not change')
+    add_pix_fmt_flag(p)
     add_contract_flag(p, ('fp32', 'fp32w'))
     add_rate_flags(p)
     add_scene_flag(p)
@@ -88,6 +117,7 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
+    check_input_range(a)
     dev = resolve_device(a.cpu)
     model = get_model(a.model, dev)
     nb_rates = len(model.codec_net.codec_net.gain_I.enc_gain_list) if a.idx_rate else 1
@@ -98,7 +128,7 @@ def main(argv=None):
                        'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
                        'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp,
                        'rate_step': a.rate_step, 'digests': a.digests, 'scene_cut': a.scene_cut, 'size': a.size,
-                       'resample': a.resample})
+                       'resample': a.resample, 'pix_fmt': a.pix_fmt})
 
 
 if __name__ == '__main__':

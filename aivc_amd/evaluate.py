@@ -3,9 +3,11 @@
 
     PSNR    [dB]: ...      MS-SSIM     : ...      MS-SSIM [dB]: ...      Size [bytes]: ...
 
-The reference walks two folders of <idx>_{y,u,v}.png planes; here --raw / --compressed are planar 8-bit 4:2:0
-.yuv files (what encode.py reads and decode.py writes -- no PNG round trip) and the three planes of every
-decoded frame are scored on the GPU (aivc_amd/clic21/metrics.py)."""
+The reference walks two folders of <idx>_{y,u,v}.png planes; here --raw / --compressed are raw video files (what encode.py
+reads and decode.py writes -- no PNG round trip): planar 8-bit 4:2:0 .yuv files, or anything aivc_amd.rawvideo.open_raw reads
+(.y4m, other layouts by --pix_fmt / --compressed_pix_fmt or the tokens of the name), which is converted to 8-bit 4:2:0 on the
+device first -- a 10-bit source is scored as the encoder saw it.  The three planes of every decoded frame are scored on the
+GPU (aivc_amd/clic21/metrics.py)."""
 import argparse
 import os
 
@@ -25,11 +27,36 @@ def _planes(path, w, h, first=0, count=None):
              'v': f[h * w + hc * wc:].reshape(hc, wc)} for f in buf]
 
 
-def evaluate_yuv(raw_path, compressed_path, start_frame=0):
-    """frame size from the raw file's name (<Name>_<W>x<H>_..., as encode.py parses it)"""
-    w, h = parse_yuv_name(raw_path)
-    dec = _planes(compressed_path, w, h)
-    raw = _planes(raw_path, w, h, start_frame, len(dec))
+def _converted(path, pix_fmt, size, first=0, count=None):
+    """a file that goes through aivc_amd.rawvideo -> (the same list of host planes as _planes, (w, h))"""
+    from aivc_amd import rawvideo
+    reader = rawvideo.open_raw(path, pix_fmt, size)
+    try:
+        n = reader.n_frames - first if count is None else min(reader.n_frames - first, count)
+        frames = reader.read(first, first + n - 1) if n > 0 else []
+    finally:
+        reader.close()
+    return [{k: fr[k][0].cpu().numpy() for k in 'yuv'} for fr in frames], (reader.w, reader.h)
+
+
+def evaluate_yuv(raw_path, compressed_path, start_frame=0, pix_fmt=None, compressed_pix_fmt=None):
+    """frame size from the raw file: its .y4m header, or its name (<Name>_<W>x<H>_..., as encode.py parses it); a headerless
+    compressed file has the raw file's size.  Plain 8-bit 4:2:0 .yuv files are read on the host as they always were."""
+    from aivc_amd import rawvideo
+    raw_conv = rawvideo.needs_conversion(raw_path, pix_fmt)
+    if raw_conv:
+        reader = rawvideo.open_raw(raw_path, pix_fmt)
+        w, h = reader.w, reader.h
+        reader.close()
+    else:
+        w, h = parse_yuv_name(raw_path)
+    if rawvideo.needs_conversion(compressed_path, compressed_pix_fmt):
+        dec, size = _converted(compressed_path, compressed_pix_fmt, None if compressed_path.endswith('.y4m') else (w, h))
+        if size != (w, h):
+            raise ValueError('%s holds %dx%d frames, %s %dx%d ones' % (compressed_path, size[0], size[1], raw_path, w, h))
+    else:
+        dec = _planes(compressed_path, w, h)
+    raw = _converted(raw_path, pix_fmt, None, start_frame, len(dec))[0] if raw_conv else _planes(raw_path, w, h, start_frame, len(dec))
     target, submit = {}, {}
     for idx, (r, d) in enumerate(zip(raw, dec)):
         for c in 'yuv':
@@ -40,13 +67,17 @@ def evaluate_yuv(raw_path, compressed_path, start_frame=0):
 
 def main(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--raw', default='', type=str, help='planar 4:2:0 .yuv file with the input frames')
-    p.add_argument('--compressed', default='', type=str, help='planar 4:2:0 .yuv file written by decode.py')
+    from aivc_amd.rawvideo import PIX_FMTS
+    p.add_argument('--raw', default='', type=str, help='raw video file with the input frames: planar 4:2:0 .yuv, .y4m, or --pix_fmt')
+    p.add_argument('--compressed', default='', type=str, help='raw video file written by decode.py (.yuv or .y4m)')
+    p.add_argument('--pix_fmt', default=None, choices=PIX_FMTS, metavar='NAME', help='layout of a headerless --raw (encode.py --pix_fmt)')
+    p.add_argument('--compressed_pix_fmt', default=None, choices=PIX_FMTS, metavar='NAME',
+                   help='layout of a headerless --compressed (decode.py --out_pix_fmt)')
     p.add_argument('--bitstream', default='../bitstream.bin', type=str, help='Path of the bitstream')
     p.add_argument('--start_frame', default=0, type=int, help='index of the first coded frame inside --raw')
     a = p.parse_args(argv)
-    comp = a.compressed if a.compressed.endswith('.yuv') else a.compressed + '.yuv'
-    results = evaluate_yuv(a.raw, comp, a.start_frame)
+    comp = a.compressed if a.compressed.endswith(('.yuv', '.y4m')) else a.compressed + '.yuv'
+    results = evaluate_yuv(a.raw, comp, a.start_frame, a.pix_fmt, a.compressed_pix_fmt)
     print('PSNR    [dB]: ' + '%.5f' % (results.get('PSNR')))
     print('MS-SSIM     : ' + '%.5f' % (results.get('MSSSIM')))
     print('MS-SSIM [dB]: ' + '%.5f' % (results.get('MSSSIM_dB')))

@@ -690,6 +690,76 @@ def resize_u8(planes, h_out, w_out, filter='bicubic'):
     return out
 
 
+def _rawvideo_layout(fmt, w, h, layout, op):
+    from . import rawvideo
+    fmt = rawvideo.PixFmt(fmt)
+    w, h = int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError('%s: a frame of %d x %d (w x h): every side must be at least 1' % (op, w, h))
+    offsets, pitches, nbytes = fmt.layout(w, h) if layout is None else layout
+    if nbytes >= 1 << 31:
+        raise ValueError('%s: a %s frame of %d x %d is %d bytes, the kernel takes less than 2^31' % (op, fmt.name, w, h, nbytes))
+    return fmt, fmt.struct(w, h, offsets, pitches), nbytes
+
+
+def raw_to_yuv420u8(blob, offsets, fmt, w, h, layout=None):
+    """Frames of a raw video layout -> the codec's 8-bit 4:2:0 planes (include/aivc_hip_rawvideo.h, where the arithmetic is stated).
+    blob: a uint8 CUDA tensor that holds the frames, e.g. a stretch of a file as it is; offsets: the byte offset of each of the n
+    frames in it -- ANY offsets: the frames of a .y4m lie behind `FRAME` lines; fmt: an aivc_amd.rawvideo.PixFmt or its name;
+    w, h: the luma size; layout: (plane offsets, row pitches, bytes per frame) where the rows are not tight (pitched surfaces), default
+    fmt.layout(w, h).  -> (y [n, h, w], u, v [n, ceil(h/2), ceil(w/2)]) uint8 CUDA tensors.  One launch for all frames and planes on
+    the current stream; the pointer table is one small host-to-device copy; no synchronisation."""
+    blob = _dev(blob, torch.uint8, 'blob').reshape(-1)
+    fmt, st, nbytes = _rawvideo_layout(fmt, w, h, layout, 'raw_to_yuv420u8')
+    offsets = [int(o) for o in offsets]
+    n, hc, wc = len(offsets), (st.h + 1) // 2, (st.w + 1) // 2
+    if offsets and (min(offsets) < 0 or max(offsets) + nbytes > blob.numel()):
+        raise ValueError('raw_to_yuv420u8: %s frames of %d bytes at offsets %d ... %d do not lie inside a blob of %d bytes'
+                         % (fmt.name, nbytes, min(offsets), max(offsets), blob.numel()))
+    y = torch.empty((n, st.h, st.w), dtype=torch.uint8, device=blob.device)
+    u = torch.empty((n, hc, wc), dtype=torch.uint8, device=blob.device)
+    v = torch.empty((n, hc, wc), dtype=torch.uint8, device=blob.device)
+    if n == 0:
+        return y, u, v
+    table, _ = _stage(blob.device, [(np.asarray(offsets, np.uint64) + np.uint64(blob.data_ptr())).view(np.uint8)])
+    _hbm_profiled('raw_to_yuv420u8', n * (nbytes + st.h * st.w + 2 * hc * wc),
+                  lambda: call('aivc_rawvideo_to_yuv420u8', _p(table), n, C.byref(st), _p(y), _p(u), _p(v), _stream()))
+    return y, u, v
+
+
+def yuv420u8_to_raw(y, u, v, fmt, lead=b''):
+    """The codec's 8-bit 4:2:0 planes -> frames of a raw video layout (4:2:0 and grey layouts: include/aivc_hip_rawvideo.h).
+    y: uint8 CUDA tensor [n, h, w]; u, v: [n, ceil(h/2), ceil(w/2)] (ignored by a grey layout); fmt: a PixFmt or its name;
+    lead: bytes to put in front of every frame (a .y4m file's b'FRAME\\n': the frames then lie at any byte).
+    -> uint8 CUDA tensor [n, len(lead) + bytes per frame], the frames tight.  One launch on the current stream, no synchronisation."""
+    y = _dev(y, torch.uint8, 'y')
+    if y.dim() != 3:
+        raise ValueError('yuv420u8_to_raw: expected y [n, h, w], got %s' % (tuple(y.shape),))
+    n, h, w = y.shape
+    fmt, st, nbytes = _rawvideo_layout(fmt, w, h, None, 'yuv420u8_to_raw')
+    if fmt.chroma != abi.CHROMA_NONE and not (fmt.shift_x == 1 and fmt.shift_y == 1):
+        raise ValueError('yuv420u8_to_raw: %s: only 4:2:0 and grey layouts are written (4:2:2 and 4:4:4 need an upsampling filter)'
+                         % fmt.name)
+    if fmt.chroma != abi.CHROMA_NONE:
+        u, v = _dev(u, torch.uint8, 'u'), _dev(v, torch.uint8, 'v')
+        want = (n, (h + 1) // 2, (w + 1) // 2)
+        if tuple(u.shape) != want or tuple(v.shape) != want:
+            raise ValueError('yuv420u8_to_raw: expected u and v %s, got %s and %s' % (want, tuple(u.shape), tuple(v.shape)))
+    else:
+        u = v = None
+    lead = bytes(lead)
+    out = torch.empty((n, len(lead) + nbytes), dtype=torch.uint8, device=y.device)
+    if n == 0:
+        return out
+    ptrs = out.data_ptr() + len(lead) + np.arange(n, dtype=np.uint64) * np.uint64(len(lead) + nbytes)
+    table, offs = _stage(y.device, [ptrs.astype(np.uint64).view(np.uint8), np.frombuffer(lead, np.uint8)])
+    if lead:
+        out[:, :len(lead)] = table[offs[1]:offs[1] + len(lead)]
+    _hbm_profiled('yuv420u8_to_raw', n * (nbytes + h * w + (0 if u is None else 2 * u[0].numel())),
+                  lambda: call('aivc_yuv420u8_to_rawvideo', _p(y), _p(u), _p(v), n, C.byref(st), _p(table), _stream()))
+    return out
+
+
 def downsample2x(x, ch0, nch):
     """NHWC x -> planar [n, nch, h//2, w//2] 2x2 means of channels ch0..ch0+nch-1 (OutputLayer)."""
     x = _dev(x, torch.float32, 'x')

@@ -151,9 +151,14 @@ def decode_one_video(param):
     filter `resample`, default bicubic; each plane on its own, chroma to the ceil half size, chroma siting ignored).  The
     stream has no display-size field, so the size is the caller's to give, and so is a .yuv file name that states it.
     Verification and flag_bitstream_debug look at the planes at CODED size, before the resize; a partial decode resizes only
-    the frames it returns."""
+    the frames it returns.
+    out_pix_fmt: the layout of the file that is written, a 4:2:0 or grey name of aivc_amd.rawvideo.PIX_FMTS (default yuv420p);
+    an out_file that ends in .y4m gets a header and `FRAME` lines, fps: its frame rate (numerator, denominator) -- the stream
+    stores none, default (25, 1).  The export runs on the device after the resize (aivc_amd.rawvideo.write_raw); the frames that
+    are returned, verified and digested stay the 8-bit planes.  yuv420p into a headerless file is written as it always was."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
-               'verify': '', 'contract': '', 'frames': None, 'max_level': None, 'out_size': None, 'resample': 'bicubic'}
+               'verify': '', 'contract': '', 'frames': None, 'max_level': None, 'out_size': None, 'resample': 'bicubic', 'out_pix_fmt': 'yuv420p',
+               'fps': (25, 1)}
     decoder = get_value('decoder', param, default).eval()
     path = get_value('bitstream_path', param, default)
     dev = torch.device(get_value('device', param, default))
@@ -166,6 +171,11 @@ def decode_one_video(param):
     _VERIFY_BAD[0] = 0
     out_size = get_value('out_size', param, default)
     resize = None if out_size is None else (int(out_size[0]), int(out_size[1]), get_value('resample', param, default))
+    from .. import rawvideo
+    out_fmt = rawvideo.check_writable(get_value('out_pix_fmt', param, default), '' if is_png_folder(out_file) else out_file)
+    raw_out = None  # (layout, frame rate) where the file goes through the exporter
+    if out_file and not is_png_folder(out_file) and (out_file.endswith('.y4m') or out_fmt.name != 'yuv420p'):
+        raw_out = (out_fmt, tuple(get_value('fps', param, default)))
     manifest = None
     manifest_file = verify if isinstance(verify, str) and verify else digests.manifest_path(path)
     if verify or (contract == 'auto' and os.path.exists(manifest_file)):
@@ -182,7 +192,7 @@ def decode_one_video(param):
         elif contract:
             ops.set_precision(contract)
         return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default),
-                                 resize)
+                                 resize, raw_out)
     finally:
         ops.set_precision(prev_precision)
 
@@ -201,7 +211,7 @@ def read_plan(path, span, max_level):
     return plan._replace(video=video._replace(gops=gops))
 
 
-def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize=None):
+def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize=None, raw_out=None):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel, partial
@@ -244,6 +254,9 @@ def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstre
         frames = resize_frames(frames, resize[0], resize[1], resize[2], dev)
     if is_png_folder(out_file):
         write_png_folder(frames, out_file, dev, shown)
+    elif out_file and raw_out is not None:  # (after the resize: the export sees the size that is written)
+        from .. import rawvideo
+        rawvideo.write_raw(frames, out_file, raw_out[0], raw_out[1], dev)
     elif out_file:
         write_yuv(frames, out_file)
     dist_barrier_after_write(world)

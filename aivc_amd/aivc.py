@@ -62,12 +62,8 @@ def parse_args(argv=None):
 def input_size(path, pix_fmt=None):
     """(w, h) of the frames in -i: a .y4m header's, else the name's"""
     from aivc_amd import rawvideo
-    if not rawvideo.needs_conversion(path, pix_fmt):
-        from aivc_amd.real_life.encode import parse_yuv_name
-        return parse_yuv_name(path)
-    reader = rawvideo.open_raw(path, pix_fmt)
-    reader.close()
-    return reader.w, reader.h
+    with rawvideo.open_raw(path, pix_fmt) as reader:
+        return reader.w, reader.h
 
 
 def size_text(size):
@@ -107,9 +103,9 @@ def main(argv=None):
     if os.path.isdir(a.i) or dec_cli.is_png_folder(a.o):  # (evaluate.py scores planar files)
         print('[INFO] evaluation skipped: it compares two planar .yuv files, -i / -o name picture folders')
         return status
-    source = input_size(a.i, a.pix_fmt)
     written = a.out_size if a.out_size is not None else a.size  # the size of the frames in -o, where it was chosen here
-    if written is not None and written != source:
+    source = written and input_size(a.i, a.pix_fmt)  # (-i is looked at only where a size was chosen)
+    if written != source:
         print('[INFO] evaluation skipped: -o holds %dx%d frames, -i %dx%d ones (evaluate.py compares frames of one size; '
               '--out_size with the size of -i brings them back)' % (written + source))
         return status

@@ -69,18 +69,15 @@ def add_pix_fmt_flag(p):
 
 
 def check_input_range(a):
-    """a .y4m or converted -i: exit status 2 with the file's range for --start_frame / --end_frame outside it, before a device is
+    """a raw video file as -i: exit status 2 with the file's range for --start_frame / --end_frame outside it, before a device is
     looked for (like a partial decode's request outside the stream)"""
     import os
     from aivc_amd import rawvideo
-    if os.path.isdir(a.i) or not os.path.exists(a.i) or not rawvideo.needs_conversion(a.i, a.pix_fmt):
+    if not os.path.isfile(a.i):
         return
     try:
-        reader = rawvideo.open_raw(a.i, a.pix_fmt)
-        try:
+        with rawvideo.open_raw(a.i, a.pix_fmt) as reader:
             reader.frame_range(a.start_frame, a.end_frame)
-        finally:
-            reader.close()
     except rawvideo.RawVideoError as e:
         print('[ERROR] %s: %s' % (a.i, e))
         raise SystemExit(2)

@@ -4,59 +4,34 @@
     PSNR    [dB]: ...      MS-SSIM     : ...      MS-SSIM [dB]: ...      Size [bytes]: ...
 
 The reference walks two folders of <idx>_{y,u,v}.png planes; here --raw / --compressed are raw video files (what encode.py
-reads and decode.py writes -- no PNG round trip): planar 8-bit 4:2:0 .yuv files, or anything aivc_amd.rawvideo.open_raw reads
-(.y4m, other layouts by --pix_fmt / --compressed_pix_fmt or the tokens of the name), which is converted to 8-bit 4:2:0 on the
-device first -- a 10-bit source is scored as the encoder saw it.  The three planes of every decoded frame are scored on the
+reads and decode.py writes -- no PNG round trip), read by the one reader, aivc_amd.rawvideo.open_raw: planar 8-bit 4:2:0 .yuv
+files, .y4m, other layouts by --pix_fmt / --compressed_pix_fmt or the tokens of the name, which are converted to 8-bit 4:2:0 on
+the device first -- a 10-bit source is scored as the encoder saw it.  The three planes of every decoded frame are scored on the
 GPU (aivc_amd/clic21/metrics.py)."""
 import argparse
 import os
 
-import numpy as np
-
 from aivc_amd.clic21.metrics import evaluate
-from aivc_amd.real_life.encode import parse_yuv_name
 
 
-def _planes(path, w, h, first=0, count=None):
-    hc, wc = (h + 1) // 2, (w + 1) // 2
-    fsize = h * w + 2 * hc * wc
-    n = os.path.getsize(path) // fsize - first
-    n = n if count is None else min(n, count)
-    buf = np.fromfile(path, np.uint8, count=n * fsize, offset=first * fsize).reshape(n, fsize)
-    return [{'y': f[:h * w].reshape(h, w), 'u': f[h * w:h * w + hc * wc].reshape(hc, wc),
-             'v': f[h * w + hc * wc:].reshape(hc, wc)} for f in buf]
-
-
-def _converted(path, pix_fmt, size, first=0, count=None):
-    """a file that goes through aivc_amd.rawvideo -> (the same list of host planes as _planes, (w, h))"""
-    from aivc_amd import rawvideo
-    reader = rawvideo.open_raw(path, pix_fmt, size)
-    try:
-        n = reader.n_frames - first if count is None else min(reader.n_frames - first, count)
-        frames = reader.read(first, first + n - 1) if n > 0 else []
-    finally:
-        reader.close()
-    return [{k: fr[k][0].cpu().numpy() for k in 'yuv'} for fr in frames], (reader.w, reader.h)
+def _host_planes(reader, first=0, count=None):
+    """an opened aivc_amd.rawvideo reader -> the host planes [{'y', 'u', 'v'}] of its frames from `first` on, at most `count`"""
+    n = reader.n_frames - first if count is None else min(reader.n_frames - first, count)
+    frames = reader.read(first, first + n - 1) if n > 0 else []
+    return [{k: fr[k][0].cpu().numpy() for k in 'yuv'} for fr in frames]
 
 
 def evaluate_yuv(raw_path, compressed_path, start_frame=0, pix_fmt=None, compressed_pix_fmt=None):
     """frame size from the raw file: its .y4m header, or its name (<Name>_<W>x<H>_..., as encode.py parses it); a headerless
-    compressed file has the raw file's size.  Plain 8-bit 4:2:0 .yuv files are read on the host as they always were."""
+    compressed file has the raw file's size"""
     from aivc_amd import rawvideo
-    raw_conv = rawvideo.needs_conversion(raw_path, pix_fmt)
-    if raw_conv:
-        reader = rawvideo.open_raw(raw_path, pix_fmt)
-        w, h = reader.w, reader.h
-        reader.close()
-    else:
-        w, h = parse_yuv_name(raw_path)
-    if rawvideo.needs_conversion(compressed_path, compressed_pix_fmt):
-        dec, size = _converted(compressed_path, compressed_pix_fmt, None if compressed_path.endswith('.y4m') else (w, h))
-        if size != (w, h):
-            raise ValueError('%s holds %dx%d frames, %s %dx%d ones' % (compressed_path, size[0], size[1], raw_path, w, h))
-    else:
-        dec = _planes(compressed_path, w, h)
-    raw = _converted(raw_path, pix_fmt, None, start_frame, len(dec))[0] if raw_conv else _planes(raw_path, w, h, start_frame, len(dec))
+    with rawvideo.open_raw(raw_path, pix_fmt) as src:
+        w, h = src.w, src.h
+        with rawvideo.open_raw(compressed_path, compressed_pix_fmt, None if compressed_path.endswith('.y4m') else (w, h)) as out:
+            if (out.w, out.h) != (w, h):
+                raise ValueError('%s holds %dx%d frames, %s %dx%d ones' % (compressed_path, out.w, out.h, raw_path, w, h))
+            dec = _host_planes(out)
+        raw = _host_planes(src, start_frame, len(dec))
     target, submit = {}, {}
     for idx, (r, d) in enumerate(zip(raw, dec)):
         for c in 'yuv':

@@ -1,5 +1,5 @@
-"""Raw video files in other layouts than headerless planar 8-bit 4:2:0: what a layout is (PixFmt, under ffmpeg's names), .y4m
-and headerless files as readers of the codec's planes (open_raw), and the writer (write_raw).
+"""Raw video files: what a layout is (PixFmt, under ffmpeg's names), the one reader of the codec's planes (open_raw: .y4m and
+headerless files, planar 8-bit 4:2:0 as every other layout) and the one writer (write_raw).
 
 The host does no sample arithmetic.  A file's bytes travel to the device as they are -- a stretch of the file per batch, `FRAME`
 lines and all, through the pinned pool of aivc_amd.ops._stage -- and one launch per batch converts them to 8-bit 4:2:0 planes
@@ -105,7 +105,7 @@ class PixFmt:
 
 # ---- names and headers ---------------------------------------------------------------------------------------------------------
 def parse_size_name(path):
-    """'<Name>_<W>x<H>_...' -> (w, h), as real_life.encode.parse_yuv_name"""
+    """'<Name>_<W>x<H>_<fps>_420.yuv' -> (w, h)  (src/format_conversion/utils.py:45-72)"""
     for tok in os.path.basename(path).split('_'):
         m = re.fullmatch(r'(\d+)x(\d+)', tok)
         if m:
@@ -211,6 +211,18 @@ class RawReader:
             self._map.close()
         self._file.close()
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def is_plain(self):
+        """a headerless file of planar 8-bit 4:2:0: the planes are the file's bytes, nothing is converted (and read_yuv prints no
+        `[INFO] input:` line)"""
+        return not self.is_y4m and self.pix_fmt.name == 'yuv420p'
+
     def frame_range(self, first=0, last=-1):
         """(first, last) with last < 0 the file's last frame; a RawVideoError that states the file's range for a request outside"""
         last = self.n_frames - 1 if last < 0 else last
@@ -262,14 +274,6 @@ def open_raw(path, pix_fmt=None, size=None):
     return RawReader(path, pix_fmt, size)
 
 
-def needs_conversion(path, pix_fmt=None):
-    """whether a file is read through open_raw: a .y4m, a named layout, or a name that states another layout than yuv420p.
-    False: the headerless planar 8-bit 4:2:0 file real_life.encode.read_yuv has always read."""
-    if path.endswith('.y4m'):
-        return True
-    return (pix_fmt_from_name(path) if pix_fmt is None else PixFmt(pix_fmt)).name != 'yuv420p'
-
-
 # ---- writing ---------------------------------------------------------------------------------------------------------------------
 def parse_fps(text):
     """'N' or 'N:D' -> (N, D)"""
@@ -301,7 +305,9 @@ def _on(t, device):
 def write_raw(frames, path, pix_fmt='yuv420p', fps=(25, 1), device=None):
     """frames: a list of {'y','u','v'} dicts of uint8 planes [1, h, w] / [1, ceil(h/2), ceil(w/2)] (device tensors, or host ones:
     those are copied over) -> the file `path` in the layout pix_fmt; a .y4m path gets the header (C tag from the layout, F from
-    fps) and a `FRAME` line per frame.  One export launch and one device-to-host copy per batch of at most BATCH_BYTES."""
+    fps) and a `FRAME` line per frame.  One export launch and one device-to-host copy per batch of at most BATCH_BYTES -- but for
+    headerless yuv420p, THE ONE DECISION of the writer: there the file is the planes as they are, and copying them back one by one
+    measured twice as fast as the export's one large copy back (experiments/one_raw_io.md)."""
     import torch
     from . import ops
     fmt = check_writable(pix_fmt, path)
@@ -311,6 +317,11 @@ def write_raw(frames, path, pix_fmt='yuv420p', fps=(25, 1), device=None):
         if not frames:
             if y4m:
                 raise ValueError('write_raw: a .y4m file needs a frame size, and there is no frame')
+            return
+        if not y4m and fmt.name == 'yuv420p':
+            for fr in frames:
+                for k in 'yuv':
+                    f.write(np.ascontiguousarray(torch.as_tensor(fr[k]).cpu().numpy()).tobytes())
             return
         h, w = frames[0]['y'].shape[-2:]
         if y4m:

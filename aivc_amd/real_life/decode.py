@@ -1,7 +1,7 @@
 """Frame / GOP / video decoder with the reference's class and function names
 (src/real_life/decode.py).  Decoder.decode keeps the reference's dictionary contract (float YUV
-dicts, one bitstream file per frame); decode_one_video reads the container and writes planar YUV
-directly, or on request a folder of RGB pictures (the reference's per-frame `dd` forks are out of scope)."""
+dicts, one bitstream file per frame); decode_one_video reads the container and writes a raw video
+file (aivc_amd.rawvideo.write_raw, the one writer), or on request a folder of RGB pictures (the reference's per-frame `dd` forks are out of scope)."""
 import os
 import time
 
@@ -78,16 +78,6 @@ class Decoder(Module):
         return _to_float_dic(rec)
 
 
-def write_yuv(frames, path):
-    """frames: list of dicts of uint8 tensors/arrays [1,h,w] -> planar I420 file."""
-    with open(path, 'wb') as f:
-        for fr in frames:
-            for k in 'yuv':
-                a = fr[k]
-                a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-                f.write(np.ascontiguousarray(a).tobytes())
-
-
 def write_png_folder(frames, directory, device, indices):
     """decoded frames -> <directory>/<idx>.png, RGB pictures (func_util.img_processing.save_tensor_as_img, mode 'yuv420':
     the colour conversion runs on the device, straight from the decoder's 8-bit planes).  indices: the absolute index of
@@ -154,8 +144,9 @@ def decode_one_video(param):
     the frames it returns.
     out_pix_fmt: the layout of the file that is written, a 4:2:0 or grey name of aivc_amd.rawvideo.PIX_FMTS (default yuv420p);
     an out_file that ends in .y4m gets a header and `FRAME` lines, fps: its frame rate (numerator, denominator) -- the stream
-    stores none, default (25, 1).  The export runs on the device after the resize (aivc_amd.rawvideo.write_raw); the frames that
-    are returned, verified and digested stay the 8-bit planes.  yuv420p into a headerless file is written as it always was."""
+    stores none, default (25, 1).  The export runs on the device after the resize (aivc_amd.rawvideo.write_raw, for every file:
+    yuv420p into a headerless file is the planes one after the other); the frames that are returned, verified and digested stay
+    the 8-bit planes."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
                'verify': '', 'contract': '', 'frames': None, 'max_level': None, 'out_size': None, 'resample': 'bicubic', 'out_pix_fmt': 'yuv420p',
                'fps': (25, 1)}
@@ -173,9 +164,7 @@ def decode_one_video(param):
     resize = None if out_size is None else (int(out_size[0]), int(out_size[1]), get_value('resample', param, default))
     from .. import rawvideo
     out_fmt = rawvideo.check_writable(get_value('out_pix_fmt', param, default), '' if is_png_folder(out_file) else out_file)
-    raw_out = None  # (layout, frame rate) where the file goes through the exporter
-    if out_file and not is_png_folder(out_file) and (out_file.endswith('.y4m') or out_fmt.name != 'yuv420p'):
-        raw_out = (out_fmt, tuple(get_value('fps', param, default)))
+    raw_out = (out_fmt, tuple(get_value('fps', param, default)))  # (layout, frame rate) of a file that is written
     manifest = None
     manifest_file = verify if isinstance(verify, str) and verify else digests.manifest_path(path)
     if verify or (contract == 'auto' and os.path.exists(manifest_file)):
@@ -211,7 +200,7 @@ def read_plan(path, span, max_level):
     return plan._replace(video=video._replace(gops=gops))
 
 
-def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize=None, raw_out=None):
+def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize, raw_out):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel, partial
@@ -254,11 +243,9 @@ def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstre
         frames = resize_frames(frames, resize[0], resize[1], resize[2], dev)
     if is_png_folder(out_file):
         write_png_folder(frames, out_file, dev, shown)
-    elif out_file and raw_out is not None:  # (after the resize: the export sees the size that is written)
+    elif out_file:  # (after the resize: the export sees the size that is written)
         from .. import rawvideo
         rawvideo.write_raw(frames, out_file, raw_out[0], raw_out[1], dev)
-    elif out_file:
-        write_yuv(frames, out_file)
     dist_barrier_after_write(world)
     if manifest is not None:  # the frames returned against their rows of the manifest; a whole decode against all of it
         from .. import digests

@@ -1,5 +1,5 @@
-"""encode(param) with the reference's signature and RESULT lines (src/real_life/encode.py), reading a
-planar .yuv file, or -- when sequence_path is a directory -- the reference's folders of PNG pictures."""
+"""encode(param) with the reference's signature and RESULT lines (src/real_life/encode.py), reading a raw video
+file (aivc_amd.rawvideo, the one reader), or -- when sequence_path is a directory -- the reference's folders of PNG pictures."""
 import os
 import time
 
@@ -11,48 +11,19 @@ from ..func_util.console_display import print_log_msg
 from ..func_util.nn_util import get_value
 
 
-def parse_yuv_name(path):
-    """'<Name>_<W>x<H>_<fps>_420.yuv' -> (w, h)  (src/format_conversion/utils.py:45-72)"""
-    for tok in os.path.basename(path).split('_'):
-        if 'x' in tok:
-            a, b = tok.split('x')
-            if a.isdigit() and b.isdigit():
-                return int(a), int(b)
-    raise ValueError('cannot parse WxH from %s' % path)
-
-
 def read_yuv(path, first=0, last=-1, device=None, pix_fmt=None):
     """A raw video file -> (the frames first ... last as dicts of uint8 planes {'y','u','v'} [1, h', w'] on `device`, first, last).
-    THE ONE PLACE that decides how a file is read: a headerless file whose name states no other layout than planar 8-bit 4:2:0,
-    with pix_fmt unset, is read plane by plane as it always was; a .y4m file, a named pix_fmt or a name with a _422 / _444 / _10b
-    ... token goes through aivc_amd.rawvideo (the file's bytes to the device in batches, one conversion launch per batch) and
-    prints one `[INFO] input:` line.  A request outside such a file is an aivc_amd.rawvideo.RawVideoError."""
-    from .. import rawvideo
-    if rawvideo.needs_conversion(path, pix_fmt):
-        reader = rawvideo.open_raw(path, pix_fmt)
-        try:
-            first, last = reader.frame_range(first, last)
-            frames = reader.read(first, last, device)
-        finally:
-            reader.close()
-        from .. import parallel
-        if parallel.rank_world()[0] == 0:
-            print('[INFO] input: %s %dx%d, %d frames (converted to 8-bit 4:2:0 on the device)'
-                  % (reader.pix_fmt.name, reader.w, reader.h, len(frames)))
-        return frames, first, last
-    w, h = parse_yuv_name(path)
-    hc, wc = (h + 1) // 2, (w + 1) // 2
-    fsize = h * w + 2 * hc * wc
-    n_total = os.path.getsize(path) // fsize
-    last = n_total - 1 if last < 0 else last
-    frames = []
-    with open(path, 'rb') as f:
-        f.seek(first * fsize)
-        for _ in range(first, last + 1):
-            buf = np.frombuffer(f.read(fsize), np.uint8)
-            fr = {'y': buf[:h * w].reshape(1, h, w), 'u': buf[h * w:h * w + hc * wc].reshape(1, hc, wc),
-                  'v': buf[h * w + hc * wc:].reshape(1, hc, wc)}
-            frames.append({k: torch.from_numpy(v.copy()).to(device) for k, v in fr.items()})
+    Every file goes through the one reader, aivc_amd.rawvideo.open_raw: the file's bytes to the device in batches, one ingest launch
+    per batch, the frames views into the batches' stacks.  A headerless planar 8-bit 4:2:0 file's planes are its bytes; anything else
+    (a .y4m file, a named pix_fmt, a name with a _422 / _444 / _10b ... token) prints one `[INFO] input:` line.  A request outside
+    the file is an aivc_amd.rawvideo.RawVideoError that names the file's range."""
+    from .. import parallel, rawvideo
+    with rawvideo.open_raw(path, pix_fmt) as reader:
+        first, last = reader.frame_range(first, last)
+        frames = reader.read(first, last, device)
+    if not reader.is_plain and parallel.rank_world()[0] == 0:
+        print('[INFO] input: %s %dx%d, %d frames (converted to 8-bit 4:2:0 on the device)'
+              % (reader.pix_fmt.name, reader.w, reader.h, len(frames)))
     return frames, first, last
 
 
@@ -103,16 +74,17 @@ def encode(param):
     size: the header, the scene cuts, the digests, the w x h of the byte budget, the sharding -- and the quality log, whose
     PSNR and MS-SSIM score the reconstruction against the RESIZED source.  The stream has no display-size field: the decoder
     is told the size to write (decode_one_video: out_size).  Every rank resizes the clip it read.
-    pix_fmt: None (the default) -- a .y4m file says what it holds, a headerless file's name does (read_yuv; a plain *_420.yuv is
-    read as it always was); a name of aivc_amd.rawvideo.PIX_FMTS -- the layout of a headerless file.  The conversion to the
-    8-bit 4:2:0 planes that are coded runs on the device before everything else, the resize included: header, scene cuts,
-    digests, budgets and the quality log see the converted planes, and the log scores against the CONVERTED source."""
+    pix_fmt: None (the default) -- a .y4m file says what it holds, a headerless file's name does (read_yuv); a name of
+    aivc_amd.rawvideo.PIX_FMTS -- the layout of a headerless file.  The conversion to the 8-bit 4:2:0 planes that are coded runs
+    on the device before everything else, the resize included: header, scene cuts, digests, budgets and the quality log see the
+    converted planes, and the log scores against the CONVERTED source.
+    The stages: _source (file or folder -> frames), _code (frames -> bitstream), the gathers of what every rank found,
+    _write_outputs (manifest, debug digests, bitstream), _report (RESULT lines and the returned dictionary)."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
                'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False, 'scene_cut': None,
                'size': None, 'resample': 'bicubic', 'pix_fmt': None}
     model = get_value('model', param, default)
-    want_digests = get_value('digests', param, default)
     seq = get_value('sequence_path', param, default)
     gop_name = get_value('GOP_struct_name', param, default)
     final_file = get_value('final_file', param, default)
@@ -121,20 +93,14 @@ def encode(param):
     working_dir = get_value('working_dir', param, default)
     idx_rate = get_value('idx_rate', param, default)
     target_bpp = get_value('target_bpp', param, default)
-    rate_step = get_value('rate_step', param, default)
     scene_cut = get_value('scene_cut', param, default)
+    want_digests = get_value('digests', param, default)
     dev = next(model.parameters()).device
     if first > last and last != -1:
         print('ERROR: First frame index bigger than last frame index')
         return
-    if os.path.isdir(seq):
-        frames, first, last = read_png_folder(seq, first, last, dev)
-    else:
-        frames, first, last = read_yuv(seq, first, last, dev, get_value('pix_fmt', param, default))
-    size = get_value('size', param, default)
-    if size is not None:
-        from ..func_util.img_processing import resize_frames
-        frames = resize_frames(frames, int(size[0]), int(size[1]), get_value('resample', param, default), dev)
+    frames, first, last = _source(seq, first, last, dev, get_value('pix_fmt', param, default), get_value('size', param, default),
+                                  get_value('resample', param, default))
     print_log_msg('INFO', 'Start encoding', '', '')
     t0 = time.time()
     fc = FrameCodec(model)
@@ -146,41 +112,27 @@ def encode(param):
     if working_dir:
         from ..quality import QualityStats
         stats = QualityStats()
-    budgeted = None
     layout, cuts = None, None
     if scene_cut is not None:
         layout, cuts = _scene_layout(frames, gop_name, float(scene_cut), first, rank)
-    lay = {} if layout is None else {'layout': layout}
+    n = last - first + 1
     with torch.no_grad(), bitstream.estimating_rate():  # the reference's in-band rate check (RESULT lines)
-        if target_bpp and target_bpp > 0:
-            budgeted = _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev, layout)
-            blob, enc, idx_rate = budgeted
-        elif world > 1:  # one process per GPU: intra-period units over the ranks, the container on rank 0
-            blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=idx_rate, return_enc=True, stats=stats,
-                                                      **lay)
-        else:
-            enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last, idx_rate=idx_rate, stats=stats,
-                                  **lay)
-            blob = fc.assemble_video(enc)
-        n = last - first + 1
+        blob, enc, rates = _code(fc, frames, gop_name, first, last, idx_rate, target_bpp, get_value('rate_step', param, default),
+                                 stats, layout, rank, world, dev)
+        # this rank's frames that are not padding (all of the clip's on one GPU): (position in the clip, reconstruction)
+        own = [(idx, r) for idx, r in _own_frames(enc) if idx < n]
         digested = None
         if want_digests:  # (queued behind the encode, before the device is waited for)
             from .. import ops
             from .decode import digest_frames
             contract = ops.precision_name()
-            digested = [(first + idx, r) for idx, r in _own_frames(enc) if idx < n]
-            digested = ([i for i, _ in digested], digest_frames([r for _, r in digested], dev) if digested else None)
+            digested = digest_frames([r for _, r in own], dev) if own else None
         torch.cuda.synchronize()
     dt = time.time() - t0
     est_bits, payload = fc.estimated_bits, float(fc.coded_payload_bytes)
-    # squared error of the frames THIS process reconstructed (all of them on one GPU), summed over the ranks
-    se = cnt = 0.0
-    mine = []  # (absolute frame index, reconstruction)
-    for idx, r in _own_frames(enc):
-        if idx < n:
-            mine.append((first + idx, r))
-            if stats is not None:  # (scored on the device already)
-                continue
+    se = cnt = 0.0  # squared error of the frames THIS process reconstructed, summed over the ranks
+    if stats is None:  # (else scored on the device already)
+        for idx, r in own:
             se += sum(float(((r[k].float() - frames[idx][k].float()) ** 2).sum()) for k in 'yuv')
             cnt += sum(frames[idx][k].numel() for k in 'yuv')
     if world > 1:
@@ -191,45 +143,87 @@ def encode(param):
     seq_res = None
     if stats is not None:  # every rank scored the frames of its units: the rows travel to rank 0 (to all, in fact)
         from ..model_mngt.model_management import lambda_tradeoff_of, sequence_result_from_rows, write_detailed_log
-        keys = enc['layout'].keys()
-        rows = parallel.gather_quality_rows(stats.rows(), keys, dev)
+        rows = parallel.gather_quality_rows(stats.rows(), enc['layout'].keys(), dev)
         if rank == 0:
-            lambdas = [lambda_tradeoff_of(model, r) for r in idx_rate] if isinstance(idx_rate, (list, tuple)) \
-                else lambda_tradeoff_of(model, idx_rate)
+            lambdas = [lambda_tradeoff_of(model, r) for r in rates] if isinstance(rates, (list, tuple)) \
+                else lambda_tradeoff_of(model, rates)
             seq_res = sequence_result_from_rows(rows, enc['nb_gop'], enc['layout'], first, n, lambdas)
-            name = os.path.basename(os.path.normpath(seq))
-            write_detailed_log(working_dir, seq_res, name[:-4] if name.endswith(('.yuv', '.y4m')) else name)
-    if digested is not None:  # 48 bytes per frame travel to rank 0 (to all, in fact), like the quality rows
-        from .. import digests
-        idxs, dig = digested
-        host = [] if dig is None else [t.cpu().numpy() for t in dig]  # y, u, v: [frames of this rank, 16] each
-        rows = {i: b''.join(d[k].tobytes() for d in host) for k, i in enumerate(idxs)}
+            write_detailed_log(working_dir, seq_res, _sequence_name(seq))
+    manifest = None
+    if want_digests:  # 48 bytes per frame travel to rank 0 (to all, in fact), like the quality rows
+        host = [] if digested is None else [t.cpu().numpy() for t in digested]  # y, u, v: [frames of this rank, 16] each
+        rows = {first + idx: b''.join(d[k].tobytes() for d in host) for k, (idx, _) in enumerate(own)}
         if world > 1:
             rows = parallel.gather_bytes_all(rows, list(range(first, first + n)), None, world, dev)
-        if rank == 0:
-            parent = os.path.dirname(final_file)
-            if parent:
-                os.makedirs(parent, exist_ok=True)
-            digests.write_manifest(digests.manifest_path(final_file), contract,
-                                   {i: (b[:16].hex(), b[16:32].hex(), b[32:].hex()) for i, b in rows.items()})
-    if get_value('flag_bitstream_debug', param, default):
-        from .decode import debug_dir, write_debug_md5
-        for idx, r in mine:  # every rank writes the digests of its own frames
-            write_debug_md5([r], idx, debug_dir(final_file))
-    if rank == 0:
-        parent = os.path.dirname(final_file)
-        if parent:
-            os.makedirs(parent, exist_ok=True)
-        with open(final_file, 'wb') as f:
-            f.write(blob)
+        manifest = (contract, {i: (b[:16].hex(), b[16:32].hex(), b[32:].hex()) for i, b in rows.items()})
+    debug = [(first + idx, r) for idx, r in own] if get_value('flag_bitstream_debug', param, default) else []
+    _write_outputs(final_file, blob, manifest, debug, rank)
     if world > 1:
         dist.barrier()  # the file exists before any rank goes on (to decode it)
     if rank != 0:
         return None
-    if seq_res is None:
-        psnr = 10 * np.log10(255.0 ** 2 / max(se / cnt, 1e-12))
+    psnr = 10 * np.log10(255.0 ** 2 / max(se / cnt, 1e-12)) if seq_res is None else seq_res['sequence']['psnr']
+    extra = {'rates': list(rates)} if target_bpp and target_bpp > 0 else {}
+    if layout is not None:
+        extra.update(cuts=[first + t for t in cuts], unit_names=list(layout.names))
+    return _report(final_file, len(blob), n, dt, psnr, seq_res, est_bits, payload, extra)
+
+
+def _source(seq, first, last, dev, pix_fmt, size, resample):
+    """sequence_path -> (frames, first, last): a folder of pictures or a raw video file, then the optional resize.  THE ONE PLACE
+    that looks at what sequence_path is."""
+    if os.path.isdir(seq):
+        frames, first, last = read_png_folder(seq, first, last, dev)
     else:
-        psnr = seq_res['sequence']['psnr']
+        frames, first, last = read_yuv(seq, first, last, dev, pix_fmt)
+    if size is not None:
+        from ..func_util.img_processing import resize_frames
+        frames = resize_frames(frames, int(size[0]), int(size[1]), resample, dev)
+    return frames, first, last
+
+
+def _sequence_name(seq):
+    """the name detailed.txt gives the clip: the folder's or the file's, without the file's extension"""
+    name = os.path.basename(os.path.normpath(seq))
+    return name[:-4] if name.endswith(('.yuv', '.y4m')) else name
+
+
+def _code(fc, frames, gop_name, first, last, idx_rate, target_bpp, rate_step, stats, layout, rank, world, dev):
+    """frames -> (bitstream: None off rank 0, this rank's encode_video record, the rate index: idx_rate as given, or the list
+    with one per unit that a byte budget chose).  Under a budget every rank searches its units; else one process per GPU shares
+    the intra-period units out, the container on rank 0; else this process codes them all."""
+    from .. import parallel
+    lay = {} if layout is None else {'layout': layout}
+    if target_bpp and target_bpp > 0:
+        return _encode_budgeted(fc, frames, gop_name, target_bpp, rate_step, first, stats, rank, world, dev, layout)
+    if world > 1:
+        blob, enc = parallel.encode_video_sharded(fc, frames, gop_name, first, idx_rate=idx_rate, return_enc=True, stats=stats, **lay)
+    else:
+        enc = fc.encode_video(frames, gop_name, idx_starting_frame=first, idx_end_frame=last, idx_rate=idx_rate, stats=stats, **lay)
+        blob = fc.assemble_video(enc)
+    return blob, enc, idx_rate
+
+
+def _write_outputs(final_file, blob, manifest, debug, rank):
+    """the files next to the bitstream and the bitstream: rank 0 writes the manifest ((contract, rows) or None) and the
+    bitstream, every rank the debug digests of its own frames ([(absolute index, reconstruction)])"""
+    parent = os.path.dirname(final_file)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    if manifest is not None and rank == 0:
+        from .. import digests
+        digests.write_manifest(digests.manifest_path(final_file), manifest[0], manifest[1])
+    if debug:
+        from .decode import debug_dir, write_debug_md5
+        for idx, r in debug:
+            write_debug_md5([r], idx, debug_dir(final_file))
+    if rank == 0:
+        with open(final_file, 'wb') as f:
+            f.write(blob)
+
+
+def _report(final_file, real_byte, n, dt, psnr, seq_res, est_bits, payload, extra):
+    """rank 0: the RESULT lines -> the dictionary encode() returns; extra: the entries a byte budget and scene cuts add"""
     print_log_msg('INFO', 'Encoding done', '', '')
     print_log_msg('INFO', 'Bitstream path', '', final_file)
     print_log_msg('RESULT', 'Number of frames', '[frame]', int(n))
@@ -244,19 +238,16 @@ def encode(param):
     # is the file, whose overhead over the estimate is the range coder's flush (< 2 bytes per stream), the map lists
     # and the container's length prefixes and headers.
     est_byte = est_bits / 8
-    overhead = (len(blob) / est_byte - 1) * 100 if est_byte > 0 else float('nan')
+    overhead = (real_byte / est_byte - 1) * 100 if est_byte > 0 else float('nan')
     print_log_msg('RESULT', 'Estimated rate', '[byte]', '%.1f' % est_byte)
-    print_log_msg('RESULT', 'Real rate', '[byte]', len(blob))
+    print_log_msg('RESULT', 'Real rate', '[byte]', real_byte)
     print_log_msg('RESULT', 'Estimated rate overhead', '[%]', '%.2f' % overhead)
-    out = {'real_rate_byte': len(blob), 'psnr': psnr, 'nb_frames_to_code': n, 'estimated_rate_byte': est_byte,
+    out = {'real_rate_byte': real_byte, 'psnr': psnr, 'nb_frames_to_code': n, 'estimated_rate_byte': est_byte,
            'rate_overhead_percent': overhead, 'range_coder_payload_byte': int(payload)}
     if seq_res is not None:
         avg = seq_res['sequence']
         out.update(ms_ssim_db=avg['ms_ssim_db'], h=avg['h'], w=avg['w'], nb_coded_frames=len(seq_res) - 1)
-    if budgeted is not None:
-        out['rates'] = list(idx_rate)
-    if layout is not None:
-        out.update(cuts=[first + t for t in cuts], unit_names=list(layout.names))
+    out.update(extra)
     return out
 
 

@@ -2,11 +2,15 @@
 running the reference's own functions; then the command-line path on a folder of RGB pictures, end to end.  The folders are
 written here with PIL from the fixture's pictures.  Every comparison is exact."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import scene_cases as cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -96,7 +100,7 @@ def test_rgb_folder_end_to_end(cuda, tmp_path):
     from aivc_amd import ops, synth
     from aivc_amd.func_util.GOP_structure import generate_gop_struct
     from aivc_amd.models import arch
-    from aivc_amd.real_life.decode import Decoder, decode_one_video, write_yuv
+    from aivc_amd.real_life.decode import Decoder, decode_one_video
     from aivc_amd.real_life.encode import encode
     w, h, n = 64, 48, 3
     rng = np.random.default_rng(3)
@@ -108,7 +112,8 @@ def test_rgb_folder_end_to_end(cuda, tmp_path):
         Image.fromarray(rgb[i], 'RGB').save(os.path.join(src, '%d.png' % i))
     y, u, v = ops.rgb8_to_yuv420u8(torch.from_numpy(rgb).to(cuda))
     yuv = str(tmp_path / ('clip_%dx%d_25_420.yuv' % (w, h)))
-    write_yuv([{'y': y[i:i + 1], 'u': u[i:i + 1], 'v': v[i:i + 1]} for i in range(n)], yuv)
+    y, u, v = (t.cpu().numpy() for t in (y, u, v))
+    cases.write_yuv(yuv, [{'y': y[i], 'u': u[i], 'v': v[i]} for i in range(n)])
 
     model = synth.make_model(arch.TINY_WIDTHS, seed=7, device=cuda)
     blobs = {}

@@ -203,6 +203,33 @@ def test_reader_spans_two_batches(tmp_path, cuda, monkeypatch):
         assert all(np.array_equal(fr[k][0].cpu().numpy(), want[i]) for i, k in enumerate('yuv'))
 
 
+@pytest.mark.parametrize('w,h', [(1, 1), (5, 3), (17, 5), (257, 2)])
+def test_plain_file_planes_are_the_files_bytes(w, h, tmp_path, cuda, capsys):
+    """a headerless planar 8-bit 4:2:0 file through read_yuv -- the one reader -- and back through write_raw -- the one writer:
+    the planes are numpy's slices of the file, the file written from them is the file.  5 x 3: 27-byte frames, so odd frame
+    starts, odd sides, ceil-sized chroma; 17 and 257: a row one byte past one and sixteen 16-byte chunks; 1 x 1: the smallest"""
+    from aivc_amd import rawvideo
+    from aivc_amd.real_life.encode import read_yuv
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    data = np.random.default_rng([w, h]).integers(0, 256, (3, h * w + 2 * hc * wc), dtype=np.uint8)
+    path = str(tmp_path / ('clip_%dx%d_25_420.yuv' % (w, h)))
+    data.tofile(path)
+    want = [{'y': fr[:h * w].reshape(1, h, w), 'u': fr[h * w:h * w + hc * wc].reshape(1, hc, wc),
+             'v': fr[h * w + hc * wc:].reshape(1, hc, wc)} for fr in data]
+    for (first, last), span in (((0, -1), (0, 2)), ((1, 2), (1, 2))):
+        frames, a, b = read_yuv(path, first, last, cuda)
+        assert (a, b) == span and len(frames) == b - a + 1
+        for fr, ref in zip(frames, want[a:]):
+            for k in 'yuv':
+                assert fr[k].is_cuda and fr[k].dtype == torch.uint8 and tuple(fr[k].shape) == ref[k].shape
+                assert np.array_equal(fr[k].cpu().numpy(), ref[k]), (w, h, first, k)
+        assert both_fills(lambda fill: read_yuv(path, first, last, cuda)[0]) == [{k: ref[k].tobytes() for k in 'yuv'} for ref in want[a:]]
+        out = str(tmp_path / 'back.yuv')
+        rawvideo.write_raw(frames, out, 'yuv420p')
+        assert open(out, 'rb').read() == data[a:].tobytes()
+    assert '[INFO] input:' not in capsys.readouterr().out
+
+
 def test_write_raw_y4m_reads_back(tmp_path, cuda):
     from aivc_amd import rawvideo
     rng = np.random.default_rng(9)

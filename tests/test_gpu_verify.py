@@ -247,6 +247,29 @@ def test_trial_decode_for_a_request_that_does_not_touch_unit_0(model, cuda, clis
     assert ops.precision_name() == default
 
 
+def test_encode_stages_write_the_bytes_of_the_one_body(model, cuda, golden, tmp_path, capsys):
+    """encode() with the quality log, the manifest, scene cuts and flag_bitstream_debug all on: the bitstream, the manifest and
+    detailed.txt are the bytes the commit before the stages wrote for the same call without the debug flag
+    (tests/golden/encode_stages.npz, tools/gen_golden_encode_stages.py); the debug digests -- one per reconstructed plane, of
+    every frame that is not padding -- are accepted by check_debug_md5 against the decode of that bitstream"""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
+    import gen_golden_encode_stages as gen
+    from aivc_amd.real_life.decode import Decoder, check_debug_md5, debug_dir, decode_one_video
+    fx = golden('encode_stages')
+    out, files = gen.encode_case(model, str(tmp_path), flag_bitstream_debug=True)
+    blob = open(files['bitstream'], 'rb').read()
+    assert blob == fx['bitstream'].tobytes()
+    assert open(files['manifest']).read() == str(fx['manifest'])
+    assert open(files['detailed']).read() == str(fx['detailed'])
+    assert out['real_rate_byte'] == len(blob) and out['nb_frames_to_code'] == gen.N
+    assert sorted(os.listdir(debug_dir(files['bitstream']))) == sorted('%d_%s.md5' % (i, c) for i in range(gen.N) for c in 'yuv')
+    frames = decode_one_video({'decoder': Decoder({'full_net': model}).eval(), 'bitstream_path': files['bitstream'], 'device': str(cuda)})
+    capsys.readouterr()
+    assert len(frames) == gen.N and check_debug_md5(frames, 0, debug_dir(files['bitstream'])) == 0
+    assert capsys.readouterr().out.count('Identical reconstruction!') == 3 * gen.N
+
+
 def test_two_ranks_write_the_manifest_of_one_process(model, cuda, tmp_path):
     """aivc.py --digests under `torch.distributed.run` with two ranks on the one GPU over gloo (as
     tests/test_gpu_multi_process.py::test_cli_two_ranks_equals_one_process): every rank digests the units it coded, the 48-byte

@@ -238,30 +238,46 @@ def test_request_past_the_end_names_the_range(tmp_path):
 def test_headerless_names(file, name, tmp_path):
     from aivc_amd import rawvideo
     assert rawvideo.pix_fmt_from_name('/some/dir/' + file).name == name
-    assert rawvideo.needs_conversion(file) == (name != 'yuv420p')
-    assert rawvideo.needs_conversion(file, 'nv12') and rawvideo.needs_conversion('x.y4m')
     w, h = rawvideo.parse_size_name(file)
     path = tmp_path / file
     path.write_bytes(b'\0' * (rvc.frame_bytes(name, w, h) * 2 + 1))
     rd = rawvideo.open_raw(str(path))
     assert (rd.w, rd.h, rd.fps, rd.n_frames, rd.pix_fmt.name) == (w, h, None, 2, name)
+    # the reader's one predicate (whether read_yuv announces a conversion), where needs_conversion(name, pix_fmt) was asked
+    assert (not rd.is_plain) == (name != 'yuv420p')
+    y4m, _ = _clip(tmp_path, 'yuv420p', file='x.y4m')
+    assert not rawvideo.open_raw(str(path), 'nv12').is_plain and not rawvideo.open_raw(y4m).is_plain
     rd = rawvideo.open_raw(str(path), 'gray', (2, 2))  # pix_fmt and size given: the name is not consulted
     assert (rd.w, rd.h, rd.pix_fmt.name, rd.n_frames) == (2, 2, 'gray', (rvc.frame_bytes(name, w, h) * 2 + 1) // 4)
     with pytest.raises(rawvideo.RawVideoError):
         rawvideo.parse_size_name('nosize_420.yuv')
 
 
-def test_plain_files_keep_the_old_reader(tmp_path, monkeypatch):
-    """read_yuv is the one place that decides: a plain *_420.yuv never reaches aivc_amd.rawvideo's reader"""
+def test_plain_files_go_through_the_one_reader(tmp_path):
+    """a plain *_420.yuv is a file of the reader like any other: frames back to back, a truncated tail not counted, a request
+    outside it refused with its range -- by encode.py with exit status 2 before a device is looked for, as for a .y4m.  (That the
+    planes are the file's bytes is tests/test_gpu_rawvideo.py::test_plain_file_planes_are_the_files_bytes.)"""
+    from aivc_amd import encode as enc_cli
     from aivc_amd import rawvideo
-    from aivc_amd.real_life import encode as enc
-    monkeypatch.setattr(rawvideo, 'open_raw', lambda *a, **k: pytest.fail('the converting reader was opened'))
+    for w, h in ((4, 2), (5, 3), (1, 1)):
+        fb = w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+        path = tmp_path / ('clip_%dx%d_25_420.yuv' % (w, h))
+        for tail in (0, 1, fb - 1):
+            path.write_bytes(b'\1' * (3 * fb + tail))
+            with rawvideo.open_raw(str(path)) as rd:
+                assert rd.is_plain and (rd.w, rd.h, rd.frame_bytes, rd.n_frames) == (w, h, fb, 3)
+                assert rd.offsets == [i * fb for i in range(3)]
+                assert rd.frame_range(0, -1) == (0, 2) and rd.frame_range(1, 2) == (1, 2)
+                for first, last in ((0, 3), (3, -1), (2, 1), (-1, 1)):
+                    with pytest.raises(rawvideo.RawVideoError) as e:
+                        rd.frame_range(first, last)
+                    assert '0 ... 2' in str(e.value)
     path = tmp_path / 'clip_4x2_25_420.yuv'
-    data = np.arange(24, dtype=np.uint8)
-    path.write_bytes(data.tobytes())
-    frames, first, last = enc.read_yuv(str(path), 0, -1, 'cpu')
-    assert (first, last) == (0, 1) and frames[1]['y'].shape == (1, 2, 4)
-    assert np.array_equal(np.concatenate([frames[1][k].numpy().reshape(-1) for k in 'yuv']), data[12:])
+    path.write_bytes(b'\0' * (12 * 2 + 5))  # two frames and a truncated one
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf), pytest.raises(SystemExit) as e:
+        enc_cli.main(['-i', str(path), '-o', str(tmp_path / 'x.bin'), '--start_frame', '2'])
+    assert e.value.code == 2 and '[ERROR]' in buf.getvalue() and '0 ... 1' in buf.getvalue() and not os.path.exists(tmp_path / 'x.bin')
 
 
 # ---- flags --------------------------------------------------------------------------------------------------------------------------

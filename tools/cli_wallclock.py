@@ -65,6 +65,8 @@ def main():
     run('warm_call')
     res['bitstream_bytes'] = os.path.getsize(bits)
     res['decoded_bytes'] = os.path.getsize(dec)
+    from aivc_amd import ops
+    res['pinned_staging_bytes'] = sum(buf.numel() for _, buf in ops._STAGING)  # the pool keeps its buffers (the clip went through it)
     wc = res['warm_call']
     res['warm_with_model_build_fps'] = round(n / (wc['encode_s'] + wc['decode_s'] + 2 * res['model_build_s']), 2)
     res['note'] = ('encode = read .yuv from local disk + H2D + FrameCodec.encode_video + write the container; decode = read the '

@@ -32,6 +32,7 @@ def load():
         _lib = C.CDLL(LIB_PATH)
         fns = abi.declare(_lib)
         fns.update(abi.declare_rawvideo(_lib))
+        fns.update(abi.declare_png(_lib))
     except (OSError, AttributeError) as e:
         raise AivcNativeError('aivc_amd: cannot load %s: %s' % (LIB_PATH, e))
     err = _lib.aivc_last_error

@@ -1,6 +1,6 @@
 """ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h,
-include/aivc_hip_rates.h, include/aivc_hip_digest.h, include/aivc_hip_scene.h, include/aivc_hip_resize.h and
-include/aivc_hip_rawvideo.h (struct layouts, constants, prototypes).
+include/aivc_hip_rates.h, include/aivc_hip_digest.h, include/aivc_hip_scene.h, include/aivc_hip_resize.h,
+include/aivc_hip_rawvideo.h and include/aivc_hip_png.h (struct layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -270,6 +270,26 @@ def declare_rawvideo(lib):
     the library does not export one of them."""
     fns = {}
     for name, args in RAWVIDEO_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = list(args) + [C.c_void_p]
+        fn.restype = C.c_int
+        fns[name] = fn
+    return fns
+
+
+# include/aivc_hip_png.h: device only (their statement is Pillow and zlib reading the result: tests/test_gpu_png.py)
+PNG_RUN, PNG_SEG_WORDS = 32, 4  # AIVC_PNG_RUN, AIVC_PNG_SEG_WORDS
+PNG_PROTOTYPES = {
+    'aivc_png_deflate': [_f, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _f],
+    'aivc_png_gather': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _f],
+}
+
+
+def declare_png(lib):
+    """Attach argtypes/restype for the entries of include/aivc_hip_png.h (device library only), beside declare() for the reason
+    declare_rawvideo states; raises AttributeError when the library does not export one of them."""
+    fns = {}
+    for name, args in PNG_PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.argtypes = list(args) + [C.c_void_p]
         fn.restype = C.c_int

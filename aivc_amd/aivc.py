@@ -48,6 +48,7 @@ def parse_args(argv=None):
     enc_cli.add_scene_flag(p)
     enc_cli.add_pix_fmt_flag(p)
     dec_cli.add_out_format_flags(p)
+    dec_cli.add_png_coder_flag(p)
     from aivc_amd.resize import add_resize_flags, check_resize_flags
     add_resize_flags(p, {'--size': enc_cli.SIZE_HELP, '--out_size': dec_cli.OUT_SIZE_HELP})
     a = p.parse_args(argv)
@@ -56,6 +57,7 @@ def parse_args(argv=None):
     a.resample = check_resize_flags(p, a, ('--size', '--out_size'))
     dec_cli.check_out_size(p, a, a.o)
     dec_cli.check_out_format(p, a, a.o)
+    dec_cli.check_png_coder(p, a, a.o)
     return a
 
 
@@ -96,6 +98,7 @@ def main(argv=None):
                           + (['--out_size', size_text(a.out_size), '--resample', a.resample] if a.out_size is not None else [])
                           + (['--out_pix_fmt', a.out_pix_fmt] if a.out_pix_fmt != 'yuv420p' else [])
                           + (['--fps', '%d:%d' % a.fps] if a.fps != (25, 1) else [])
+                          + (['--png_coder', a.png_coder] if a.png_coder != 'pillow' else [])
                           + (['--contract', a.contract] if a.contract else []))
     from aivc_amd import parallel
     if parallel.rank_world()[0] != 0:  # multi-rank job: rank 0 evaluates

@@ -40,6 +40,23 @@ def check_out_format(p, a, out):
         p.error(str(e))
 
 
+def add_png_coder_flag(p):
+    """--png_coder {pillow,device} (shared with aivc.py)"""
+    from aivc_amd.png import CODERS
+    p.add_argument('--png_coder', default='pillow', choices=CODERS,
+                   help='who codes the <idx>.png pictures of a folder given as -o: pillow (one Image.save per frame on the host, the '
+                        'default) or device (row filters and a Huffman deflate on the GPU: the same pixels, other bytes)')
+
+
+def check_png_coder(p, a, out):
+    """an argparse error for --png_coder device where -o is not a picture folder"""
+    from aivc_amd import png
+    try:
+        png.check_coder(a.png_coder, out, is_png_folder(out))
+    except ValueError as e:
+        p.error(str(e))
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--cpu', action='store_true')
@@ -56,10 +73,12 @@ def parse_args(argv=None):
                    help='partial decode: only frames of temporal level <= L (the dependency depth inside an intra-period unit: '
                         '0 the I frame, 1 the P frame; 1_GOP_32 has levels 0 ... 6, each one less halves the frame count)')
     add_out_format_flags(p)
+    add_png_coder_flag(p)
     from aivc_amd.resize import add_resize_flags, check_resize_flags
     add_resize_flags(p, {'--out_size': OUT_SIZE_HELP})
     a = p.parse_args(argv)
     check_out_format(p, a, a.o)
+    check_png_coder(p, a, a.o)
     if a.max_level is not None and a.max_level < 0:
         p.error('--max_level %d: temporal levels count from 0' % a.max_level)
     a.resample = check_resize_flags(p, a, ('--out_size',))
@@ -93,7 +112,8 @@ def main(argv=None):
         with contract_scope(a.contract):
             decode_one_video({'decoder': dec, 'bitstream_path': a.i, 'device': str(dev), 'out_file': out, 'verify': a.verify,
                               'contract': 'auto' if a.contract == 'auto' else '', 'frames': a.frames, 'max_level': a.max_level,
-                              'out_size': a.out_size, 'resample': a.resample, 'out_pix_fmt': a.out_pix_fmt, 'fps': a.fps})
+                              'out_size': a.out_size, 'resample': a.resample, 'out_pix_fmt': a.out_pix_fmt, 'fps': a.fps,
+                              'png_coder': a.png_coder})
     except ContainerError as e:  # a truncated / damaged file: say so and stop (exit status 2), no frames are written
         print('[ERROR] %s is not a complete bitstream: %s' % (a.i, e))
         raise SystemExit(2)

@@ -1,6 +1,7 @@
 """Image helpers with the reference's names (src/func_util/img_processing.py).
 
-PNG decoding and encoding is file I/O and stays Pillow on the host; colour conversion and chroma resampling run on the device
+PNG decoding is file I/O and stays Pillow on the host, and so does PNG encoding unless a caller asks for coder='device'
+(aivc_amd/png.py: the same pixels, coded on the device); colour conversion and chroma resampling run on the device
 (ops.rgb8_to_yuv420u8 / ops.yuv8_to_rgb8, include/aivc_hip_color.h), bit for bit what Pillow computes for the reference.
 
 The loaders return what the reference returns -- float tensors in [0, 1], value k / 255 for the 8-bit level k -- but on the
@@ -156,12 +157,17 @@ def _chw(x):
     return x[0] if x.ndim == 4 else x
 
 
-def _save_png(a, path_img, mode):
+def _save_png(a, path_img, mode, coder='pillow'):
+    """a: uint8 [h, w, 3] ('RGB') or [h, w] ('L').  coder 'device': coded where the tensor lies (aivc_amd.png.write_pictures)"""
+    from .. import png
+    if png.check_coder(coder) == 'device':
+        png.write_pictures(a.reshape((1,) + tuple(a.shape[:2]) + (3 if mode == 'RGB' else 1,)), [path_img])
+        return
     from PIL import Image
     Image.fromarray(np.ascontiguousarray(a.cpu().numpy()), mode).save(path_img)
 
 
-def save_tensor_as_img(x, path_img, mode='yuv420'):
+def save_tensor_as_img(x, path_img, mode='yuv420', coder='pillow'):
     """src/func_util/img_processing.py:221-287.  x holds floats in [0, 1] (cast like to_pil_image: mul(255), truncated) or uint8
     levels, on the device.
       'yuv420'        x: dict, chroma at half resolution -> nearest x 2, cropped to the luma size, YCbCr -> RGB on the device
@@ -170,20 +176,21 @@ def save_tensor_as_img(x, path_img, mode='yuv420'):
       'rgb'           x: [1,3,h,w] or [3,h,w] tensor; the planar -> interleaved step is a torch permute of the uint8 tensor
       'L'             x: [1,1,h,w] or [1,h,w] tensor
     Only batch entry 0 is written, as in the reference.  'yuv420' with floor-sized chroma and an odd luma size repeats the
-    last chroma row / column (the reference raises there: its upsampled planes are one short)."""
+    last chroma row / column (the reference raises there: its upsampled planes are one short).
+    coder: 'pillow', or 'device' for a file coded on the device (aivc_amd/png.py): the same pixels, other bytes."""
     if mode in ('yuv420', 'yuv444'):
         y, u, v = (_to_u8(_chw(t)) for t in get_y_u_v(x))
         y, u, v = (t.reshape(1, t.shape[-2], t.shape[-1]) for t in (y, u, v))
         rgb = ops.yuv8_to_rgb8(y, u, v, chroma_shift=1 if mode == 'yuv420' else 0)
-        _save_png(rgb[0], path_img, 'RGB')
+        _save_png(rgb[0], path_img, 'RGB', coder)
     elif mode == 'yuv444_nodic':
         p = _to_u8(_chw(x))
         rgb = ops.yuv8_to_rgb8(p[0:1], p[1:2], p[2:3], chroma_shift=0)
-        _save_png(rgb[0], path_img, 'RGB')
+        _save_png(rgb[0], path_img, 'RGB', coder)
     elif mode == 'rgb':
-        _save_png(_to_u8(_chw(x)).permute(1, 2, 0), path_img, 'RGB')
+        _save_png(_to_u8(_chw(x)).permute(1, 2, 0), path_img, 'RGB', coder)
     elif mode == 'L':
-        _save_png(_to_u8(_chw(x))[0], path_img, 'L')
+        _save_png(_to_u8(_chw(x))[0], path_img, 'L', coder)
     else:
         raise ValueError('save_tensor_as_img: mode %r' % (mode,))
 

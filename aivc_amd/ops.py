@@ -760,6 +760,52 @@ def yuv420u8_to_raw(y, u, v, fmt, lead=b''):
     return out
 
 
+def png_encode(pix, filter=5):
+    """8-bit pictures -> one zlib stream each, the payload of a PNG's IDAT chunk (include/aivc_hip_png.h; the container is
+    aivc_amd.png.assemble).  pix: uint8 CUDA tensor [n, h, w, c], c = 1 (grey) or 3 (RGB); filter: 0 ... 4 for every row, 5 the
+    smallest sum of absolute residuals per row.  -> a list of n bytes objects.  A picture's bytes depend on its pixels and the
+    filter alone.  Batches of at most 256 MiB of pixels; per batch three launches and two host synchronisations: the segments'
+    lengths and Adler sums, then the bytes."""
+    from . import png, rawvideo
+    pix = _dev(pix, torch.uint8, 'pix')
+    if pix.dim() != 4:
+        raise ValueError('png_encode: expected [n, h, w, c], got %s' % (tuple(pix.shape),))
+    n, h, w, c = pix.shape
+    if filter not in png.FILTERS:
+        raise ValueError('png_encode: filter %r, expected 0 ... 5' % (filter,))
+    if n == 0:
+        return []
+    rows, nseg, seg_stride, slot_bytes = png.segment_plan(h, w, c)
+    lengths = png.segment_lengths(h, w, c)
+    if rows * (1 + w * c) >= 1 << 31:
+        raise ValueError('png_encode: a row of %d bytes, the kernel takes segments of less than 2^31' % (1 + w * c))
+    per = max(1, rawvideo.BATCH_BYTES // (h * w * c))
+    streams = []
+    for i0 in range(0, n, per):
+        part = pix[i0:i0 + per]
+        k = part.shape[0]
+        filt = torch.empty(k * nseg * seg_stride, dtype=torch.uint8, device=pix.device)
+        slots = torch.empty(k * nseg * slot_bytes, dtype=torch.uint8, device=pix.device)
+        info = torch.empty((k * nseg, abi.PNG_SEG_WORDS), dtype=torch.int32, device=pix.device)
+        _hbm_profiled('png_deflate', k * h * (2 * w * c + 1),
+                      lambda: call('aivc_png_deflate', _p(part), k, h, w, c, filter, rows, _p(filt), _p(slots), _p(info), _stream()))
+        seg = info.cpu().numpy().view(np.uint32).astype(np.int64)  # (synchronises: the lengths)
+        sizes = seg[:, 0].reshape(k, nseg)
+        totals = 2 + sizes.sum(1) + 5 + 4  # header, segments, the final empty block, the Adler-32
+        starts = np.concatenate([[0], np.cumsum(totals)[:-1]])
+        dst = (starts[:, None] + 2 + np.cumsum(sizes, 1) - sizes).astype(np.uint64)
+        table, _ = _stage(pix.device, [dst.reshape(-1).view(np.uint8)])
+        out = torch.empty(int(totals.sum()), dtype=torch.uint8, device=pix.device)
+        _hbm_profiled('png_gather', 2 * int(sizes.sum()),
+                      lambda: call('aivc_png_gather', _p(slots), _p(info), _p(table), k, h, w, c, rows, _p(out), _stream()))
+        host = out.cpu().numpy()  # (synchronises: the bytes)
+        for j in range(k):
+            adler = png.adler_fold(zip(lengths, seg[j * nseg:(j + 1) * nseg, 1].tolist(), seg[j * nseg:(j + 1) * nseg, 2].tolist()))
+            lo, hi = int(starts[j]), int(starts[j] + totals[j])
+            streams.append(host[lo:hi - 4].tobytes() + adler.to_bytes(4, 'big'))
+    return streams
+
+
 def downsample2x(x, ch0, nch):
     """NHWC x -> planar [n, nch, h//2, w//2] 2x2 means of channels ch0..ch0+nch-1 (OutputLayer)."""
     x = _dev(x, torch.float32, 'x')

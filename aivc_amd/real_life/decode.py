@@ -78,12 +78,25 @@ class Decoder(Module):
         return _to_float_dic(rec)
 
 
-def write_png_folder(frames, directory, device, indices):
+def write_png_folder(frames, directory, device, indices, coder='pillow'):
     """decoded frames -> <directory>/<idx>.png, RGB pictures (func_util.img_processing.save_tensor_as_img, mode 'yuv420':
     the colour conversion runs on the device, straight from the decoder's 8-bit planes).  indices: the absolute index of
-    every frame handed in"""
-    from ..func_util.img_processing import save_tensor_as_img
+    every frame handed in.  coder: 'pillow' (one Image.save per frame on the host) or 'device': the planes of a batch of at
+    most 256 MiB of pixels take one colour launch and are coded on the device (aivc_amd.png.write_pictures) -- the same names,
+    the same pixels, other bytes"""
+    from .. import png
+    png.check_coder(coder)
     os.makedirs(directory, exist_ok=True)
+    if coder == 'device' and frames:
+        from .. import ops, rawvideo
+        h, w = frames[0]['y'].shape[-2:]
+        per = max(1, rawvideo.BATCH_BYTES // (3 * h * w))
+        for i0 in range(0, len(frames), per):
+            part = frames[i0:i0 + per]
+            y, u, v = (torch.cat([torch.as_tensor(fr[k]).to(device).reshape((1,) + tuple(fr[k].shape[-2:])) for fr in part]) for k in 'yuv')
+            png.write_pictures(ops.yuv8_to_rgb8(y, u, v, chroma_shift=1), [os.path.join(directory, '%d.png' % idx) for idx in indices[i0:i0 + per]])
+        return
+    from ..func_util.img_processing import save_tensor_as_img
     for idx, fr in zip(indices, frames):
         save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % idx), mode='yuv420')
 
@@ -146,10 +159,12 @@ def decode_one_video(param):
     an out_file that ends in .y4m gets a header and `FRAME` lines, fps: its frame rate (numerator, denominator) -- the stream
     stores none, default (25, 1).  The export runs on the device after the resize (aivc_amd.rawvideo.write_raw, for every file:
     yuv420p into a headerless file is the planes one after the other); the frames that are returned, verified and digested stay
-    the 8-bit planes."""
+    the 8-bit planes.
+    png_coder: 'pillow' (the default) or 'device', who codes the pictures of a folder (write_png_folder); 'device' with an
+    out_file that names a raw video file is a ValueError."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
                'verify': '', 'contract': '', 'frames': None, 'max_level': None, 'out_size': None, 'resample': 'bicubic', 'out_pix_fmt': 'yuv420p',
-               'fps': (25, 1)}
+               'fps': (25, 1), 'png_coder': 'pillow'}
     decoder = get_value('decoder', param, default).eval()
     path = get_value('bitstream_path', param, default)
     dev = torch.device(get_value('device', param, default))
@@ -165,6 +180,8 @@ def decode_one_video(param):
     from .. import rawvideo
     out_fmt = rawvideo.check_writable(get_value('out_pix_fmt', param, default), '' if is_png_folder(out_file) else out_file)
     raw_out = (out_fmt, tuple(get_value('fps', param, default)))  # (layout, frame rate) of a file that is written
+    from .. import png
+    png_coder = png.check_coder(get_value('png_coder', param, default), out_file or None, is_png_folder(out_file))
     manifest = None
     manifest_file = verify if isinstance(verify, str) and verify else digests.manifest_path(path)
     if verify or (contract == 'auto' and os.path.exists(manifest_file)):
@@ -181,7 +198,7 @@ def decode_one_video(param):
         elif contract:
             ops.set_precision(contract)
         return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default),
-                                 resize, raw_out)
+                                 resize, raw_out, png_coder)
     finally:
         ops.set_precision(prev_precision)
 
@@ -200,7 +217,7 @@ def read_plan(path, span, max_level):
     return plan._replace(video=video._replace(gops=gops))
 
 
-def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize, raw_out):
+def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize, raw_out, png_coder='pillow'):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel, partial
@@ -242,7 +259,7 @@ def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstre
         from ..func_util.img_processing import resize_frames
         frames = resize_frames(frames, resize[0], resize[1], resize[2], dev)
     if is_png_folder(out_file):
-        write_png_folder(frames, out_file, dev, shown)
+        write_png_folder(frames, out_file, dev, shown, png_coder)
     elif out_file:  # (after the resize: the export sees the size that is written)
         from .. import rawvideo
         rawvideo.write_raw(frames, out_file, raw_out[0], raw_out[1], dev)

@@ -33,6 +33,7 @@ def load():
         fns = abi.declare(_lib)
         fns.update(abi.declare_rawvideo(_lib))
         fns.update(abi.declare_png(_lib))
+        fns.update(abi.declare_png_read(_lib))
     except (OSError, AttributeError) as e:
         raise AivcNativeError('aivc_amd: cannot load %s: %s' % (LIB_PATH, e))
     err = _lib.aivc_last_error

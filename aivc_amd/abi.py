@@ -1,6 +1,6 @@
 """ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h,
 include/aivc_hip_rates.h, include/aivc_hip_digest.h, include/aivc_hip_scene.h, include/aivc_hip_resize.h,
-include/aivc_hip_rawvideo.h and include/aivc_hip_png.h (struct layouts, constants, prototypes).
+include/aivc_hip_rawvideo.h, include/aivc_hip_png.h and include/aivc_hip_png_read.h (struct layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -290,6 +290,31 @@ def declare_png(lib):
     declare_rawvideo states; raises AttributeError when the library does not export one of them."""
     fns = {}
     for name, args in PNG_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = list(args) + [C.c_void_p]
+        fn.restype = C.c_int
+        fns[name] = fn
+    return fns
+
+
+# include/aivc_hip_png_read.h: device only (their statement is zlib.decompress and Pillow: tests/test_gpu_png_read.py)
+INFLATE_OK = 0
+INFLATE_STATUS = {0: 'ok', 1: 'the source ends inside the stream', 2: 'bad zlib header', 3: 'reserved block type',
+                  4: 'stored block: NLEN is not ~LEN', 5: 'bad set of code lengths', 6: 'invalid symbol',
+                  7: 'a match that starts before the output', 8: 'more output than expected', 9: 'less output than expected',
+                  10: 'Adler-32 mismatch', 11: 'a stream of 2^31 bytes or more'}  # AIVC_INFLATE_*
+PNG_UNFILTER_STATUS = {0: 'ok', 1: 'a filter type above 4', 2: 'a shape the kernel does not take'}  # AIVC_PNG_UNFILTER_*
+PNG_READ_PROTOTYPES = {
+    'aivc_inflate': [_f, _f, _i32, C.c_uint64, C.c_uint64, _f, _f],
+    'aivc_png_unfilter': [_f, _f, _i32, C.c_uint64, _f, _f],
+}
+
+
+def declare_png_read(lib):
+    """Attach argtypes/restype for the entries of include/aivc_hip_png_read.h (device library only), beside declare() for the
+    reason declare_rawvideo states; raises AttributeError when the library does not export one of them."""
+    fns = {}
+    for name, args in PNG_READ_PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.argtypes = list(args) + [C.c_void_p]
         fn.restype = C.c_int

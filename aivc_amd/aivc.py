@@ -47,6 +47,7 @@ def parse_args(argv=None):
     enc_cli.add_rate_flags(p)
     enc_cli.add_scene_flag(p)
     enc_cli.add_pix_fmt_flag(p)
+    enc_cli.add_png_reader_flag(p)
     dec_cli.add_out_format_flags(p)
     dec_cli.add_png_coder_flag(p)
     from aivc_amd.resize import add_resize_flags, check_resize_flags
@@ -54,6 +55,7 @@ def parse_args(argv=None):
     a = p.parse_args(argv)
     enc_cli.check_rate_flags(p, a)
     enc_cli.check_scene_flag(p, a)
+    enc_cli.check_png_reader(p, a)
     a.resample = check_resize_flags(p, a, ('--size', '--out_size'))
     dec_cli.check_out_size(p, a, a.o)
     dec_cli.check_out_format(p, a, a.o)
@@ -88,6 +90,7 @@ def main(argv=None):
                  + (['--digests'] if a.digests else [])
                  + (['--scene_cut', repr(a.scene_cut)] if a.scene_cut is not None else [])
                  + (['--pix_fmt', a.pix_fmt] if a.pix_fmt is not None else [])
+                 + (['--png_reader', a.png_reader] if a.png_reader != 'pillow' else [])
                  + (['--size', size_text(a.size), '--resample', a.resample] if a.size is not None else [])
                  + (['--contract', a.contract] if a.contract not in (None, 'auto') else []))  # (auto is the decoder's choice)
     banner(('*' * 80).center(120))

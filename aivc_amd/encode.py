@@ -68,6 +68,25 @@ def add_pix_fmt_flag(p):
                         'digested and scored by --log_dir are the converted planes' % ', '.join(PIX_FMTS))
 
 
+def add_png_reader_flag(p):
+    """--png_reader {pillow,device} (shared with aivc.py)"""
+    from aivc_amd.png import READERS
+    p.add_argument('--png_reader', default='pillow', choices=READERS,
+                   help='who reads the pictures of a folder given as -i: pillow (one Image.open per picture on the host, the default) or '
+                        'device (8-bit grey and RGB pictures are inflated and unfiltered on the device, all pictures of the clip at '
+                        'once; any other PNG still goes through Pillow); the same planes and the same bitstream either way')
+
+
+def check_png_reader(p, a):
+    """an argparse error for --png_reader device where -i is not a picture folder"""
+    import os
+    from aivc_amd import png
+    try:
+        png.check_reader(a.png_reader, a.i, os.path.isdir(a.i))
+    except ValueError as e:
+        p.error(str(e))
+
+
 def check_input_range(a):
     """a raw video file as -i: exit status 2 with the file's range for --start_frame / --end_frame outside it, before a device is
     looked for (like a partial decode's request outside the stream)"""
@@ -100,6 +119,7 @@ def parse_args(argv=None):
                    help='write the sidecar manifest <bitstream>.md5: the arithmetic contract and one MD5 per reconstructed plane, '
                         'computed on the device (decode.py --verify checks a decode against it); the bitstream does not change')
     add_pix_fmt_flag(p)
+    add_png_reader_flag(p)
     add_contract_flag(p, ('fp32', 'fp32w'))
     add_rate_flags(p)
     add_scene_flag(p)
@@ -107,6 +127,7 @@ def parse_args(argv=None):
     a = p.parse_args(argv)
     a.idx_rate = check_rate_flags(p, a)
     check_scene_flag(p, a)
+    check_png_reader(p, a)
     from aivc_amd.resize import check_resize_flags
     a.resample = check_resize_flags(p, a, ('--size',))
     return a
@@ -125,7 +146,7 @@ def main(argv=None):
                        'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
                        'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp,
                        'rate_step': a.rate_step, 'digests': a.digests, 'scene_cut': a.scene_cut, 'size': a.size,
-                       'resample': a.resample, 'pix_fmt': a.pix_fmt})
+                       'resample': a.resample, 'pix_fmt': a.pix_fmt, 'png_reader': a.png_reader})
 
 
 if __name__ == '__main__':

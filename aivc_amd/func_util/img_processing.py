@@ -1,7 +1,7 @@
 """Image helpers with the reference's names (src/func_util/img_processing.py).
 
-PNG decoding is file I/O and stays Pillow on the host, and so does PNG encoding unless a caller asks for coder='device'
-(aivc_amd/png.py: the same pixels, coded on the device); colour conversion and chroma resampling run on the device
+PNG decoding and encoding are Pillow's on the host unless a caller asks for reader='device' / coder='device' (aivc_amd/png.py:
+the same pixels, inflated or coded on the device); colour conversion and chroma resampling run on the device
 (ops.rgb8_to_yuv420u8 / ops.yuv8_to_rgb8, include/aivc_hip_color.h), bit for bit what Pillow computes for the reference.
 
 The loaders return what the reference returns -- float tensors in [0, 1], value k / 255 for the 8-bit level k -- but on the
@@ -72,9 +72,12 @@ def load_frames(param):
     """{'frame_0': {'y','u','v'}, 'frame_1': ...} from the folder <sequence_path> (src/func_util/img_processing.py:78-176):
     <idx>_{y,u,v}.png ('old'), <folder name>_<idx, 5 digits>_{y,u,v}.png ('clic'), or one RGB <name>.png per frame (rgb).
     nb_frame_to_load frames from idx_starting_frame on; the last nb_pad_frame of them are not read but repeat the last frame
-    that was.  Every plane is a [1, 1, h, w] float tensor on param['device'] (default 'cuda')."""
+    that was.  Every plane is a [1, 1, h, w] float tensor on param['device'] (default 'cuda').
+    png_reader: 'pillow' (the default) -- one Image.open per picture on the host; 'device' -- the clip's pictures are read by ONE
+    aivc_amd.png.read_pictures call (y, u and v together as grey pictures; RGB pictures, then one colour launch per picture size),
+    the same planes.  png_stats: a dict that call counts into ('device', 'pillow')."""
     default = {'sequence_path': None, 'idx_starting_frame': 0, 'nb_frame_to_load': 3, 'nb_pad_frame': 0, 'rgb': False,
-               'loading_mode': 'old', 'device': 'cuda'}
+               'loading_mode': 'old', 'device': 'cuda', 'png_reader': 'pillow', 'png_stats': None}
     sequence_path = get_value('sequence_path', param, default)
     first = get_value('idx_starting_frame', param, default)
     nb = get_value('nb_frame_to_load', param, default)
@@ -85,6 +88,12 @@ def load_frames(param):
     if not sequence_path.endswith('/'):
         sequence_path += '/'
     last_loaded = first + nb - nb_pad - 1
+    from .. import png
+    if png.check_reader(get_value('png_reader', param, default)) == 'device':
+        idx = [min(first + gop_idx, last_loaded) for gop_idx in range(nb)]
+        read = _load_on_device({i: _frame_storage_name(sequence_path, i, loading_mode) for i in sorted(set(idx))}, rgb, device,
+                               get_value('png_stats', param, default))
+        return {'frame_' + str(gop_idx): _from_u8(read[i], 4) for gop_idx, i in enumerate(idx)}
     frames = {}
     for gop_idx in range(nb):
         name = _frame_storage_name(sequence_path, min(first + gop_idx, last_loaded), loading_mode)
@@ -93,6 +102,23 @@ def load_frames(param):
         else:
             frames['frame_' + str(gop_idx)] = _with_batch_dim(load_YUV_as_dic_tensor(name, device))
     return frames
+
+
+def _load_on_device(names, rgb, device, stats=None):
+    """{frame index: storage name} -> {frame index: uint8 planes {'y','u','v'} of [1, h, w]}: one read_pictures call for the clip"""
+    from .. import png
+    order = list(names)
+    if not rgb:
+        pics = png.read_pictures([names[i] + '_' + k + '.png' for i in order for k in 'yuv'], device, 'L', stats)
+        return {i: {k: pics[3 * n + j].view(1, *pics[3 * n + j].shape[:2]) for j, k in enumerate('yuv')} for n, i in enumerate(order)}
+    pics = png.read_pictures([names[i] + '.png' for i in order], device, 'RGB', stats)
+    out = {}
+    for shape in sorted({tuple(p.shape) for p in pics}):  # (a clip has one size: one colour launch)
+        group = [n for n, p in enumerate(pics) if tuple(p.shape) == shape]
+        y, u, v = ops.rgb8_to_yuv420u8(torch.stack([pics[n] for n in group]))
+        for j, n in enumerate(group):
+            out[order[n]] = {'y': y[j:j + 1], 'u': u[j:j + 1], 'v': v[j:j + 1]}
+    return out
 
 
 def _with_batch_dim(x):
@@ -121,10 +147,14 @@ def _from_u8(planes, ndim):
     return out
 
 
-def load_RGB_as_YUV420_dic(path_img, device='cuda'):
+def load_RGB_as_YUV420_dic(path_img, device='cuda', reader='pillow'):
     """<path_img>.png, an RGB picture -> {'y': [1,1,h,w], 'u','v': [1,1,h//2,w//2]} (src/func_util/img_processing.py:179-196):
     Pillow's 8-bit RGB -> YCbCr, chroma sample (2i, 2j) kept (nearest, scale 0.5), on the device.  A PNG of another mode
-    (palette, grey, alpha) is first brought to 8-bit RGB by Pillow, as part of decoding the file."""
+    (palette, grey, alpha) is first brought to 8-bit RGB by Pillow, as part of decoding the file.  reader 'device': the file is
+    inflated on the device (aivc_amd.png.read_pictures), the same planes."""
+    from .. import png
+    if png.check_reader(reader) == 'device':
+        return _from_u8(_load_on_device({0: path_img}, True, device)[0], 4)
     from PIL import Image
     img = Image.open(path_img + '.png')
     if img.mode != 'RGB':
@@ -134,9 +164,12 @@ def load_RGB_as_YUV420_dic(path_img, device='cuda'):
     return _from_u8({'y': y, 'u': u, 'v': v}, 4)
 
 
-def load_YUV_as_dic_tensor(path_img, device='cuda'):
+def load_YUV_as_dic_tensor(path_img, device='cuda', reader='pillow'):
     """<path_img>_{y,u,v}.png, 8-bit grey pictures -> {'y','u','v'} of 3-D tensors [1, h, w], no batch dimension
-    (src/func_util/img_processing.py:199-218)."""
+    (src/func_util/img_processing.py:199-218).  reader 'device': inflated on the device, the same planes."""
+    from .. import png
+    if png.check_reader(reader) == 'device':
+        return _from_u8(_load_on_device({0: path_img}, False, device)[0], 3)
     from PIL import Image
     planes = {}
     for k in ('y', 'u', 'v'):

@@ -806,6 +806,101 @@ def png_encode(pix, filter=5):
     return streams
 
 
+def _byte_pieces(stream):
+    """a stream given as one bytes-like object or as a list of them (a PNG's IDAT payloads) -> [flat uint8 arrays]"""
+    parts = stream if isinstance(stream, (list, tuple)) else (stream,)
+    return [np.frombuffer(p, np.uint8) for p in parts]
+
+
+def inflate_launch(streams, sizes, device, gap=0):
+    """inflate() without the wait: -> ([the output of each stream: uint8 views into dst], info: int32 CUDA tensor [n, 4], dst).
+    gap: bytes left untouched in front of every destination range and behind the last (tests)."""
+    n = len(streams)
+    sizes = [int(s) for s in sizes]
+    if len(sizes) != n or n < 1:
+        raise ValueError('inflate: %d streams, %d sizes (at least one stream)' % (n, len(sizes)))
+    pieces = [_byte_pieces(s) for s in streams]
+    src_n = [sum(p.size for p in ps) for ps in pieces]
+    for i in range(n):
+        if not (0 <= sizes[i] < 1 << 31 and src_n[i] < 1 << 31):
+            raise ValueError('inflate: stream %d: %d bytes to %d bytes, the kernel takes less than 2^31' % (i, src_n[i], sizes[i]))
+    device = torch.device(device)
+    dst_off = np.cumsum([gap] + [s + gap for s in sizes])
+    dst = torch.empty(max(int(dst_off[-1]), 1), dtype=torch.uint8, device=device)
+    # one blob: the table, then every piece of every stream back to back -- a stream starts at whatever byte it falls on
+    flat = [p for ps in pieces for p in ps]
+    offs, _ = _stage_layout([32 * n] + [p.size for p in flat], 1)
+    table = np.zeros((n, 4), np.uint64)
+    table[:, 0] = np.cumsum([offs[1] if flat else 32 * n] + src_n)[:-1]
+    table[:, 1], table[:, 2], table[:, 3] = src_n, dst_off[:-1], sizes
+    blob, _ = _stage(device, [table.reshape(-1).view(np.uint8)] + flat, 1)
+    info = torch.empty((n, 4), dtype=torch.int32, device=device)
+    _hbm_profiled('inflate', sum(src_n) + sum(sizes),
+                  lambda: call('aivc_inflate', _p(blob), _p(blob), n, max(src_n), max(sizes), _p(dst), _p(info), _stream()))
+    return [dst[int(o):int(o) + s] for o, s in zip(dst_off[:-1], sizes)], info, dst
+
+
+def inflate(streams, sizes, device, check=True, gap=0):
+    """zlib streams -> their bytes on the device, all in ONE launch, a workgroup per stream (include/aivc_hip_png_read.h).
+    streams: the n streams on the host, each a bytes-like object or a list of them that are taken back to back (the IDAT payloads of
+    a PNG); sizes: the bytes each inflates to, EXACTLY.  One pinned staging buffer, one host-to-device copy, one copy of the status
+    rows back.  -> a list of n uint8 CUDA tensors, views into one buffer where they lie back to back.  A stream that fails raises
+    ValueError naming the first such stream and its status in words; with check=False nothing is raised and the call returns
+    (the tensors, the status rows as a uint32 array [n, 4]: status, bytes produced, source bytes consumed, 0; the buffer)."""
+    outs, info, dst = inflate_launch(streams, sizes, device, gap)
+    rows = info.cpu().numpy().view(np.uint32)  # (synchronises)
+    if not check:
+        return outs, rows, dst
+    for i in np.flatnonzero(rows[:, 0]):
+        raise ValueError('inflate: stream %d: %s' % (i, abi.INFLATE_STATUS.get(int(rows[i, 0]), 'status %d' % rows[i, 0])))
+    return outs
+
+
+def png_unfilter_launch(filt, shapes):
+    """png_unfilter() without the wait: -> ([pictures: uint8 views [h, w, c]], status: int32 CUDA tensor [n])"""
+    from . import png
+    shapes = [png.check_size(*s) for s in shapes]
+    keep = [_dev(t, torch.uint8, 'filt[%d]' % i).reshape(-1) for i, t in enumerate(filt)]
+    n = len(keep)
+    if n < 1 or len(shapes) != n:
+        raise ValueError('png_unfilter: %d filtered streams, %d shapes (at least one picture)' % (n, len(shapes)))
+    need = [h * (1 + w * c) for h, w, c in shapes]
+    for i in range(n):
+        if keep[i].numel() != need[i] or need[i] >= 1 << 31:
+            raise ValueError('png_unfilter: picture %d: %d filtered bytes for %d x %d x %d (w x h x c), expected %d, less than 2^31'
+                             % (i, keep[i].numel(), shapes[i][1], shapes[i][0], shapes[i][2], need[i]))
+    device = keep[0].device
+    base = min(t.data_ptr() for t in keep)
+    pix_off = np.cumsum([0] + [h * w * c for h, w, c in shapes])
+    table = np.zeros((n, 4), np.uint64)
+    table[:, 0] = [t.data_ptr() - base for t in keep]
+    table[:, 1] = pix_off[:-1]
+    table[:, 2] = [(h << 32) | w for h, w, _ in shapes]
+    table[:, 3] = [c for _, _, c in shapes]
+    blob, _ = _stage(device, [table.reshape(-1).view(np.uint8)])
+    pix = torch.empty(int(pix_off[-1]), dtype=torch.uint8, device=device)
+    status = torch.empty((n,), dtype=torch.int32, device=device)
+    _hbm_profiled('png_unfilter', sum(need) + int(pix_off[-1]),
+                  lambda: call('aivc_png_unfilter', base, _p(blob), n, max(need), _p(pix), _p(status), _stream()))
+    del keep
+    return [pix[int(o):int(o) + h * w * c].view(h, w, c) for o, (h, w, c) in zip(pix_off[:-1], shapes)], status
+
+
+def png_unfilter(filt, shapes, check=True):
+    """The filtered streams of PNG pictures (what inflate() gives for their IDAT payloads) -> the pixels, all in ONE launch, a
+    wavefront per picture (include/aivc_hip_png_read.h).  filt: a list of n uint8 CUDA tensors on one device, any alignment;
+    shapes: [(h, w, c)], c = 1 (grey) or 3 (RGB); picture i has h (1 + w c) filtered bytes.  -> a list of uint8 CUDA tensors
+    [h, w, c], views into one buffer.  A filter type above 4 raises ValueError naming the picture; with check=False the call
+    returns (the pictures, the status words as a uint32 array [n])."""
+    pics, status = png_unfilter_launch(filt, shapes)
+    words = status.cpu().numpy().view(np.uint32)  # (synchronises)
+    if not check:
+        return pics, words
+    for i in np.flatnonzero(words):
+        raise ValueError('png_unfilter: picture %d: %s' % (i, abi.PNG_UNFILTER_STATUS.get(int(words[i]), 'status %d' % words[i])))
+    return pics
+
+
 def downsample2x(x, ch0, nch):
     """NHWC x -> planar [n, nch, h//2, w//2] 2x2 means of channels ch0..ch0+nch-1 (OutputLayer)."""
     x = _dev(x, torch.float32, 'x')

@@ -1,10 +1,15 @@
-"""PNG files of 8-bit grey and RGB pictures, coded on the device (include/aivc_hip_png.h: row filters, and a dynamic-Huffman
-deflate of independent segments of whole rows; aivc_amd.ops.png_encode).  What stays on the host is what needs every byte of a
-picture in order and costs next to nothing: the fold of the segments' Adler-32 sums, the container (signature, IHDR, one IDAT,
-IEND) and the CRC-32 of each chunk (zlib.crc32 over bytes that are on the host anyway, to be written).
+"""PNG files of 8-bit grey and RGB pictures, coded and read on the device.
+Writing (include/aivc_hip_png.h: row filters, and a dynamic-Huffman deflate of independent segments of whole rows;
+aivc_amd.ops.png_encode): what stays on the host is what needs every byte of a picture in order and costs next to nothing: the
+fold of the segments' Adler-32 sums, the container (signature, IHDR, one IDAT, IEND) and the CRC-32 of each chunk (zlib.crc32
+over bytes that are on the host anyway, to be written).
+Reading (include/aivc_hip_png_read.h: a zlib inflate and the inverse of the row filters; read_pictures): one PNG is one serial
+inflate stream, but a clip is hundreds of independent ones, so every stream of a batch gets a workgroup of its own.  The host
+walks the chunks and checks their CRC-32 (parse: the bytes are on the host anyway, to be uploaded).
 
-Out of scope: reading PNGs on the device (a PNG is one serial inflate stream per picture), PNG triplets as decoder output,
-16-bit samples, palette, alpha, Adam7 and general LZ77 matching."""
+Out of scope: PNG triplets as decoder output, general LZ77 matching in the writer; on the device, pictures with 16-bit or
+sub-byte samples, a palette, alpha or Adam7 interlace (the reader hands those to Pillow), one stream split over several
+workgroups -- the sync-flush boundaries of this project's own files included -- and a CRC-32."""
 import struct
 import zlib
 
@@ -13,6 +18,7 @@ ADLER_MOD = 65521
 SIGNATURE = b'\x89PNG\r\n\x1a\n'
 FILTERS = (0, 1, 2, 3, 4, 5)  # None, Sub, Up, Average, Paeth; 5: per row, the smallest sum of absolute residuals
 CODERS = ('pillow', 'device')
+READERS = ('pillow', 'device')
 
 
 def check_size(h, w, c):
@@ -102,3 +108,135 @@ def write_pictures(pix, paths, filter=5):
     for path, z in zip(paths, ops.png_encode(pix, filter)):
         with open(path, 'wb') as f:
             f.write(assemble(w, h, c, z))
+
+
+# ---- reading -----------------------------------------------------------------------------------------------------------------------
+class PngError(ValueError):
+    """a file that is no PNG, or a broken one; the message names what is wrong"""
+
+
+class Unsupported(Exception):
+    """a valid PNG of a kind the device does not read: palette, alpha, 16-bit or sub-byte samples, Adam7"""
+
+
+def check_reader(reader, in_path=None, is_folder=None):
+    """-> reader; a ValueError for an unknown one, or for 'device' where the input (in_path given) is not a picture folder"""
+    if reader not in READERS:
+        raise ValueError('png reader %r: expected one of %s' % (reader, ', '.join(READERS)))
+    if reader == 'device' and in_path is not None and not is_folder:
+        raise ValueError('--png_reader device reads the pictures of a folder: -i %s is not a directory' % (in_path,))
+    return reader
+
+
+def parse(data):
+    """the bytes of a PNG file -> (w, h, c, [(offset, length) of every IDAT payload in data, in order]) for an 8-bit grey (c = 1)
+    or 8-bit RGB (c = 3) picture without interlace.  The chunk headers are walked, the CRC-32 of IHDR and of every IDAT is
+    checked, ancillary chunks are skipped.  Unsupported: a valid PNG of another kind.  PngError: a broken file."""
+    data = memoryview(data)
+    if bytes(data[:8]) != SIGNATURE:
+        raise PngError('not a PNG file: wrong signature')
+    at, idats, head, ended = 8, [], None, False
+    while at < len(data):
+        if at + 8 > len(data):
+            raise PngError('truncated chunk header at byte %d' % at)
+        n, = struct.unpack('>I', data[at:at + 4])
+        kind = bytes(data[at + 4:at + 8])
+        if at + 12 + n > len(data):
+            raise PngError('truncated %s chunk at byte %d: %d bytes stated, %d left' % (kind.decode('latin-1'), at, n, len(data) - at - 12))
+        if head is None and kind != b'IHDR':
+            raise PngError('the first chunk is %s, not IHDR' % kind.decode('latin-1'))
+        if kind in (b'IHDR', b'IDAT'):
+            crc, = struct.unpack('>I', data[at + 8 + n:at + 12 + n])
+            if zlib.crc32(data[at + 4:at + 8 + n]) & 0xffffffff != crc:
+                raise PngError('CRC-32 mismatch in the %s chunk at byte %d' % (kind.decode('latin-1'), at))
+        if kind == b'IHDR':
+            if head is not None or n != 13:
+                raise PngError('a second IHDR chunk, or one of %d bytes' % n)
+            head = struct.unpack('>IIBBBBB', data[at + 8:at + 21])
+        elif kind == b'IDAT':
+            idats.append((at + 8, n))
+        elif kind == b'IEND':
+            ended = True
+            break
+        at += 12 + n
+    if head is None:
+        raise PngError('no IHDR chunk')
+    if not ended:
+        raise PngError('no IEND chunk')
+    if not idats:
+        raise PngError('no IDAT chunk')
+    w, h, depth, colour, compression, filter_method, interlace = head
+    if w < 1 or h < 1 or colour not in (0, 2, 3, 4, 6) or depth not in (1, 2, 4, 8, 16) or compression or filter_method or interlace > 1:
+        raise PngError('IHDR: %d x %d, depth %d, colour type %d, compression %d, filter %d, interlace %d'
+                       % (w, h, depth, colour, compression, filter_method, interlace))
+    if depth != 8 or colour not in (0, 2) or interlace:
+        raise Unsupported('depth %d, colour type %d, interlace %d: the device reads 8-bit grey and RGB without interlace' % (depth, colour, interlace))
+    return w, h, 1 if colour == 0 else 3, idats
+
+
+def _pillow_picture(path, mode, device):
+    import numpy as np
+    import torch
+    from PIL import Image
+    img = Image.open(path)
+    if img.mode != mode:
+        img = img.convert(mode)
+    a = np.asarray(img)
+    return torch.from_numpy(a.copy()).to(device).view(a.shape[0], a.shape[1], -1)
+
+
+def read_pictures(paths, device, mode, stats=None):
+    """The PNG files `paths` -> a list of uint8 tensors [h, w, c] on `device`, c = 1 for mode 'L' and 3 for 'RGB': the pixels Pillow
+    reads.  The 8-bit files of that mode are inflated and unfiltered on the device: their IDAT payloads go through one pinned
+    staging buffer in batches of at most rawvideo.BATCH_BYTES (of filtered bytes), each batch one inflate launch, one unfilter
+    launch and one copy back of the status words.  Every other file -- Unsupported, or of another colour type -- is read by Pillow
+    with the conversion the loaders of func_util.img_processing apply, and takes its place in the list.  A broken file, or a
+    stream the device refuses, raises PngError with the file's name.  stats: a dict whose 'device' and 'pillow' counts grow."""
+    import numpy as np
+    import torch
+    from . import abi, ops, rawvideo
+    if mode not in ('L', 'RGB'):
+        raise ValueError('read_pictures: mode %r, expected L or RGB' % (mode,))
+    paths = list(paths)
+    out, jobs = [None] * len(paths), []
+    for i, path in enumerate(paths):
+        with open(path, 'rb') as f:
+            data = f.read()
+        try:
+            w, h, c, idats = parse(data)
+        except Unsupported:
+            c = None
+        except PngError as e:
+            raise PngError('%s: %s' % (path, e))
+        if c != (1 if mode == 'L' else 3):
+            out[i] = _pillow_picture(path, mode, device)
+        else:
+            view = memoryview(data)
+            jobs.append((i, (h, w, c), [view[o:o + n] for o, n in idats]))
+    at = 0
+    while at < len(jobs):
+        end, total = at, 0
+        while end < len(jobs) and (end == at or total + _filtered_bytes(jobs[end][1]) <= rawvideo.BATCH_BYTES):
+            total += _filtered_bytes(jobs[end][1])
+            end += 1
+        batch = jobs[at:end]
+        shapes = [s for _, s, _ in batch]
+        filt, info, _ = ops.inflate_launch([p for _, _, p in batch], [_filtered_bytes(s) for s in shapes], device)
+        pics, status = ops.png_unfilter_launch(filt, shapes)
+        words = torch.cat([info[:, 0], status]).cpu().numpy().view(np.uint32)  # (synchronises: the one copy back)
+        for k, (i, _, _) in enumerate(batch):
+            if words[k]:
+                raise PngError('%s: inflate: %s' % (paths[i], abi.INFLATE_STATUS.get(int(words[k]), 'status %d' % words[k])))
+            if words[len(batch) + k]:
+                raise PngError('%s: %s' % (paths[i], abi.PNG_UNFILTER_STATUS.get(int(words[len(batch) + k]), 'status %d' % words[len(batch) + k])))
+            out[i] = pics[k]
+        at = end
+    if stats is not None:
+        stats['device'] = stats.get('device', 0) + len(jobs)
+        stats['pillow'] = stats.get('pillow', 0) + len(paths) - len(jobs)
+    return out
+
+
+def _filtered_bytes(shape):
+    h, w, c = shape
+    return h * (1 + w * c)

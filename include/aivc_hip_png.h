@@ -5,8 +5,8 @@
  * What it is for: writing the RGB pictures of a decode (aivc_amd/png.py, decode.py --png_coder device) without one host core
  * running zlib per picture.  The device produces, per picture, the bytes of a complete zlib stream but for its last four -- the
  * Adler-32, which the host folds from per-segment partial sums -- and the host wraps them into the container: signature, IHDR,
- * one IDAT, IEND, the CRC-32 of each chunk (aivc_amd/png.py: assemble).  Out of scope: reading PNGs, 16-bit samples, palette,
- * alpha, Adam7, general LZ77 matching.
+ * one IDAT, IEND, the CRC-32 of each chunk (aivc_amd/png.py: assemble).  Reading PNGs is aivc_hip_png_read.h.  Out of scope:
+ * 16-bit samples, palette, alpha, Adam7, general LZ77 matching.
  *
  * THE FILTERED STREAM.  pix [n][h][w][c] uint8, c = 1 (grey) or 3 (RGB).  With rb = w c, row r of a picture becomes the 1 + rb
  * bytes `type, x[0] - pred(0), ..., x[rb - 1] - pred(rb - 1)` (mod 256), where a = x[i - c] (0 for i < c), b = the byte above

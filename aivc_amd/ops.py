@@ -57,6 +57,36 @@ def _dev(t, dtype=None, name='tensor'):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _shaped(t, dtype, shape, name='tensor'):
+    """_dev of a tensor of this dtype and EXACTLY this shape (None on an axis: any size; t None stays None).  The kernels see an
+    address and the integers of the call: what the two say about each other is checked here, from the tensor's attributes alone."""
+    if t is None:
+        return None
+    t = _dev(t, dtype, name)
+    if t.shape != shape and (t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape))):
+        raise ValueError('aivc_amd.ops: %s has shape %s, expected [%s]'
+                         % (name, tuple(t.shape), ', '.join('any' if s is None else str(int(s)) for s in shape)))
+    return t
+
+
+def _out(t, dtype, shape, name, device=None, at_least=False):
+    """a caller's output, which the kernel writes in place: nothing can be converted or copied for it, so it IS a contiguous
+    tensor of this dtype on this device (None: any GPU), of exactly this shape or (at_least) of at least shape[0] rows of it -> t"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or (device is not None and t.device != device):
+        raise AivcNativeError('aivc_amd.ops: %s is %s; an output is a CUDA tensor on %s'
+                              % (name, 'on %s' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, device or 'the GPU'))
+    if t.dtype != dtype:
+        raise AivcNativeError('aivc_amd.ops: %s has dtype %s, expected %s' % (name, t.dtype, dtype))
+    if not t.is_contiguous():
+        raise ValueError('aivc_amd.ops: %s is not contiguous (a copy would lose the result)' % name)
+    ok = t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(int(s) for s in shape[1:]) \
+        and (t.shape[0] >= shape[0] if at_least else t.shape[0] == shape[0])
+    if not ok:
+        raise ValueError('aivc_amd.ops: %s has shape %s, expected %s%s' % (name, tuple(t.shape), 'at least ' if at_least else '',
+                                                                         tuple(int(s) for s in shape)))
+    return t
+
+
 def _p(t):
     return None if t is None else t.data_ptr()
 
@@ -77,6 +107,8 @@ def pad_channels(x, c_out):
     c_in = x.shape[-1]
     if c_in == c_out:
         return x
+    if c_out < c_in:
+        raise ValueError('pad_channels: %d channels cannot be padded to %d' % (c_in, c_out))
     out = torch.empty(x.shape[:-1] + (c_out,), dtype=torch.float32, device=x.device)
     call('aivc_pad_channels', _p(x), x.numel() // c_in, c_in, _p(out), c_out, _stream())
     return out
@@ -250,6 +282,28 @@ def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, ac
         st = ImageStack([x], x.shape[1], x.shape[2], x.device)  # a single float image (the prediction fed to g_a_ref)
         st._packed = x
         x = st
+    # every tensor against the integers of the launch, before the first kernel of the call (packing, padding, a first half)
+    if not isinstance(x, ImageStack):
+        x = _shaped(x, torch.float32, (None,) * 4, 'x')
+    n, h, w_, c = x.shape
+    w_ohwi = _shaped(w_ohwi, torch.float32, (None,) * 4, 'weight')
+    co, k, k2, cw = w_ohwi.shape
+    if k2 != k:
+        raise ValueError('conv2d: a %d x %d kernel; the kernels are square' % (k, k2))
+    if cw != (c + 3) // 4 * 4:
+        raise AivcNativeError('conv2d: weight packed for %d stored channels, input has %d' % (cw, (c + 3) // 4 * 4))
+    co2, w3, b3 = 0, None, None
+    if tail is not None:
+        w3 = _shaped(tail[0], torch.float32, (None, 1, 1, (co + 3) // 4 * 4), 'tail weight')
+        co2 = w3.shape[0]
+        b3 = _shaped(tail[1], torch.float32, (co2,), 'tail bias')
+        tail = (w3, b3)
+    ho, wo = abi.conv_out_size(mode, h, w_, k, stride, pad)
+    bias = _shaped(bias, torch.float32, (co,), 'bias')
+    mul = _shaped(mul, torch.float32, (n, ho, wo, co2 or co), 'mul')
+    res = _shaped(res, torch.float32, (n, ho, wo, co2 or co), 'res')
+    if gdn is not None:  # (the fused epilogue reads them as they lie: contiguous fp32 on the device, like every other operand)
+        gdn = (_shaped(gdn[0], torch.float32, (co,), 'gdn beta'), _shaped(gdn[1], torch.float32, (co, co), 'gdn gamma'), gdn[2])
     if isinstance(x, ImageStack):
         y = None
         if tail is None and mode == abi.MODE_CONV:
@@ -257,13 +311,8 @@ def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, ac
         if y is not None:
             return y
         x = x.tensor()
-    x = _dev(x, torch.float32, 'x')
-    n, h, w_, c = x.shape
     if tail is not None:
-        w_ohwi, w3 = _dev(w_ohwi, torch.float32, 'weight'), _dev(tail[0], torch.float32, 'tail weight')
-        co, k, _, cw = w_ohwi.shape
-        co2 = w3.shape[0]
-        if not (c % 4 == 0 and cw == c and tuple(w3.shape) == (co2, 1, 1, co) and bias is not None and tail[1] is not None):
+        if not (c % 4 == 0 and co % 4 == 0 and bias is not None and b3 is not None):
             return _two_launches(x, w_ohwi, bias, mode, stride, pad, act1, act2, mul, res, algo, gdn, tail, frame_h)
         c_real, flags = c, 0  # (a tail launch counts stored channels)
     else:
@@ -272,28 +321,15 @@ def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, ac
         if c % 4:
             x = pad_channels(x, (c + 3) // 4 * 4)
             c = x.shape[-1]
-        w_ohwi = _dev(w_ohwi, torch.float32, 'weight')
-        co, k, _, cw = w_ohwi.shape
-        co2 = 0
-        if cw != c:
-            raise AivcNativeError('conv2d: weight packed for %d stored channels, input has %d' % (cw, c))
         # 3-channel images stored as 4: the zero pad channels are exact no-ops the MFMA kernels may skip
         flags = abi.CONV_SPARSE4 if cmap is not None and all(ci % 4 != 3 for ci in cmap) else 0
         if WINO_ANY_SIZE:
             flags |= abi.CONV_WINO_ANY_SIZE
-    ho, wo = abi.conv_out_size(mode, h, w_, k, stride, pad)
     y = torch.empty((n, ho, wo, co2 or co), dtype=torch.float32, device=x.device)
-    bias = _dev(bias, torch.float32, 'bias')
-    mul = _dev(mul, torch.float32, 'mul')
-    res = _dev(res, torch.float32, 'res')
-    for t, nm in ((mul, 'mul'), (res, 'res')):
-        if t is not None and tuple(t.shape) != tuple(y.shape):
-            raise AivcNativeError('conv2d: %s shape %s != output shape %s' % (nm, tuple(t.shape), tuple(y.shape)))
     g_beta, g_gamma, gflag = (None, None, 0) if gdn is None else (gdn[0], gdn[1], 2 if gdn[2] else 1)
     p = abi.ConvParams(mode, k, stride, pad, n, h, w_, c, ho, wo, co, act1, act2, algo, gflag, flags,
                        _p(x), _p(w_ohwi), _p(bias), _p(mul), _p(res), _p(y), _p(g_beta), _p(g_gamma))
     if co2:
-        b3 = _dev(tail[1], torch.float32, 'tail bias')
         p.tail_w, p.tail_bias, p.tail_c_out = _p(w3), _p(b3), co2
     p.precision = PRECISION
     if frame_h is not None and PRECISION == abi.PREC_FP32_WINO:
@@ -316,9 +352,9 @@ def conv2d(x, w_ohwi, bias=None, mode=abi.MODE_CONV, stride=1, pad=0, act1=0, ac
 
 
 def gdn_reparam(beta, gamma, beta_bound, gamma_bound, pedestal):
-    beta = _dev(beta.detach(), torch.float32, 'beta')
-    gamma = _dev(gamma.detach(), torch.float32, 'gamma')
+    beta = _shaped(beta.detach(), torch.float32, (None,), 'beta')
     c = beta.shape[0]
+    gamma = _shaped(gamma.detach(), torch.float32, (c, c), 'gamma')
     be = torch.empty_like(beta)
     ge = torch.empty_like(gamma)
     call('aivc_gdn_reparam', _p(beta), _p(gamma), c, float(beta_bound), float(gamma_bound),
@@ -339,6 +375,8 @@ def diag_hold_lds(lds_bytes, iterations, out=None):
     (aivc_diag_hold_lds, a diagnostic for the tests and tools of the persistent kernels) -> the 64 chain ends, int32"""
     if out is None:
         out = torch.empty(64, dtype=torch.int32, device=torch.device('cuda'))
+    else:
+        _out(out, torch.int32, (64,), 'out')
     call('aivc_diag_hold_lds', int(lds_bytes), int(iterations), _p(out), _stream())
     return out
 
@@ -358,6 +396,7 @@ def detmath_eval(fn, a, b=None):
 def gdn(x, beta_eff, gamma_eff, inverse=False, res=None, algo=abi.ALGO_AUTO, frame_h=None):
     c = x.shape[-1]
     mode = abi.MODE_IGDN if inverse else abi.MODE_GDN
+    beta_eff, gamma_eff = _shaped(beta_eff, torch.float32, (c,), 'beta'), _shaped(gamma_eff, torch.float32, (c, c), 'gamma')
     if c % 4 == 0:
         return conv2d(x, gamma_eff.reshape(c, 1, 1, c), beta_eff, mode=mode, res=res, algo=algo, frame_h=frame_h)
     # channel counts that are not a multiple of 4 (never the case in a real model): run on a zero
@@ -376,8 +415,13 @@ def yuv420_to_444(y, u, v, c_store=4, c_off=0, out=None):
     """planes [n,h,w] / [n,ceil(h/2),ceil(w/2)] (fp32 levels or uint8) -> NHWC [n,h,w,c_store]"""
     u8 = y.dtype == torch.uint8
     dt = torch.uint8 if u8 else torch.float32
-    y, u, v = _dev(y, dt, 'y'), _dev(u, dt, 'u'), _dev(v, dt, 'v')
+    y = _shaped(y, dt, (None,) * 3, 'y')
     n, h, w = y.shape
+    u, v = (_shaped(t, dt, (n, (h + 1) // 2, (w + 1) // 2), nm) for t, nm in ((u, 'u'), (v, 'v')))
+    if out is not None:
+        _out(out, torch.float32, (n, h, w, c_store), 'out', y.device)
+    if not 0 <= c_off <= c_store - 3:
+        raise ValueError('yuv420_to_444: channels %d .. %d of %d stored ones' % (c_off, c_off + 2, c_store))
     if out is None:
         # the kernel writes channels c_off .. c_off + 2 (+ the zero pad channel): nothing else to clear when that is all
         full = c_off == 0 and c_store <= 4
@@ -399,20 +443,27 @@ def _n_frames(parts):
     return next(p['y'].shape[0] if isinstance(p, dict) else p.shape[0] for p in parts if p is not None)
 
 
-def _image_sources(parts):
-    """up to 3 image sources (plane dicts, float NHWC tensors, None) -> (frames per image, ImageSrc array, tensors to keep alive)"""
+def _image_sources(parts, h, w):
+    """up to 3 image sources of h x w pixels (plane dicts, float NHWC tensors, None)
+    -> (frames per image, ImageSrc array, tensors to keep alive)"""
+    if not 1 <= len(parts) <= abi.MAX_IMAGES or all(p is None for p in parts):
+        raise ValueError('image sources: %d of them (1 ... %d, not all absent)' % (len(parts), abi.MAX_IMAGES))
+    n = _n_frames(parts)
     arr = (abi.ImageSrc * abi.MAX_IMAGES)()
     keep = []
     for i, p in enumerate(parts):
         if isinstance(p, dict):
-            y, u, v = (_dev(p[k], torch.uint8, k) for k in 'yuv')
+            y = _shaped(p['y'], torch.uint8, (n, h, w), 'y')
+            u, v = (_shaped(p[k], torch.uint8, (n, (h + 1) // 2, (w + 1) // 2), k) for k in 'uv')
             keep += [y, u, v]
             arr[i].y, arr[i].u, arr[i].v = y.data_ptr(), u.data_ptr(), v.data_ptr()
         elif p is not None:
-            f = _dev(p, torch.float32, 'image')
+            f = _shaped(p, torch.float32, (n, h, w, None), 'image')
+            if f.shape[-1] < 3:
+                raise ValueError('image sources: a float image of %d channels, at least 3' % f.shape[-1])
             keep.append(f)
             arr[i].f, arr[i].f_channels = f.data_ptr(), f.shape[-1]
-    return _n_frames(parts), arr, keep
+    return n, arr, keep
 
 
 class ImageStack:
@@ -431,7 +482,7 @@ class ImageStack:
 
     def sources(self):
         """(ImageSrc array, tensors to keep alive)"""
-        return _image_sources(self.parts)[1:]
+        return _image_sources(self.parts, self.h, self.w)[1:]
 
     def tensor(self):
         if self._packed is None:
@@ -469,7 +520,7 @@ def pack_images(parts, h, w, device):
     """parts: up to 3 sources, each a dict of uint8 planes {'y','u','v'} ([n,h,w] / [n,ceil(h/2),ceil(w/2)]), a
     float NHWC tensor [n,h,w,c>=3] (its first 3 channels are taken) or None (zeros) -> NHWC [n,h,w,4*len(parts)]
     with every image stored as (c0, c1, c2, 0); carries the stored position of the real channels for the conv."""
-    n, arr, keep = _image_sources(parts)
+    n, arr, keep = _image_sources(parts, h, w)
     out = torch.empty((n, h, w, 4 * len(parts)), dtype=torch.float32, device=device)
     nb = n * h * w * (16 * len(parts) + sum(1.5 if isinstance(p, dict) else (12 if p is not None else 0) for p in parts))
     _hbm_profiled('pack_images', nb, lambda: call('aivc_pack_images', arr, len(parts), n, h, w, _p(out), _stream()))
@@ -478,9 +529,13 @@ def pack_images(parts, h, w, device):
 
 
 def frame_to_yuv420(x, h, w, skip=None, want_float=True, want_u8=True):
-    x = _dev(x, torch.float32, 'x')
-    skip = _dev(skip, torch.float32, 'skip')
+    x = _shaped(x, torch.float32, (None,) * 4, 'x')
     n, hx, wx, cx = x.shape
+    if not (0 <= h <= hx and 0 <= w <= wx and cx >= 3):
+        raise ValueError('frame_to_yuv420: a frame of %d x %d (w x h) from x %s (at least that size, 3 channels)' % (w, h, tuple(x.shape)))
+    skip = _shaped(skip, torch.float32, (n, h, w, None), 'skip')
+    if skip is not None and skip.shape[-1] < 3:
+        raise ValueError('frame_to_yuv420: skip has %d channels, at least 3' % skip.shape[-1])
     hc, wc = (h + 1) // 2, (w + 1) // 2
     dev = x.device
     f = [None] * 3
@@ -903,8 +958,10 @@ def png_unfilter(filt, shapes, check=True):
 
 def downsample2x(x, ch0, nch):
     """NHWC x -> planar [n, nch, h//2, w//2] 2x2 means of channels ch0..ch0+nch-1 (OutputLayer)."""
-    x = _dev(x, torch.float32, 'x')
+    x = _shaped(x, torch.float32, (None,) * 4, 'x')
     n, h, w, c = x.shape
+    if ch0 < 0 or nch < 0 or ch0 + nch > c:
+        raise ValueError('downsample2x: channels %d .. %d of %d' % (ch0, ch0 + nch - 1, c))
     out = torch.empty((n, nch, h // 2, w // 2), dtype=torch.float32, device=x.device)
     call('aivc_downsample2x', _p(x), n, h, w, c, ch0, nch, _p(out), _stream())
     return out
@@ -920,14 +977,13 @@ def warp(x, flow, interp='bilinear', pad='border', align_corners=True):
     of 4 channels (other channel counts are zero padded for the call)."""
     if interp not in WARP_INTERP or pad not in WARP_PAD:
         raise ValueError('warp: interp %r / pad %r: expected one of %s and one of %s' % (interp, pad, sorted(WARP_INTERP), sorted(WARP_PAD)))
-    x, flow = _dev(x, torch.float32, 'x'), _dev(flow, torch.float32, 'flow')
+    x = _shaped(x, torch.float32, (None,) * 4, 'x')
     n, h, w, c = x.shape
+    flow = _shaped(flow, torch.float32, (n, h, w, 2), 'flow')
     if interp == 'bilinear' and pad == 'border' and align_corners:
         out = torch.empty_like(x)
         call('aivc_warp', _p(x), _p(flow), n, h, w, c, _p(out), _stream())
         return out
-    if tuple(flow.shape) != (n, h, w, 2):
-        raise ValueError('warp: flow %s does not go with x %s' % (tuple(flow.shape), tuple(x.shape)))
     c4 = (c + 3) // 4 * 4
     x = pad_channels(x, c4)
     out = torch.empty_like(x)
@@ -941,10 +997,15 @@ def warp(x, flow, interp='bilinear', pad='border', align_corners=True):
 def warp_blend(mof, prev, nxt, h, w, frame_type, co=4, want_aux=False, rows=None):
     """rows = (row0, n_rows): only that band of the frame -- mof is then the band of the MOFNet output (its row 0 =
     frame row row0), prev / nxt stay whole frames, the outputs are [n, n_rows, w, co] (aivc_warp_blend_rows)."""
-    mof, prev, nxt = (_dev(t, torch.float32, nm) for t, nm in ((mof, 'mof'), (prev, 'prev'), (nxt, 'next')))
+    mof = _shaped(mof, torch.float32, (None,) * 4, 'mof')
     n, hm, wm, cm = mof.shape
+    prev = _shaped(prev, torch.float32, (n, h, w, None), 'prev')
+    nxt = _shaped(nxt, torch.float32, (n, h, w, prev.shape[-1]), 'next')
     dev = mof.device
     row0, nr = (0, h) if rows is None else rows
+    if not (0 <= row0 and 0 <= nr <= hm and row0 + nr <= h and w <= wm and cm >= 6 and prev.shape[-1] >= 3 and co >= 3):
+        raise ValueError('warp_blend: rows %d .. %d of a %d x %d frame (w x h), %d reference channels, %d output channels from a '
+                         'MOFNet band %s' % (row0, row0 + nr - 1, w, h, prev.shape[-1], co, tuple(mof.shape)))
     pred = torch.empty((n, nr, w, co), dtype=torch.float32, device=dev)
     skip = torch.empty_like(pred)
     xw = alpha = beta = None
@@ -963,19 +1024,28 @@ def warp_blend(mof, prev, nxt, h, w, frame_type, co=4, want_aux=False, rows=None
 
 
 def hyper_params(hs, c, h, w):
-    hs = _dev(hs, torch.float32, 'hs')
+    hs = _shaped(hs, torch.float32, (None,) * 4, 'hs')
     n, hh, wh, c2 = hs.shape
     if c2 != 2 * c:
         raise AivcNativeError('hyper_params: expected %d channels, got %d' % (2 * c, c2))
+    if not (0 <= h <= hh and 0 <= w <= wh):
+        raise ValueError('hyper_params: a crop of %d x %d (w x h) from a map of %d x %d' % (w, h, wh, hh))
     mu = torch.empty((n, h, w, c), dtype=torch.float32, device=hs.device)
     sigma = torch.empty_like(mu)
     call('aivc_hyper_params', _p(hs), n, hh, wh, c, h, w, _p(mu), _p(sigma), _stream())
     return mu, sigma
 
 
+def _gain_vector(gain, t):
+    """one gain per channel of t [..., c] (any shape of c elements; None stays None)"""
+    if t.dim() < 1:
+        raise ValueError('aivc_amd.ops: a tensor [..., c], got a scalar')
+    return None if gain is None else _shaped(gain.detach().reshape(-1), torch.float32, (t.shape[-1],), 'gain')
+
+
 def channel_gain(x, gain):
     x = _dev(x, torch.float32, 'x')
-    gain = None if gain is None else _dev(gain.detach().reshape(-1), torch.float32, 'gain')
+    gain = _gain_vector(gain, x)
     out = torch.empty_like(x)
     call('aivc_channel_gain', _p(x), _p(gain), x.numel() // x.shape[-1], x.shape[-1], _p(out), _stream())
     return out
@@ -983,7 +1053,7 @@ def channel_gain(x, gain):
 
 def gain_interp(g_r, g_t, lam):
     g_r = _dev(g_r.detach().reshape(-1), torch.float32, 'g_r')
-    g_t = _dev(g_t.detach().reshape(-1), torch.float32, 'g_t')
+    g_t = _shaped(g_t.detach().reshape(-1), torch.float32, (g_r.numel(),), 'g_t')
     out = torch.empty_like(g_r)
     call('aivc_gain_interp', _p(g_r), _p(g_t), g_r.numel(), float(lam), _p(out), _stream())
     return out
@@ -991,8 +1061,8 @@ def gain_interp(g_r, g_t, lam):
 
 def quantize_center(y, mu=None, gain_dec=None, want_yhat=True):
     y = _dev(y, torch.float32, 'y')
-    mu = _dev(mu, torch.float32, 'mu')
-    gain_dec = None if gain_dec is None else _dev(gain_dec.detach().reshape(-1), torch.float32, 'gain')
+    mu = _shaped(mu, torch.float32, y.shape, 'mu')
+    gain_dec = _gain_vector(gain_dec, y)
     q = torch.empty(y.shape, dtype=torch.int16, device=y.device)
     y_hat = torch.empty_like(y) if want_yhat else None
     call('aivc_quantize_center', _p(y), _p(mu), _p(gain_dec), y.numel() // y.shape[-1], y.shape[-1],
@@ -1002,8 +1072,8 @@ def quantize_center(y, mu=None, gain_dec=None, want_yhat=True):
 
 def dequantize(q, mu=None, gain_dec=None):
     q = _dev(q, torch.int16, 'q')
-    mu = _dev(mu, torch.float32, 'mu')
-    gain_dec = None if gain_dec is None else _dev(gain_dec.detach().reshape(-1), torch.float32, 'gain')
+    mu = _shaped(mu, torch.float32, q.shape, 'mu')
+    gain_dec = _gain_vector(gain_dec, q)
     out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
     call('aivc_dequantize', _p(q), _p(mu), _p(gain_dec), q.numel() // q.shape[-1], q.shape[-1], _p(out),
          _stream())
@@ -1039,7 +1109,7 @@ def channel_gain_rows(x, gains):
 
 def quantize_center_rows(y, mu, gains_dec, want_yhat=True, want_q=True):
     y = _dev(y, torch.float32, 'y')
-    mu = _dev(mu, torch.float32, 'mu')
+    mu = _shaped(mu, torch.float32, y.shape, 'mu')
     n, npix, c = _rows_dims(y)
     gains_dec = _gain_rows(gains_dec, n, c)
     q = torch.empty(y.shape, dtype=torch.int16, device=y.device) if want_q else None
@@ -1050,7 +1120,7 @@ def quantize_center_rows(y, mu, gains_dec, want_yhat=True, want_q=True):
 
 def dequantize_rows(q, mu, gains_dec):
     q = _dev(q, torch.int16, 'q')
-    mu = _dev(mu, torch.float32, 'mu')
+    mu = _shaped(mu, torch.float32, q.shape, 'mu')
     n, npix, c = _rows_dims(q)
     gains_dec = _gain_rows(gains_dec, n, c)
     out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
@@ -1060,7 +1130,7 @@ def dequantize_rows(q, mu, gains_dec):
 
 # entropy model ---------------------------------------------------------------------------------
 def balle_cdf_table(params, want_float=False):
-    params = _dev(params, torch.float32, 'params')
+    params = _shaped(params, torch.float32, (None, abi.BALLE_PARAMS), 'params')
     c = params.shape[0]
     table = torch.empty((c, abi.CDF_ROW), dtype=torch.int16, device=params.device)  # uint16 payload
     cdf = torch.empty((c, abi.LP), dtype=torch.float32, device=params.device) if want_float else None
@@ -1079,16 +1149,34 @@ def nonzero_flags(q):
     return flags
 
 
+def _one_image(sigma, maps, name='sigma'):
+    """sigma [1,h,w,c] (one image) and the coded channels of it -> (sigma, npix, c, aivc_map_list)"""
+    sigma = _shaped(sigma, torch.float32, (1, None, None, None), name)
+    c = sigma.shape[-1]
+    _check_maps(maps, c)
+    return sigma, sigma.numel() // c if c else 0, c, abi.MapList.make(maps)
+
+
+def _check_maps(maps, c):
+    if any(not 0 <= int(m) < c for m in maps):
+        raise ValueError('aivc_amd.ops: coded maps %s of a latent of %d channels' % (list(maps), c))
+
+
+def _row_range(row_off, n_rows):
+    if row_off < 0:
+        raise ValueError('aivc_amd.ops: row_off %d' % row_off)
+    return row_off + n_rows
+
+
 def laplace_cdf_rows(sigma, maps, out=None, row_off=0):
     """sigma [1,h,w,c] (one image) -> rows [(len(maps)*npix), CDF_ROW]; with `out` given the rows are
     written starting at row `row_off` of that (larger) tensor."""
-    sigma = _dev(sigma, torch.float32, 'sigma')
-    c = sigma.shape[-1]
-    npix = sigma.numel() // c
-    ml = abi.MapList.make(maps)
+    sigma, npix, c, ml = _one_image(sigma, maps)
     if out is None:
         out = torch.empty((len(maps) * npix, abi.CDF_ROW), dtype=torch.int16, device=sigma.device)
         row_off = 0
+    else:
+        _out(out, torch.int16, (_row_range(row_off, len(maps) * npix), abi.CDF_ROW), 'out', sigma.device, at_least=True)
     # fp64-VALU bound, not HBM bound: 514 expm1 evaluations per coded position; the profile counts CDF POINTS
     _hbm_profiled('cdf_points:laplace_cdf_rows', len(maps) * npix * abi.LP,
                   lambda: call('aivc_laplace_cdf_rows', _p(sigma), npix, c, C.byref(ml),
@@ -1099,14 +1187,14 @@ def laplace_cdf_rows(sigma, maps, out=None, row_off=0):
 def laplace_cdf_windows(sigma, maps, out=None, row_off=0):
     """Like laplace_cdf_rows, restricted to the decoder's fast-path window: -> (win [n_pos, CDF_WIN] int16,
     sigma_pos [n_pos] float32); with `out` = (win, sigma_pos) given, written from position `row_off` on."""
-    sigma = _dev(sigma, torch.float32, 'sigma')
-    c = sigma.shape[-1]
-    npix = sigma.numel() // c
-    ml = abi.MapList.make(maps)
+    sigma, npix, c, ml = _one_image(sigma, maps)
     if out is None:
         out = (torch.empty((len(maps) * npix, abi.CDF_WIN), dtype=torch.int16, device=sigma.device),
                torch.empty(len(maps) * npix, dtype=torch.float32, device=sigma.device))
         row_off = 0
+    else:
+        _out(out[0], torch.int16, (_row_range(row_off, len(maps) * npix), abi.CDF_WIN), 'out[0]', sigma.device, at_least=True)
+        _out(out[1], torch.float32, (row_off + len(maps) * npix,), 'out[1]', sigma.device, at_least=True)
     win, sp = out
     _hbm_profiled('cdf_points:laplace_cdf_windows', len(maps) * npix * abi.CDF_WIN,
                   lambda: call('aivc_laplace_cdf_windows', _p(sigma), npix, c, C.byref(ml),
@@ -1129,8 +1217,11 @@ def laplace_cdf_windows_batch(sigma, maps_list, out, table=None):
     n, npix, c = _rows_dims(sigma)
     table = table or frame_maps_to_device(maps_list, npix, sigma.device)
     dev, offs, total = table
+    for m in maps_list:
+        _check_maps(m, c)
     win, sp = out
-    assert win.shape[0] >= total and sp.shape[0] >= total
+    _out(win, torch.int16, (total, abi.CDF_WIN), 'out[0]', sigma.device, at_least=True)
+    _out(sp, torch.float32, (total,), 'out[1]', sigma.device, at_least=True)
     mx = max((len(m) for m in maps_list), default=0)
     if total:
         _hbm_profiled('cdf_points:laplace_cdf_windows', total * abi.CDF_WIN,
@@ -1140,8 +1231,11 @@ def laplace_cdf_windows_batch(sigma, maps_list, out, table=None):
 
 def laplace_bounds_batch(sigma, q, maps_list):
     """-> (bounds int32 [total], [pos_off per frame]) of a frame batch in one launch"""
-    sigma, q = _dev(sigma, torch.float32, 'sigma'), _dev(q, torch.int16, 'q')
+    sigma = _dev(sigma, torch.float32, 'sigma')
+    q = _shaped(q, torch.int16, sigma.shape, 'q')
     n, npix, c = _rows_dims(sigma)
+    for m in maps_list:
+        _check_maps(m, c)
     dev, offs, total = frame_maps_to_device(maps_list, npix, sigma.device)
     bounds = torch.empty(max(total, 1), dtype=torch.int32, device=sigma.device)
     mx = max((len(m) for m in maps_list), default=0)
@@ -1154,13 +1248,27 @@ def table_bounds_batch(table, q):
     """q [n,h,w,c] -> bounds int32 [n, c * npix] (every channel of every frame, pmf mode) in one launch"""
     q = _dev(q, torch.int16, 'q')
     n, npix, c = _rows_dims(q)
+    table = _shaped(table, torch.int16, (c, abi.CDF_ROW), 'table')
     bounds = torch.empty((n, c * npix), dtype=torch.int32, device=q.device)
     call('aivc_table_bounds_batch', _p(table), _p(q), n, npix, c, _p(bounds), _stream())
     return bounds
 
 
+def _symbols(sym, total):
+    """decoded symbols in stream order: an int16 CUDA vector of at least `total` of them"""
+    sym = _shaped(sym, torch.int16, (None,), 'sym')
+    if sym.shape[0] < total:
+        raise ValueError('aivc_amd.ops: %d symbols, the maps hold %d' % (sym.shape[0], total))
+    return sym
+
+
 def scatter_symbols_batch(sym, maps_list, n, npix, c, table=None):
     """sym: the decoded symbols of the batch in stream order (frame f's at its pos_off) -> q int16 [n, npix, c]"""
+    sym = _symbols(sym, sum(len(m) for m in maps_list) * npix)
+    for m in maps_list:
+        _check_maps(m, c)
+    if len(maps_list) != n:
+        raise ValueError('scatter_symbols_batch: %d map lists for %d frames' % (len(maps_list), n))
     dev_ = sym.device
     table = table or frame_maps_to_device(maps_list, npix, dev_)
     q = torch.empty((n, npix, c), dtype=torch.int16, device=dev_)
@@ -1172,10 +1280,8 @@ def laplace_bounds(sigma, q, maps):
     """sigma / q [1,h,w,c] (one image) -> bounds int32 [len(maps) * npix]: aivc_laplace_bounds, the one-frame case of the
     batch kernel with the map list passed by value.  Nothing under aivc_amd/ calls it (the codec goes through
     laplace_bounds_batch); the tests, the oracle comparisons and tools/bench_rangecoder.py do."""
-    sigma, q = _dev(sigma, torch.float32, 'sigma'), _dev(q, torch.int16, 'q')
-    c = sigma.shape[-1]
-    npix = sigma.numel() // c
-    ml = abi.MapList.make(maps)
+    sigma, npix, c, ml = _one_image(sigma, maps)
+    q = _shaped(q, torch.int16, sigma.shape, 'q')
     bounds = torch.empty(len(maps) * npix, dtype=torch.int32, device=sigma.device)
     call('aivc_laplace_bounds', _p(sigma), _p(q), npix, c, C.byref(ml), _p(bounds), _stream())
     return bounds
@@ -1185,9 +1291,10 @@ def table_bounds(table, q):
     """q [1,h,w,c] (one image) -> bounds int32 [c * npix]: aivc_table_bounds = aivc_table_bounds_batch with n = 1.
     Nothing under aivc_amd/ calls it (the codec goes through table_bounds_batch); the tests, the oracle comparisons and
     tools/bench_rangecoder.py do."""
-    q = _dev(q, torch.int16, 'q')
+    q = _shaped(q, torch.int16, (1, None, None, None), 'q')
     c = q.shape[-1]
-    npix = q.numel() // c
+    npix = q.numel() // c if c else 0
+    table = _shaped(table, torch.int16, (c, abi.CDF_ROW), 'table')
     bounds = torch.empty(c * npix, dtype=torch.int32, device=q.device)
     call('aivc_table_bounds', _p(table), _p(q), npix, c, _p(bounds), _stream())
     return bounds
@@ -1203,6 +1310,8 @@ def bounds_rate(bounds, out=None):
     """packed CDF bounds (laplace_bounds / table_bounds) -> device fp64 [1]: the bits the range coder pays for them
     (sum of -log2((c_hi - c_lo) / 2^16), fixed summation order).  No sync.  out: a 1-element fp64 view to fill."""
     bounds = _dev(bounds, torch.int32, 'bounds')
+    if out is not None:
+        _out(out, torch.float64, (1,), 'out', bounds.device)
     lanes, out = _rate_scratch(bounds.device, out)
     call('aivc_bounds_rate', _p(bounds), bounds.numel(), _p(lanes), _p(out), _stream())
     return out
@@ -1260,6 +1369,11 @@ def range_encode(bounds_list, streams=None):
     streams: optional HIP streams; the launches (a kernel lasts as long as its longest stream) then
     run concurrently on them, forked from / joined back into the current stream with events."""
     n = len(bounds_list)
+    for i, b in enumerate(bounds_list):  # (looked at as they are: a view into a packed tensor stays that view)
+        if not b.is_cuda or b.dtype != torch.int32 or b.dim() != 1 or b.device != bounds_list[0].device:
+            raise AivcNativeError('aivc_amd.ops: bounds_list[%d] is %s %s on %s; a stream is an int32 CUDA vector'
+                                  % (i, b.dtype, tuple(b.shape), b.device))
+    bounds_list = [b if b.is_contiguous() else b.contiguous() for b in bounds_list]
     dev = bounds_list[0].device
     # views that already sit back to back in one tensor (the batched bounds kernels) need no concatenation
     base = bounds_list[0]._base if bounds_list[0]._base is not None else bounds_list[0]
@@ -1314,6 +1428,15 @@ def range_decode(payloads, rows, row_offs, n_syms, planes, sigma_pos=None, want_
     Returns a list of int16 CUDA tensors (uint16 payload: symbols 0..512); with want_bits also an int32 CUDA tensor [n]
     of the bits each stream consumed (include/aivc_hip.h: len(payload) == (bits + 2 + 7) // 8 for an intact stream)."""
     n = len(payloads)
+    if not len(row_offs) == len(n_syms) == len(planes) == n:
+        raise ValueError('range_decode: %d payloads, %d row offsets, %d symbol counts, %d planes' % (n, len(row_offs), len(n_syms), len(planes)))
+    rows = _shaped(rows, torch.int16, (None, abi.CDF_ROW if sigma_pos is None else abi.CDF_WIN), 'rows')
+    sigma_pos = _shaped(sigma_pos, torch.float32, (rows.shape[0],), 'sigma_pos')
+    for i in range(n):  # the rows stream i reads: one per symbol, or one per `plane` symbols
+        used = n_syms[i] if planes[i] == 0 else -(-n_syms[i] // planes[i])
+        if row_offs[i] < 0 or n_syms[i] < 0 or planes[i] < 0 or row_offs[i] + used > rows.shape[0] or (planes[i] and sigma_pos is not None):
+            raise ValueError('range_decode: stream %d reads rows %d .. %d of %d (plane %d)'
+                             % (i, row_offs[i], row_offs[i] + used - 1, rows.shape[0], planes[i]))
     dev = rows.device
     # the decoder kernels read past a payload's end by design: every payload is padded to 4 bytes and followed by 8 spare ones,
     # zeros everywhere outside the payloads, at least 4 bytes in all
@@ -1340,7 +1463,9 @@ def range_decode(payloads, rows, row_offs, n_syms, planes, sigma_pos=None, want_
 
 
 def scatter_symbols(sym, npix, c, maps):
+    _check_maps(maps, c)
     ml = abi.MapList.make(maps)
+    sym = None if sym is None else _symbols(sym, len(maps) * npix)
     dev = sym.device if sym is not None else torch.device('cuda')
     q = torch.empty((npix, c), dtype=torch.int16, device=dev)
     call('aivc_scatter_symbols', _p(sym), npix, c, C.byref(ml), _p(q), _stream())
@@ -1356,7 +1481,8 @@ def _metrics_ws(n, h, w, dev):
 def ssim_means(a, b, win, c1, c2):
     """a, b: float64 CUDA planes [n,h,w]; win: 1-D normalised window (host sequence, len <= 11).
     -> float64 CUDA tensor [n, 2]: (mean SSIM, mean contrast-structure) of one scale."""
-    a, b = _dev(a, torch.float64, 'a'), _dev(b, torch.float64, 'b')
+    a = _shaped(a, torch.float64, (None,) * 3, 'a')
+    b = _shaped(b, torch.float64, a.shape, 'b')
     n, h, w = a.shape
     wn = np.ascontiguousarray(np.asarray(win, np.float64))
     out = torch.empty((n, 2), dtype=torch.float64, device=a.device)
@@ -1368,7 +1494,7 @@ def ssim_means(a, b, win, c1, c2):
 def pool2x2(x, edge):
     """float64 planes [n,h,w] -> [n, ceil(h/2), ceil(w/2)] 2x2 means; edge 0: mirror past the end without
     repeating the border (torch ReflectionPad2d), 1: repeat it (scipy 'reflect')."""
-    x = _dev(x, torch.float64, 'x')
+    x = _shaped(x, torch.float64, (None,) * 3, 'x')
     n, h, w = x.shape
     out = torch.empty((n, (h + 1) // 2, (w + 1) // 2), dtype=torch.float64, device=x.device)
     call('aivc_pool2x2', _p(x), n, h, w, int(edge), _p(out), _stream())
@@ -1377,7 +1503,8 @@ def pool2x2(x, edge):
 
 def sq_err(a, b):
     """-> float64 CUDA tensor [1]: sum of squared differences of two float64 tensors of equal size"""
-    a, b = _dev(a, torch.float64, 'a'), _dev(b, torch.float64, 'b')
+    a = _dev(a, torch.float64, 'a')
+    b = _shaped(b, torch.float64, a.shape, 'b')
     out = torch.empty(1, dtype=torch.float64, device=a.device)
     ws = _metrics_ws(1, 16, 16, a.device)
     call('aivc_sq_err', _p(a), _p(b), a.numel(), _p(ws), _p(out), _stream())

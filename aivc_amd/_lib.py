@@ -34,6 +34,7 @@ def load():
         fns.update(abi.declare_rawvideo(_lib))
         fns.update(abi.declare_png(_lib))
         fns.update(abi.declare_png_read(_lib))
+        fns.update(abi.declare_color_matrix(_lib))
     except (OSError, AttributeError) as e:
         raise AivcNativeError('aivc_amd: cannot load %s: %s' % (LIB_PATH, e))
     err = _lib.aivc_last_error

@@ -1,6 +1,7 @@
 """ctypes mirror of include/aivc_hip.h, include/aivc_hip_warp.h, include/aivc_hip_color.h, include/aivc_hip_quality.h,
 include/aivc_hip_rates.h, include/aivc_hip_digest.h, include/aivc_hip_scene.h, include/aivc_hip_resize.h,
-include/aivc_hip_rawvideo.h, include/aivc_hip_png.h and include/aivc_hip_png_read.h (struct layouts, constants, prototypes).
+include/aivc_hip_rawvideo.h, include/aivc_hip_png.h, include/aivc_hip_png_read.h and include/aivc_hip_color_matrix.h (struct
+layouts, constants, prototypes).
 
 The same prototypes are bound twice: on libaivc_hip.so (device pointers, product path) by
 aivc_amd/_lib.py, and -- with the ``_ref`` suffix, host pointers -- on the CPU oracle by
@@ -315,6 +316,32 @@ def declare_png_read(lib):
     reason declare_rawvideo states; raises AttributeError when the library does not export one of them."""
     fns = {}
     for name, args in PNG_READ_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = list(args) + [C.c_void_p]
+        fn.restype = C.c_int
+        fns[name] = fn
+    return fns
+
+
+# include/aivc_hip_color_matrix.h: device only (their statement is numpy: aivc_amd/color.py, tests/test_gpu_colour_matrix.py)
+COLOR_MATRIX_SHIFT, COLOR_MATRIX_MAX_COEF = 14, 65536  # AIVC_COLOR_MATRIX_SHIFT, AIVC_COLOR_MATRIX_MAX_COEF
+
+
+class ColorMatrix(C.Structure):
+    _fields_ = [('fwd', (C.c_int32 * 3) * 3), ('fwd_off', C.c_int32 * 3), ('inv', C.c_int32 * 5), ('inv_yoff', C.c_int32)]
+
+
+COLOR_MATRIX_PROTOTYPES = {
+    'aivc_rgb8_to_yuv420u8_matrix': [_f, _i32, _i32, _i32, _P(ColorMatrix), _i32, _f, _f, _f],
+    'aivc_yuv8_to_rgb8_matrix': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _P(ColorMatrix), _f],
+}
+
+
+def declare_color_matrix(lib):
+    """Attach argtypes/restype for the entries of include/aivc_hip_color_matrix.h (device library only), beside declare() for the
+    reason declare_rawvideo states; raises AttributeError when the library does not export one of them."""
+    fns = {}
+    for name, args in COLOR_MATRIX_PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.argtypes = list(args) + [C.c_void_p]
         fn.restype = C.c_int

@@ -50,6 +50,8 @@ def parse_args(argv=None):
     enc_cli.add_png_reader_flag(p)
     dec_cli.add_out_format_flags(p)
     dec_cli.add_png_coder_flag(p)
+    from aivc_amd.color import add_colour_flags, check_colour_flags
+    add_colour_flags(p)
     from aivc_amd.resize import add_resize_flags, check_resize_flags
     add_resize_flags(p, {'--size': enc_cli.SIZE_HELP, '--out_size': dec_cli.OUT_SIZE_HELP})
     a = p.parse_args(argv)
@@ -60,6 +62,7 @@ def parse_args(argv=None):
     dec_cli.check_out_size(p, a, a.o)
     dec_cli.check_out_format(p, a, a.o)
     dec_cli.check_png_coder(p, a, a.o)
+    check_colour_flags(p, a, in_path=a.i, out_path=a.o, out_is_folder=dec_cli.is_png_folder(a.o))  # (both halves are told)
     return a
 
 
@@ -78,6 +81,7 @@ def main(argv=None):
     a = parse_args(argv)
     gop = gop_name(a.coding_config, a.gop_size, a.intra_period)
     common = ['--model', a.model] + (['--cpu'] if a.cpu else [])
+    colour = ['--matrix', a.colour.matrix, '--range', a.colour.range] if a.colour is not None else []
     import os
     banner = print if int(os.environ.get('RANK', '0')) == 0 else (lambda *x: None)  # one voice in a multi-rank job
     banner(('*' * 80).center(120))
@@ -91,6 +95,7 @@ def main(argv=None):
                  + (['--scene_cut', repr(a.scene_cut)] if a.scene_cut is not None else [])
                  + (['--pix_fmt', a.pix_fmt] if a.pix_fmt is not None else [])
                  + (['--png_reader', a.png_reader] if a.png_reader != 'pillow' else [])
+                 + colour + (['--chroma_down', a.chroma_down] if a.chroma_down != 'point' else [])
                  + (['--size', size_text(a.size), '--resample', a.resample] if a.size is not None else [])
                  + (['--contract', a.contract] if a.contract not in (None, 'auto') else []))  # (auto is the decoder's choice)
     banner(('*' * 80).center(120))
@@ -101,7 +106,7 @@ def main(argv=None):
                           + (['--out_size', size_text(a.out_size), '--resample', a.resample] if a.out_size is not None else [])
                           + (['--out_pix_fmt', a.out_pix_fmt] if a.out_pix_fmt != 'yuv420p' else [])
                           + (['--fps', '%d:%d' % a.fps] if a.fps != (25, 1) else [])
-                          + (['--png_coder', a.png_coder] if a.png_coder != 'pillow' else [])
+                          + (['--png_coder', a.png_coder] if a.png_coder != 'pillow' else []) + colour
                           + (['--contract', a.contract] if a.contract else []))
     from aivc_amd import parallel
     if parallel.rank_world()[0] != 0:  # multi-rank job: rank 0 evaluates

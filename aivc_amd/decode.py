@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""decode.py CLI (flags of src/decode.py:24-40)."""
+"""decode.py CLI (flags of src/decode.py:24-40).  -o dir/ writes RGB pictures: Pillow's YCbCr -> RGB (BT.601, full range) unless
+--matrix / --range say what the planes carry; the stream stores no colour description."""
 import argparse
 
 from aivc_amd.cli_common import add_contract_flag, contract_scope, get_model, resolve_device
@@ -74,11 +75,14 @@ def parse_args(argv=None):
                         '0 the I frame, 1 the P frame; 1_GOP_32 has levels 0 ... 6, each one less halves the frame count)')
     add_out_format_flags(p)
     add_png_coder_flag(p)
+    from aivc_amd.color import add_colour_flags, check_colour_flags
+    add_colour_flags(p, encoder=False)
     from aivc_amd.resize import add_resize_flags, check_resize_flags
     add_resize_flags(p, {'--out_size': OUT_SIZE_HELP})
     a = p.parse_args(argv)
     check_out_format(p, a, a.o)
     check_png_coder(p, a, a.o)
+    check_colour_flags(p, a, out_path=a.o, out_is_folder=is_png_folder(a.o))
     if a.max_level is not None and a.max_level < 0:
         p.error('--max_level %d: temporal levels count from 0' % a.max_level)
     a.resample = check_resize_flags(p, a, ('--out_size',))
@@ -113,7 +117,7 @@ def main(argv=None):
             decode_one_video({'decoder': dec, 'bitstream_path': a.i, 'device': str(dev), 'out_file': out, 'verify': a.verify,
                               'contract': 'auto' if a.contract == 'auto' else '', 'frames': a.frames, 'max_level': a.max_level,
                               'out_size': a.out_size, 'resample': a.resample, 'out_pix_fmt': a.out_pix_fmt, 'fps': a.fps,
-                              'png_coder': a.png_coder})
+                              'png_coder': a.png_coder, 'colour': a.colour})
     except ContainerError as e:  # a truncated / damaged file: say so and stop (exit status 2), no frames are written
         print('[ERROR] %s is not a complete bitstream: %s' % (a.i, e))
         raise SystemExit(2)

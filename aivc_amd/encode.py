@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """encode.py CLI (flags of src/encode.py:27-66).  python -m aivc_amd.encode -i clip_WxH_fps_420.yuv ...
--i may also name a .y4m file, a headerless file in another layout (--pix_fmt, or _422 / _444 / _10b ... tokens in its name), or a folder of the reference's pictures: PNG triplets (<idx>_{y,u,v}.png, or the CLIC layout) or <idx>.png RGB."""
+-i may also name a .y4m file, a headerless file in another layout (--pix_fmt, or _422 / _444 / _10b ... tokens in its name), or a folder of the reference's pictures: PNG triplets (<idx>_{y,u,v}.png, or the CLIC layout) or <idx>.png RGB.
+RGB pictures become planes by Pillow's arithmetic (BT.601, full range) unless --matrix / --range say what the planes are to carry."""
 import argparse
 
 from aivc_amd.cli_common import add_contract_flag, contract_scope, get_model, resolve_device
@@ -120,6 +121,8 @@ def parse_args(argv=None):
                         'computed on the device (decode.py --verify checks a decode against it); the bitstream does not change')
     add_pix_fmt_flag(p)
     add_png_reader_flag(p)
+    from aivc_amd.color import add_colour_flags, check_colour_flags
+    add_colour_flags(p, decoder=False)
     add_contract_flag(p, ('fp32', 'fp32w'))
     add_rate_flags(p)
     add_scene_flag(p)
@@ -128,6 +131,7 @@ def parse_args(argv=None):
     a.idx_rate = check_rate_flags(p, a)
     check_scene_flag(p, a)
     check_png_reader(p, a)
+    check_colour_flags(p, a, in_path=a.i)
     from aivc_amd.resize import check_resize_flags
     a.resample = check_resize_flags(p, a, ('--size',))
     return a
@@ -146,7 +150,8 @@ def main(argv=None):
                        'GOP_struct_name': a.gop, 'idx_rate': a.idx_rate, 'final_file': a.o, 'idx_starting_frame': a.start_frame,
                        'idx_end_frame': a.end_frame, 'working_dir': a.log_dir, 'target_bpp': a.target_bpp,
                        'rate_step': a.rate_step, 'digests': a.digests, 'scene_cut': a.scene_cut, 'size': a.size,
-                       'resample': a.resample, 'pix_fmt': a.pix_fmt, 'png_reader': a.png_reader})
+                       'resample': a.resample, 'pix_fmt': a.pix_fmt, 'png_reader': a.png_reader, 'colour': a.colour,
+                       'chroma_down': a.chroma_down})
 
 
 if __name__ == '__main__':

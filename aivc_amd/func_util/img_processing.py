@@ -3,6 +3,9 @@
 PNG decoding and encoding are Pillow's on the host unless a caller asks for reader='device' / coder='device' (aivc_amd/png.py:
 the same pixels, inflated or coded on the device); colour conversion and chroma resampling run on the device
 (ops.rgb8_to_yuv420u8 / ops.yuv8_to_rgb8, include/aivc_hip_color.h), bit for bit what Pillow computes for the reference.
+Pillow's arithmetic is BT.601, full range; a caller who names what the planes carry (`colour`, an aivc_amd.color.ColourSpec:
+BT.601 / 709 / 2020, full or limited range) gets that conversion instead (aivc_amd/color.py), between the same PNG reading and
+coding.  colour None, the default everywhere, is Pillow's arithmetic through the calls above.
 
 The loaders return what the reference returns -- float tensors in [0, 1], value k / 255 for the 8-bit level k -- but on the
 device (`device` argument / param entry, default 'cuda'), and as a YuvDic: a dict that also carries the uint8 planes it was made
@@ -68,6 +71,25 @@ def _frame_storage_name(sequence_path, absolute_idx, loading_mode):
     raise ValueError('load_frames: loading_mode %r (expected old or clic)' % (loading_mode,))
 
 
+def _rgb_to_planes(rgb, colour=None, chroma_down='point'):
+    """uint8 RGB [n, h, w, 3] on the device -> (y, u, v): Pillow's arithmetic (colour None), or the named one"""
+    from .. import color
+    color.check_chroma_down(chroma_down)
+    if colour is None:
+        if chroma_down != 'point':
+            raise ValueError('chroma_down %r needs a colour: Pillow\'s conversion keeps the chroma of pixel (2i, 2j)' % (chroma_down,))
+        return ops.rgb8_to_yuv420u8(rgb)
+    return color.rgb_to_yuv420(rgb, colour, chroma_down)
+
+
+def _planes_to_rgb(y, u, v, chroma_shift, colour=None):
+    """uint8 planes on the device -> RGB [n, h, w, 3]: Pillow's arithmetic (colour None), or the named one"""
+    if colour is None:
+        return ops.yuv8_to_rgb8(y, u, v, chroma_shift=chroma_shift)
+    from .. import color
+    return color.yuv_to_rgb(y, u, v, colour, chroma_shift=chroma_shift)
+
+
 def load_frames(param):
     """{'frame_0': {'y','u','v'}, 'frame_1': ...} from the folder <sequence_path> (src/func_util/img_processing.py:78-176):
     <idx>_{y,u,v}.png ('old'), <folder name>_<idx, 5 digits>_{y,u,v}.png ('clic'), or one RGB <name>.png per frame (rgb).
@@ -75,9 +97,12 @@ def load_frames(param):
     that was.  Every plane is a [1, 1, h, w] float tensor on param['device'] (default 'cuda').
     png_reader: 'pillow' (the default) -- one Image.open per picture on the host; 'device' -- the clip's pictures are read by ONE
     aivc_amd.png.read_pictures call (y, u and v together as grey pictures; RGB pictures, then one colour launch per picture size),
-    the same planes.  png_stats: a dict that call counts into ('device', 'pillow')."""
+    the same planes.  png_stats: a dict that call counts into ('device', 'pillow').
+    colour: None (the default) -- RGB pictures become planes by Pillow's arithmetic; an aivc_amd.color.ColourSpec -- by that matrix
+    and range, chroma_down 'point' (the default: the chroma of pixel (2i, 2j)) or 'box' (of the 2 x 2 block, rounded once).  Both
+    apply to rgb folders only, after the pictures have been read by either reader."""
     default = {'sequence_path': None, 'idx_starting_frame': 0, 'nb_frame_to_load': 3, 'nb_pad_frame': 0, 'rgb': False,
-               'loading_mode': 'old', 'device': 'cuda', 'png_reader': 'pillow', 'png_stats': None}
+               'loading_mode': 'old', 'device': 'cuda', 'png_reader': 'pillow', 'png_stats': None, 'colour': None, 'chroma_down': 'point'}
     sequence_path = get_value('sequence_path', param, default)
     first = get_value('idx_starting_frame', param, default)
     nb = get_value('nb_frame_to_load', param, default)
@@ -85,6 +110,9 @@ def load_frames(param):
     rgb = get_value('rgb', param, default)
     loading_mode = get_value('loading_mode', param, default)
     device = get_value('device', param, default)
+    colour, chroma_down = get_value('colour', param, default), get_value('chroma_down', param, default)
+    if not rgb and (colour is not None or chroma_down != 'point'):
+        raise ValueError('load_frames: colour / chroma_down convert RGB pictures; %s holds planes' % sequence_path)
     if not sequence_path.endswith('/'):
         sequence_path += '/'
     last_loaded = first + nb - nb_pad - 1
@@ -92,19 +120,19 @@ def load_frames(param):
     if png.check_reader(get_value('png_reader', param, default)) == 'device':
         idx = [min(first + gop_idx, last_loaded) for gop_idx in range(nb)]
         read = _load_on_device({i: _frame_storage_name(sequence_path, i, loading_mode) for i in sorted(set(idx))}, rgb, device,
-                               get_value('png_stats', param, default))
+                               get_value('png_stats', param, default), colour, chroma_down)
         return {'frame_' + str(gop_idx): _from_u8(read[i], 4) for gop_idx, i in enumerate(idx)}
     frames = {}
     for gop_idx in range(nb):
         name = _frame_storage_name(sequence_path, min(first + gop_idx, last_loaded), loading_mode)
         if rgb:
-            frames['frame_' + str(gop_idx)] = load_RGB_as_YUV420_dic(name, device)
+            frames['frame_' + str(gop_idx)] = load_RGB_as_YUV420_dic(name, device, colour=colour, chroma_down=chroma_down)
         else:
             frames['frame_' + str(gop_idx)] = _with_batch_dim(load_YUV_as_dic_tensor(name, device))
     return frames
 
 
-def _load_on_device(names, rgb, device, stats=None):
+def _load_on_device(names, rgb, device, stats=None, colour=None, chroma_down='point'):
     """{frame index: storage name} -> {frame index: uint8 planes {'y','u','v'} of [1, h, w]}: one read_pictures call for the clip"""
     from .. import png
     order = list(names)
@@ -115,7 +143,7 @@ def _load_on_device(names, rgb, device, stats=None):
     out = {}
     for shape in sorted({tuple(p.shape) for p in pics}):  # (a clip has one size: one colour launch)
         group = [n for n, p in enumerate(pics) if tuple(p.shape) == shape]
-        y, u, v = ops.rgb8_to_yuv420u8(torch.stack([pics[n] for n in group]))
+        y, u, v = _rgb_to_planes(torch.stack([pics[n] for n in group]), colour, chroma_down)
         for j, n in enumerate(group):
             out[order[n]] = {'y': y[j:j + 1], 'u': u[j:j + 1], 'v': v[j:j + 1]}
     return out
@@ -147,20 +175,21 @@ def _from_u8(planes, ndim):
     return out
 
 
-def load_RGB_as_YUV420_dic(path_img, device='cuda', reader='pillow'):
+def load_RGB_as_YUV420_dic(path_img, device='cuda', reader='pillow', colour=None, chroma_down='point'):
     """<path_img>.png, an RGB picture -> {'y': [1,1,h,w], 'u','v': [1,1,h//2,w//2]} (src/func_util/img_processing.py:179-196):
     Pillow's 8-bit RGB -> YCbCr, chroma sample (2i, 2j) kept (nearest, scale 0.5), on the device.  A PNG of another mode
     (palette, grey, alpha) is first brought to 8-bit RGB by Pillow, as part of decoding the file.  reader 'device': the file is
-    inflated on the device (aivc_amd.png.read_pictures), the same planes."""
+    inflated on the device (aivc_amd.png.read_pictures), the same planes.  colour: an aivc_amd.color.ColourSpec -- that matrix
+    and range instead of Pillow's arithmetic, chroma_down 'point' or 'box' (aivc_amd/color.py); the planes keep their sizes."""
     from .. import png
     if png.check_reader(reader) == 'device':
-        return _from_u8(_load_on_device({0: path_img}, True, device)[0], 4)
+        return _from_u8(_load_on_device({0: path_img}, True, device, None, colour, chroma_down)[0], 4)
     from PIL import Image
     img = Image.open(path_img + '.png')
     if img.mode != 'RGB':
         img = img.convert('RGB')
     rgb = torch.from_numpy(np.asarray(img).copy()).to(device)
-    y, u, v = ops.rgb8_to_yuv420u8(rgb.view(1, *rgb.shape))
+    y, u, v = _rgb_to_planes(rgb.view(1, *rgb.shape), colour, chroma_down)
     return _from_u8({'y': y, 'u': u, 'v': v}, 4)
 
 
@@ -200,7 +229,7 @@ def _save_png(a, path_img, mode, coder='pillow'):
     Image.fromarray(np.ascontiguousarray(a.cpu().numpy()), mode).save(path_img)
 
 
-def save_tensor_as_img(x, path_img, mode='yuv420', coder='pillow'):
+def save_tensor_as_img(x, path_img, mode='yuv420', coder='pillow', colour=None):
     """src/func_util/img_processing.py:221-287.  x holds floats in [0, 1] (cast like to_pil_image: mul(255), truncated) or uint8
     levels, on the device.
       'yuv420'        x: dict, chroma at half resolution -> nearest x 2, cropped to the luma size, YCbCr -> RGB on the device
@@ -210,16 +239,20 @@ def save_tensor_as_img(x, path_img, mode='yuv420', coder='pillow'):
       'L'             x: [1,1,h,w] or [1,h,w] tensor
     Only batch entry 0 is written, as in the reference.  'yuv420' with floor-sized chroma and an odd luma size repeats the
     last chroma row / column (the reference raises there: its upsampled planes are one short).
-    coder: 'pillow', or 'device' for a file coded on the device (aivc_amd/png.py): the same pixels, other bytes."""
+    coder: 'pillow', or 'device' for a file coded on the device (aivc_amd/png.py): the same pixels, other bytes.
+    colour: None -- Pillow's YCbCr -> RGB; an aivc_amd.color.ColourSpec -- the planes carry that matrix and range (the modes
+    'yuv420', 'yuv444' and 'yuv444_nodic'; the other two hold no YCbCr, a colour with them is a ValueError)."""
     if mode in ('yuv420', 'yuv444'):
         y, u, v = (_to_u8(_chw(t)) for t in get_y_u_v(x))
         y, u, v = (t.reshape(1, t.shape[-2], t.shape[-1]) for t in (y, u, v))
-        rgb = ops.yuv8_to_rgb8(y, u, v, chroma_shift=1 if mode == 'yuv420' else 0)
+        rgb = _planes_to_rgb(y, u, v, 1 if mode == 'yuv420' else 0, colour)
         _save_png(rgb[0], path_img, 'RGB', coder)
     elif mode == 'yuv444_nodic':
         p = _to_u8(_chw(x))
-        rgb = ops.yuv8_to_rgb8(p[0:1], p[1:2], p[2:3], chroma_shift=0)
+        rgb = _planes_to_rgb(p[0:1], p[1:2], p[2:3], 0, colour)
         _save_png(rgb[0], path_img, 'RGB', coder)
+    elif mode in ('rgb', 'L') and colour is not None:
+        raise ValueError('save_tensor_as_img: mode %r holds no YCbCr planes, colour %s does not apply' % (mode, colour))
     elif mode == 'rgb':
         _save_png(_to_u8(_chw(x)).permute(1, 2, 0), path_img, 'RGB', coder)
     elif mode == 'L':

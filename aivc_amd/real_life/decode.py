@@ -78,27 +78,30 @@ class Decoder(Module):
         return _to_float_dic(rec)
 
 
-def write_png_folder(frames, directory, device, indices, coder='pillow'):
+def write_png_folder(frames, directory, device, indices, coder='pillow', colour=None):
     """decoded frames -> <directory>/<idx>.png, RGB pictures (func_util.img_processing.save_tensor_as_img, mode 'yuv420':
     the colour conversion runs on the device, straight from the decoder's 8-bit planes).  indices: the absolute index of
     every frame handed in.  coder: 'pillow' (one Image.save per frame on the host) or 'device': the planes of a batch of at
     most 256 MiB of pixels take one colour launch and are coded on the device (aivc_amd.png.write_pictures) -- the same names,
-    the same pixels, other bytes"""
+    the same pixels, other bytes.  colour: None -- Pillow's YCbCr -> RGB (BT.601, full range); an aivc_amd.color.ColourSpec --
+    the planes carry that matrix and range (aivc_amd/color.py), with either coder"""
     from .. import png
     png.check_coder(coder)
     os.makedirs(directory, exist_ok=True)
     if coder == 'device' and frames:
-        from .. import ops, rawvideo
+        from .. import rawvideo
+        from ..func_util.img_processing import _planes_to_rgb
         h, w = frames[0]['y'].shape[-2:]
         per = max(1, rawvideo.BATCH_BYTES // (3 * h * w))
         for i0 in range(0, len(frames), per):
             part = frames[i0:i0 + per]
             y, u, v = (torch.cat([torch.as_tensor(fr[k]).to(device).reshape((1,) + tuple(fr[k].shape[-2:])) for fr in part]) for k in 'yuv')
-            png.write_pictures(ops.yuv8_to_rgb8(y, u, v, chroma_shift=1), [os.path.join(directory, '%d.png' % idx) for idx in indices[i0:i0 + per]])
+            png.write_pictures(_planes_to_rgb(y, u, v, 1, colour), [os.path.join(directory, '%d.png' % idx) for idx in indices[i0:i0 + per]])
         return
     from ..func_util.img_processing import save_tensor_as_img
     for idx, fr in zip(indices, frames):
-        save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % idx), mode='yuv420')
+        save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % idx), mode='yuv420',
+                           colour=colour)
 
 
 def is_png_folder(out_file):
@@ -161,10 +164,15 @@ def decode_one_video(param):
     yuv420p into a headerless file is the planes one after the other); the frames that are returned, verified and digested stay
     the 8-bit planes.
     png_coder: 'pillow' (the default) or 'device', who codes the pictures of a folder (write_png_folder); 'device' with an
-    out_file that names a raw video file is a ValueError."""
+    out_file that names a raw video file is a ValueError.
+    colour: None (the default) -- the pictures of a folder are Pillow's YCbCr -> RGB of the planes (BT.601, full range); an
+    aivc_amd.color.ColourSpec -- the planes carry that matrix and range and the pictures are converted by it, in integers on the
+    device (aivc_amd/color.py), after the resize; one `[INFO] colour:` line is printed.  The stream stores no colour description,
+    so this is the caller's to say, as the encoder was told.  Verification keeps digesting the coded planes.  An out_file that
+    names a raw video file is a ValueError: nothing is converted there."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
                'verify': '', 'contract': '', 'frames': None, 'max_level': None, 'out_size': None, 'resample': 'bicubic', 'out_pix_fmt': 'yuv420p',
-               'fps': (25, 1), 'png_coder': 'pillow'}
+               'fps': (25, 1), 'png_coder': 'pillow', 'colour': None}
     decoder = get_value('decoder', param, default).eval()
     path = get_value('bitstream_path', param, default)
     dev = torch.device(get_value('device', param, default))
@@ -182,6 +190,9 @@ def decode_one_video(param):
     raw_out = (out_fmt, tuple(get_value('fps', param, default)))  # (layout, frame rate) of a file that is written
     from .. import png
     png_coder = png.check_coder(get_value('png_coder', param, default), out_file or None, is_png_folder(out_file))
+    from .. import color
+    colour = get_value('colour', param, default)
+    color.check_convertible(colour, 'point', out_file, is_png_folder(out_file), flag='-o')
     manifest = None
     manifest_file = verify if isinstance(verify, str) and verify else digests.manifest_path(path)
     if verify or (contract == 'auto' and os.path.exists(manifest_file)):
@@ -198,7 +209,7 @@ def decode_one_video(param):
         elif contract:
             ops.set_precision(contract)
         return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default),
-                                 resize, raw_out, png_coder)
+                                 resize, raw_out, png_coder, colour)
     finally:
         ops.set_precision(prev_precision)
 
@@ -217,7 +228,8 @@ def read_plan(path, span, max_level):
     return plan._replace(video=video._replace(gops=gops))
 
 
-def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize, raw_out, png_coder='pillow'):
+def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize, raw_out, png_coder='pillow',
+                      colour=None):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel, partial
@@ -259,7 +271,10 @@ def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstre
         from ..func_util.img_processing import resize_frames
         frames = resize_frames(frames, resize[0], resize[1], resize[2], dev)
     if is_png_folder(out_file):
-        write_png_folder(frames, out_file, dev, shown, png_coder)
+        if colour is not None:
+            from .. import color
+            print(color.info_line(colour))
+        write_png_folder(frames, out_file, dev, shown, png_coder, colour)
     elif out_file:  # (after the resize: the export sees the size that is written)
         from .. import rawvideo
         rawvideo.write_raw(frames, out_file, raw_out[0], raw_out[1], dev)

@@ -27,21 +27,28 @@ def read_yuv(path, first=0, last=-1, device=None, pix_fmt=None):
     return frames, first, last
 
 
-def read_png_folder(path, first=0, last=-1, device=None, reader='pillow'):
+def read_png_folder(path, first=0, last=-1, device=None, reader='pillow', colour=None, chroma_down='point'):
     """A folder of the reference's pictures (func_util.img_processing.load_frames: PNG triplets in the old or the clic
     layout, or one RGB PNG per frame; detected from the file names) -> the same list of uint8 plane dicts as read_yuv.
     Frame indices are the ones in the file names; the frame size is the first picture's.  RGB pictures are converted on
     the device and have the reference's floor-sized chroma planes, the codec stores ceil-sized ones: an odd frame size is
     refused for them.  reader: 'pillow' (the default), or 'device' for pictures inflated and unfiltered on the device
-    (aivc_amd.png.read_pictures: the same planes); rank 0 then prints one `[INFO] input:` line."""
-    from .. import parallel, png
+    (aivc_amd.png.read_pictures: the same planes); rank 0 then prints one `[INFO] input:` line.
+    colour: None (the default) -- RGB pictures become planes by Pillow's arithmetic (BT.601, full range); an
+    aivc_amd.color.ColourSpec -- by that matrix and range, chroma_down 'point' (the default) or 'box' (aivc_amd/color.py); rank 0
+    then prints one `[INFO] colour:` line.  With a folder of PNG triplets either is a ValueError: nothing is converted there."""
+    from .. import color, parallel, png
     from ..func_util import img_processing as ip
     png.check_reader(reader)
     mode, rgb, present = ip.detect_folder_layout(path)
+    color.check_convertible(colour, chroma_down, path, rgb)
     last = present[-1] if last < 0 else last
     stats = {'device': 0, 'pillow': 0}
     loaded = ip.load_frames({'sequence_path': path, 'idx_starting_frame': first, 'nb_frame_to_load': last - first + 1,
-                             'rgb': rgb, 'loading_mode': mode, 'device': device, 'png_reader': reader, 'png_stats': stats})
+                             'rgb': rgb, 'loading_mode': mode, 'device': device, 'png_reader': reader, 'png_stats': stats,
+                             'colour': colour, 'chroma_down': chroma_down})
+    if colour is not None and parallel.rank_world()[0] == 0:
+        print(color.info_line(colour, chroma_down))
     if reader == 'device' and parallel.rank_world()[0] == 0:
         print('[INFO] input: %d pictures inflated on the device, %d read by Pillow' % (stats['device'], stats['pillow']))
     frames = [ip.u8_planes(loaded['frame_%d' % i]) for i in range(last - first + 1)]
@@ -86,12 +93,19 @@ def encode(param):
     converted planes, and the log scores against the CONVERTED source.
     png_reader: 'pillow' (the default) or 'device', who reads the pictures of a folder (read_png_folder); 'device' with a
     sequence_path that is no directory is a ValueError.  The bitstream is the same either way.
+    colour: None (the default) -- the RGB pictures of a folder become planes by Pillow's arithmetic (BT.601, full range), and
+    nothing below runs; an aivc_amd.color.ColourSpec (BT.601 / 709 / 2020, full or limited range) -- by that matrix and range, in
+    integers on the device (aivc_amd/color.py), chroma_down 'point' (the default: the chroma of pixel (2i, 2j)) or 'box' (of the
+    2 x 2 block, rounded once).  The conversion runs before the resize, like pix_fmt: header, scene cuts, digests, budgets and
+    the quality log see the converted planes.  One `[INFO] colour:` line is printed.  A sequence_path that holds planes already
+    (a raw video file, a folder of PNG triplets) is a ValueError.  The stream stores no colour description, as it stores no
+    frame rate and no display size: the decoder is told too (decode_one_video: colour).
     The stages: _source (file or folder -> frames), _code (frames -> bitstream), the gathers of what every rank found,
     _write_outputs (manifest, debug digests, bitstream), _report (RESULT lines and the returned dictionary)."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
                'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False, 'scene_cut': None,
-               'size': None, 'resample': 'bicubic', 'pix_fmt': None, 'png_reader': 'pillow'}
+               'size': None, 'resample': 'bicubic', 'pix_fmt': None, 'png_reader': 'pillow', 'colour': None, 'chroma_down': 'point'}
     model = get_value('model', param, default)
     seq = get_value('sequence_path', param, default)
     gop_name = get_value('GOP_struct_name', param, default)
@@ -108,7 +122,8 @@ def encode(param):
         print('ERROR: First frame index bigger than last frame index')
         return
     frames, first, last = _source(seq, first, last, dev, get_value('pix_fmt', param, default), get_value('size', param, default),
-                                  get_value('resample', param, default), get_value('png_reader', param, default))
+                                  get_value('resample', param, default), get_value('png_reader', param, default),
+                                  get_value('colour', param, default), get_value('chroma_down', param, default))
     print_log_msg('INFO', 'Start encoding', '', '')
     t0 = time.time()
     fc = FrameCodec(model)
@@ -177,14 +192,16 @@ def encode(param):
     return _report(final_file, len(blob), n, dt, psnr, seq_res, est_bits, payload, extra)
 
 
-def _source(seq, first, last, dev, pix_fmt, size, resample, png_reader='pillow'):
+def _source(seq, first, last, dev, pix_fmt, size, resample, png_reader='pillow', colour=None, chroma_down='point'):
     """sequence_path -> (frames, first, last): a folder of pictures or a raw video file, then the optional resize.  THE ONE PLACE
-    that looks at what sequence_path is."""
-    from .. import png
+    that looks at what sequence_path is.  colour / chroma_down: how the RGB pictures of a folder become planes (read_png_folder),
+    before the resize like pix_fmt; a ValueError with anything that holds planes already."""
+    from .. import color, png
     png.check_reader(png_reader, seq, os.path.isdir(seq))
     if os.path.isdir(seq):
-        frames, first, last = read_png_folder(seq, first, last, dev, png_reader)
+        frames, first, last = read_png_folder(seq, first, last, dev, png_reader, colour, chroma_down)
     else:
+        color.check_convertible(colour, chroma_down, seq, False)
         frames, first, last = read_yuv(seq, first, last, dev, pix_fmt)
     if size is not None:
         from ..func_util.img_processing import resize_frames

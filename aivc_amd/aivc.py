@@ -8,6 +8,7 @@ import sys
 from aivc_amd import decode as dec_cli
 from aivc_amd import encode as enc_cli
 from aivc_amd import evaluate as eval_cli
+from aivc_amd import options
 
 
 def gop_name(cfg, gop_size, intra_period):
@@ -41,29 +42,7 @@ def parse_args(argv=None):
     p.add_argument('--log_dir', default='', type=str, help="the encoder's per-frame table goes to <log_dir>/detailed.txt (encode.py)")
     p.add_argument('--digests', action='store_true',
                    help='the encoder writes the manifest <bitstream_out>.md5 (encode.py --digests) and the decode is verified against it')
-    dec_cli.add_verify_flag(p)
-    from aivc_amd.cli_common import add_contract_flag
-    add_contract_flag(p, ('fp32', 'fp32w', 'auto'))
-    enc_cli.add_rate_flags(p)
-    enc_cli.add_scene_flag(p)
-    enc_cli.add_pix_fmt_flag(p)
-    enc_cli.add_png_reader_flag(p)
-    dec_cli.add_out_format_flags(p)
-    dec_cli.add_png_coder_flag(p)
-    from aivc_amd.color import add_colour_flags, check_colour_flags
-    add_colour_flags(p)
-    from aivc_amd.resize import add_resize_flags, check_resize_flags
-    add_resize_flags(p, {'--size': enc_cli.SIZE_HELP, '--out_size': dec_cli.OUT_SIZE_HELP})
-    a = p.parse_args(argv)
-    enc_cli.check_rate_flags(p, a)
-    enc_cli.check_scene_flag(p, a)
-    enc_cli.check_png_reader(p, a)
-    a.resample = check_resize_flags(p, a, ('--size', '--out_size'))
-    dec_cli.check_out_size(p, a, a.o)
-    dec_cli.check_out_format(p, a, a.o)
-    dec_cli.check_png_coder(p, a, a.o)
-    check_colour_flags(p, a, in_path=a.i, out_path=a.o, out_is_folder=dec_cli.is_png_folder(a.o))  # (both halves are told)
-    return a
+    return options.parse(p, argv, 'verify', 'rate', 'scene', 'source', 'sink', contract=('fp32', 'fp32w', 'auto'))  # (both halves are told)
 
 
 def input_size(path, pix_fmt=None):
@@ -73,45 +52,26 @@ def input_size(path, pix_fmt=None):
         return reader.w, reader.h
 
 
-def size_text(size):
-    return '%dx%d' % size
-
-
 def main(argv=None):
     a = parse_args(argv)
     gop = gop_name(a.coding_config, a.gop_size, a.intra_period)
     common = ['--model', a.model] + (['--cpu'] if a.cpu else [])
-    colour = ['--matrix', a.colour.matrix, '--range', a.colour.range] if a.colour is not None else []
-    import os
     banner = print if int(os.environ.get('RANK', '0')) == 0 else (lambda *x: None)  # one voice in a multi-rank job
     banner(('*' * 80).center(120))
     banner('Starting encoding'.center(120))
-    enc_cli.main(['-i', a.i, '--gop', gop, '--start_frame', str(a.start_frame), '--end_frame', str(a.end_frame),
-                  '-o', a.bitstream_out, '--rate_step', str(a.rate_step)] + common
-                 + (['--log_dir', a.log_dir] if a.log_dir else [])
-                 + (['--idx_rate', str(a.idx_rate)] if a.idx_rate is not None else [])
-                 + (['--target_bpp', str(a.target_bpp)] if a.target_bpp > 0 else [])
-                 + (['--digests'] if a.digests else [])
-                 + (['--scene_cut', repr(a.scene_cut)] if a.scene_cut is not None else [])
-                 + (['--pix_fmt', a.pix_fmt] if a.pix_fmt is not None else [])
-                 + (['--png_reader', a.png_reader] if a.png_reader != 'pillow' else [])
-                 + colour + (['--chroma_down', a.chroma_down] if a.chroma_down != 'point' else [])
-                 + (['--size', size_text(a.size), '--resample', a.resample] if a.size is not None else [])
+    enc_cli.main(['-i', a.i, '--gop', gop, '--start_frame', str(a.start_frame), '--end_frame', str(a.end_frame), '-o', a.bitstream_out]
+                 + common + (['--log_dir', a.log_dir] if a.log_dir else []) + (['--digests'] if a.digests else [])
+                 + options.argv_of(a, options.RATE + options.SCENE, always=('rate_step',)) + options.argv_of(a.source)
                  + (['--contract', a.contract] if a.contract not in (None, 'auto') else []))  # (auto is the decoder's choice)
     banner(('*' * 80).center(120))
     banner('Starting decoding'.center(120))
-    verify = a.verify if a.verify else bool(a.digests)  # --digests verifies its own decode
-    status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common
-                          + ([] if not verify else ['--verify'] if verify is True else ['--verify', verify])
-                          + (['--out_size', size_text(a.out_size), '--resample', a.resample] if a.out_size is not None else [])
-                          + (['--out_pix_fmt', a.out_pix_fmt] if a.out_pix_fmt != 'yuv420p' else [])
-                          + (['--fps', '%d:%d' % a.fps] if a.fps != (25, 1) else [])
-                          + (['--png_coder', a.png_coder] if a.png_coder != 'pillow' else []) + colour
+    a.verify = a.verify or a.digests or ''  # --digests verifies its own decode
+    status = dec_cli.main(['-i', a.bitstream_out, '-o', a.o] + common + options.argv_of(a, options.VERIFY) + options.argv_of(a.sink)
                           + (['--contract', a.contract] if a.contract else []))
     from aivc_amd import parallel
     if parallel.rank_world()[0] != 0:  # multi-rank job: rank 0 evaluates
         return status
-    if os.path.isdir(a.i) or dec_cli.is_png_folder(a.o):  # (evaluate.py scores planar files)
+    if os.path.isdir(a.i) or options.is_png_folder(a.o):  # (evaluate.py scores planar files)
         print('[INFO] evaluation skipped: it compares two planar .yuv files, -i / -o name picture folders')
         return status
     written = a.out_size if a.out_size is not None else a.size  # the size of the frames in -o, where it was chosen here
@@ -124,7 +84,7 @@ def main(argv=None):
     print('Starting evaluation'.center(120))
     eval_cli.main(['--raw', a.i, '--compressed', a.o, '--bitstream', a.bitstream_out, '--start_frame', str(a.start_frame)]
                   + (['--pix_fmt', a.pix_fmt] if a.pix_fmt is not None else [])
-                  + (['--compressed_pix_fmt', a.out_pix_fmt] if a.out_pix_fmt != 'yuv420p' and not a.o.endswith('.y4m') else []))
+                  + (['--compressed_pix_fmt', a.out_pix_fmt] if a.out_pix_fmt != options.SINK.out_pix_fmt and not a.o.endswith('.y4m') else []))
     return status  # 3: decoded and evaluated, but the stream did not decode cleanly (real_life/decode.py)
 
 

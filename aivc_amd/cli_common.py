@@ -30,15 +30,6 @@ def resolve_device(cpu_flag):
     return dev
 
 
-def add_contract_flag(p, choices):
-    """--contract (encode.py, decode.py, aivc.py): unset is the behaviour without the flag, AIVC_CONTRACT or the library default"""
-    p.add_argument('--contract', default=None, choices=list(choices),
-                   help='arithmetic contract of the run (aivc_amd.ops.set_precision); an encoder and a decoder must agree.  '
-                        'Unset: AIVC_CONTRACT or the library default'
-                        + ('.  auto: the contract named by the manifest <bitstream>.md5, else a trial decode of the first unit'
-                           if 'auto' in choices else ''))
-
-
 class contract_scope:
     """`with contract_scope(name):` the run inside computes in contract `name` (None or 'auto': untouched here), the precision of
     the process is what it was afterwards: tests call the CLIs' main() in-process"""

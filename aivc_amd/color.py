@@ -106,46 +106,6 @@ def is_rgb_folder(path):
         return False
 
 
-MATRIX_HELP = ('the colour matrix of the 8-bit planes (%s): RGB pictures are converted by it, in integers on the device, instead of '
-               'by Pillow\'s arithmetic (BT.601, full range, the default without this flag).  --matrix alone means --range limited, '
-               'video\'s convention.  The stream stores no colour description: encoder and decoder are both told')
-
-
-def add_colour_flags(p, encoder=True, decoder=True):
-    """--matrix / --range, and on the encoder side --chroma_down (encode.py, decode.py, aivc.py)"""
-    side = ' and '.join(([('-i, a folder of RGB pictures')] if encoder else []) + ([('-o, a picture folder')] if decoder else []))
-    p.add_argument('--matrix', default=None, choices=list(MATRICES), help=MATRIX_HELP % ', '.join(MATRICES) + ' (%s)' % side)
-    p.add_argument('--range', default=None, choices=list(RANGES),
-                   help='range of the planes under --matrix: limited (luma 16 ... 235, chroma 16 ... 240; the default) or full')
-    if encoder:
-        p.add_argument('--chroma_down', default='point', choices=list(CHROMA_DOWN),
-                       help='the chroma of a 4:2:0 sample under --matrix: point (of pixel (2i, 2j) alone, the default) or box (of '
-                            'the sum of the 2 x 2 block, rounded once)')
-
-
-def check_colour_flags(p, a, in_path=None, out_path=None, out_is_folder=None):
-    """a.colour becomes None or a ColourSpec; an argparse error for --range / --chroma_down box without --matrix, and for any of
-    the flags where nothing is converted: an input (in_path given) that is no folder of RGB pictures, an output (out_path given)
-    that is no picture folder"""
-    chroma_down = getattr(a, 'chroma_down', 'point')
-    if a.matrix is None:
-        if a.range is not None:
-            p.error('--range %s needs --matrix: without it the conversion is Pillow\'s (BT.601, full range)' % a.range)
-        if chroma_down != 'point':
-            p.error('--chroma_down %s needs --matrix: Pillow\'s conversion keeps the chroma of pixel (2i, 2j)' % chroma_down)
-        a.colour = None
-        return None
-    a.colour = ColourSpec(a.matrix, a.range or 'limited')
-    try:
-        if in_path is not None:
-            check_convertible(a.colour, chroma_down, in_path, is_rgb_folder(in_path))
-        if out_path is not None:
-            check_convertible(a.colour, 'point', out_path, out_is_folder, flag='-o')
-    except ValueError as e:
-        p.error(str(e))
-    return a.colour
-
-
 def _fix(x):
     return int(round(x * (1 << SHIFT)))  # (round() of a Fraction: exact, half to even)
 

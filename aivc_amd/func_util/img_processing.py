@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..options import SINK, SOURCE, Source
 from .nn_util import get_value
 
 
@@ -71,15 +72,13 @@ def _frame_storage_name(sequence_path, absolute_idx, loading_mode):
     raise ValueError('load_frames: loading_mode %r (expected old or clic)' % (loading_mode,))
 
 
-def _rgb_to_planes(rgb, colour=None, chroma_down='point'):
-    """uint8 RGB [n, h, w, 3] on the device -> (y, u, v): Pillow's arithmetic (colour None), or the named one"""
+def _rgb_to_planes(rgb, source):
+    """uint8 RGB [n, h, w, 3] on the device -> (y, u, v): Pillow's arithmetic (source.colour None), or the named one"""
     from .. import color
-    color.check_chroma_down(chroma_down)
-    if colour is None:
-        if chroma_down != 'point':
-            raise ValueError('chroma_down %r needs a colour: Pillow\'s conversion keeps the chroma of pixel (2i, 2j)' % (chroma_down,))
+    color.check_convertible(source.colour, source.chroma_down, None, True)
+    if source.colour is None:
         return ops.rgb8_to_yuv420u8(rgb)
-    return color.rgb_to_yuv420(rgb, colour, chroma_down)
+    return color.rgb_to_yuv420(rgb, source.colour, source.chroma_down)
 
 
 def _planes_to_rgb(y, u, v, chroma_shift, colour=None):
@@ -102,7 +101,7 @@ def load_frames(param):
     and range, chroma_down 'point' (the default: the chroma of pixel (2i, 2j)) or 'box' (of the 2 x 2 block, rounded once).  Both
     apply to rgb folders only, after the pictures have been read by either reader."""
     default = {'sequence_path': None, 'idx_starting_frame': 0, 'nb_frame_to_load': 3, 'nb_pad_frame': 0, 'rgb': False,
-               'loading_mode': 'old', 'device': 'cuda', 'png_reader': 'pillow', 'png_stats': None, 'colour': None, 'chroma_down': 'point'}
+               'loading_mode': 'old', 'device': 'cuda', 'png_stats': None, **SOURCE._asdict()}
     sequence_path = get_value('sequence_path', param, default)
     first = get_value('idx_starting_frame', param, default)
     nb = get_value('nb_frame_to_load', param, default)
@@ -110,29 +109,28 @@ def load_frames(param):
     rgb = get_value('rgb', param, default)
     loading_mode = get_value('loading_mode', param, default)
     device = get_value('device', param, default)
-    colour, chroma_down = get_value('colour', param, default), get_value('chroma_down', param, default)
-    if not rgb and (colour is not None or chroma_down != 'point'):
-        raise ValueError('load_frames: colour / chroma_down convert RGB pictures; %s holds planes' % sequence_path)
+    source = Source.from_param(param)
+    from .. import color, png
+    color.check_convertible(source.colour, source.chroma_down, sequence_path, rgb)
     if not sequence_path.endswith('/'):
         sequence_path += '/'
     last_loaded = first + nb - nb_pad - 1
-    from .. import png
-    if png.check_reader(get_value('png_reader', param, default)) == 'device':
+    if png.check_reader(source.png_reader) == 'device':
         idx = [min(first + gop_idx, last_loaded) for gop_idx in range(nb)]
         read = _load_on_device({i: _frame_storage_name(sequence_path, i, loading_mode) for i in sorted(set(idx))}, rgb, device,
-                               get_value('png_stats', param, default), colour, chroma_down)
+                               get_value('png_stats', param, default), source)
         return {'frame_' + str(gop_idx): _from_u8(read[i], 4) for gop_idx, i in enumerate(idx)}
     frames = {}
     for gop_idx in range(nb):
         name = _frame_storage_name(sequence_path, min(first + gop_idx, last_loaded), loading_mode)
         if rgb:
-            frames['frame_' + str(gop_idx)] = load_RGB_as_YUV420_dic(name, device, colour=colour, chroma_down=chroma_down)
+            frames['frame_' + str(gop_idx)] = load_RGB_as_YUV420_dic(name, device, colour=source.colour, chroma_down=source.chroma_down)
         else:
             frames['frame_' + str(gop_idx)] = _with_batch_dim(load_YUV_as_dic_tensor(name, device))
     return frames
 
 
-def _load_on_device(names, rgb, device, stats=None, colour=None, chroma_down='point'):
+def _load_on_device(names, rgb, device, stats=None, source=SOURCE):
     """{frame index: storage name} -> {frame index: uint8 planes {'y','u','v'} of [1, h, w]}: one read_pictures call for the clip"""
     from .. import png
     order = list(names)
@@ -143,7 +141,7 @@ def _load_on_device(names, rgb, device, stats=None, colour=None, chroma_down='po
     out = {}
     for shape in sorted({tuple(p.shape) for p in pics}):  # (a clip has one size: one colour launch)
         group = [n for n, p in enumerate(pics) if tuple(p.shape) == shape]
-        y, u, v = _rgb_to_planes(torch.stack([pics[n] for n in group]), colour, chroma_down)
+        y, u, v = _rgb_to_planes(torch.stack([pics[n] for n in group]), source)
         for j, n in enumerate(group):
             out[order[n]] = {'y': y[j:j + 1], 'u': u[j:j + 1], 'v': v[j:j + 1]}
     return out
@@ -175,25 +173,26 @@ def _from_u8(planes, ndim):
     return out
 
 
-def load_RGB_as_YUV420_dic(path_img, device='cuda', reader='pillow', colour=None, chroma_down='point'):
+def load_RGB_as_YUV420_dic(path_img, device='cuda', reader=SOURCE.png_reader, colour=SOURCE.colour, chroma_down=SOURCE.chroma_down):
     """<path_img>.png, an RGB picture -> {'y': [1,1,h,w], 'u','v': [1,1,h//2,w//2]} (src/func_util/img_processing.py:179-196):
     Pillow's 8-bit RGB -> YCbCr, chroma sample (2i, 2j) kept (nearest, scale 0.5), on the device.  A PNG of another mode
     (palette, grey, alpha) is first brought to 8-bit RGB by Pillow, as part of decoding the file.  reader 'device': the file is
     inflated on the device (aivc_amd.png.read_pictures), the same planes.  colour: an aivc_amd.color.ColourSpec -- that matrix
     and range instead of Pillow's arithmetic, chroma_down 'point' or 'box' (aivc_amd/color.py); the planes keep their sizes."""
     from .. import png
+    source = Source(colour=colour, chroma_down=chroma_down)
     if png.check_reader(reader) == 'device':
-        return _from_u8(_load_on_device({0: path_img}, True, device, None, colour, chroma_down)[0], 4)
+        return _from_u8(_load_on_device({0: path_img}, True, device, None, source)[0], 4)
     from PIL import Image
     img = Image.open(path_img + '.png')
     if img.mode != 'RGB':
         img = img.convert('RGB')
     rgb = torch.from_numpy(np.asarray(img).copy()).to(device)
-    y, u, v = _rgb_to_planes(rgb.view(1, *rgb.shape), colour, chroma_down)
+    y, u, v = _rgb_to_planes(rgb.view(1, *rgb.shape), source)
     return _from_u8({'y': y, 'u': u, 'v': v}, 4)
 
 
-def load_YUV_as_dic_tensor(path_img, device='cuda', reader='pillow'):
+def load_YUV_as_dic_tensor(path_img, device='cuda', reader=SOURCE.png_reader):
     """<path_img>_{y,u,v}.png, 8-bit grey pictures -> {'y','u','v'} of 3-D tensors [1, h, w], no batch dimension
     (src/func_util/img_processing.py:199-218).  reader 'device': inflated on the device, the same planes."""
     from .. import png
@@ -219,7 +218,7 @@ def _chw(x):
     return x[0] if x.ndim == 4 else x
 
 
-def _save_png(a, path_img, mode, coder='pillow'):
+def _save_png(a, path_img, mode, coder=SINK.png_coder):
     """a: uint8 [h, w, 3] ('RGB') or [h, w] ('L').  coder 'device': coded where the tensor lies (aivc_amd.png.write_pictures)"""
     from .. import png
     if png.check_coder(coder) == 'device':
@@ -229,7 +228,7 @@ def _save_png(a, path_img, mode, coder='pillow'):
     Image.fromarray(np.ascontiguousarray(a.cpu().numpy()), mode).save(path_img)
 
 
-def save_tensor_as_img(x, path_img, mode='yuv420', coder='pillow', colour=None):
+def save_tensor_as_img(x, path_img, mode='yuv420', coder=SINK.png_coder, colour=SINK.colour):
     """src/func_util/img_processing.py:221-287.  x holds floats in [0, 1] (cast like to_pil_image: mul(255), truncated) or uint8
     levels, on the device.
       'yuv420'        x: dict, chroma at half resolution -> nearest x 2, cropped to the luma size, YCbCr -> RGB on the device
@@ -267,7 +266,7 @@ def save_yuv_separately(x, path_img):
         _save_png(_to_u8(_chw(x[key]))[0], path_img + '_' + key + '.png', 'L')
 
 
-def resize_frames(frames, w, h, filter='bicubic', device=None):
+def resize_frames(frames, w, h, filter=SOURCE.resample, device=None):
     """A list of 4:2:0 frames, dicts of uint8 planes {'y','u','v'} of [1, h0, w0] (device tensors, or host tensors / arrays: those
     are copied to `device`), resized to w x h on the device: y to h x w, u and v to ceil(h / 2) x ceil(w / 2), every plane on its
     own with Pillow's Image.resize arithmetic (ops.resize_u8) -- exactly what resizing each picture of a PNG triplet with Pillow

@@ -13,6 +13,7 @@ from ..codec import FrameCodec
 from ..func_util.console_display import print_log_msg
 from ..func_util.nn_util import get_value
 from ..models.full_net import _to_float_dic, _to_u8_planes
+from ..options import SINK, Sink, is_png_folder
 from .utils import BITSTREAM_SUFFIX
 
 
@@ -78,7 +79,7 @@ class Decoder(Module):
         return _to_float_dic(rec)
 
 
-def write_png_folder(frames, directory, device, indices, coder='pillow', colour=None):
+def write_png_folder(frames, directory, device, indices, coder=SINK.png_coder, colour=SINK.colour):
     """decoded frames -> <directory>/<idx>.png, RGB pictures (func_util.img_processing.save_tensor_as_img, mode 'yuv420':
     the colour conversion runs on the device, straight from the decoder's 8-bit planes).  indices: the absolute index of
     every frame handed in.  coder: 'pillow' (one Image.save per frame on the host) or 'device': the planes of a batch of at
@@ -102,11 +103,6 @@ def write_png_folder(frames, directory, device, indices, coder='pillow', colour=
     for idx, fr in zip(indices, frames):
         save_tensor_as_img({k: torch.as_tensor(fr[k]).to(device) for k in 'yuv'}, os.path.join(directory, '%d.png' % idx), mode='yuv420',
                            colour=colour)
-
-
-def is_png_folder(out_file):
-    """the opt-in of -o: a name that ends in '/' or an existing directory asks for RGB pictures, anything else for a .yuv"""
-    return bool(out_file) and (out_file.endswith('/') or os.path.isdir(out_file))
 
 
 def digest_frames(frames, device):
@@ -171,8 +167,7 @@ def decode_one_video(param):
     so this is the caller's to say, as the encoder was told.  Verification keeps digesting the coded planes.  An out_file that
     names a raw video file is a ValueError: nothing is converted there."""
     default = {'decoder': None, 'bitstream_path': '', 'device': 'cuda:0', 'out_file': '', 'flag_bitstream_debug': False,
-               'verify': '', 'contract': '', 'frames': None, 'max_level': None, 'out_size': None, 'resample': 'bicubic', 'out_pix_fmt': 'yuv420p',
-               'fps': (25, 1), 'png_coder': 'pillow', 'colour': None}
+               'verify': '', 'contract': '', 'frames': None, 'max_level': None, **SINK._asdict()}
     decoder = get_value('decoder', param, default).eval()
     path = get_value('bitstream_path', param, default)
     dev = torch.device(get_value('device', param, default))
@@ -183,16 +178,8 @@ def decode_one_video(param):
     plan = read_plan(path, get_value('frames', param, default), get_value('max_level', param, default))
     from .. import digests, ops, parallel
     _VERIFY_BAD[0] = 0
-    out_size = get_value('out_size', param, default)
-    resize = None if out_size is None else (int(out_size[0]), int(out_size[1]), get_value('resample', param, default))
-    from .. import rawvideo
-    out_fmt = rawvideo.check_writable(get_value('out_pix_fmt', param, default), '' if is_png_folder(out_file) else out_file)
-    raw_out = (out_fmt, tuple(get_value('fps', param, default)))  # (layout, frame rate) of a file that is written
-    from .. import png
-    png_coder = png.check_coder(get_value('png_coder', param, default), out_file or None, is_png_folder(out_file))
-    from .. import color
-    colour = get_value('colour', param, default)
-    color.check_convertible(colour, 'point', out_file, is_png_folder(out_file), flag='-o')
+    sink = Sink.from_param(param)
+    sink.check(out_file, odd_pictures=True)
     manifest = None
     manifest_file = verify if isinstance(verify, str) and verify else digests.manifest_path(path)
     if verify or (contract == 'auto' and os.path.exists(manifest_file)):
@@ -208,8 +195,7 @@ def decode_one_video(param):
             ops.set_precision(choice)
         elif contract:
             ops.set_precision(contract)
-        return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default),
-                                 resize, raw_out, png_coder, colour)
+        return _decode_one_video(decoder, path, plan, dev, out_file, manifest, get_value('flag_bitstream_debug', param, default), sink)
     finally:
         ops.set_precision(prev_precision)
 
@@ -228,8 +214,7 @@ def read_plan(path, span, max_level):
     return plan._replace(video=video._replace(gops=gops))
 
 
-def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, resize, raw_out, png_coder='pillow',
-                      colour=None):
+def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstream_debug, sink):
     print_log_msg('INFO', 'Start decoding', '', '')
     t0 = time.time()
     from .. import parallel, partial
@@ -267,17 +252,17 @@ def _decode_one_video(decoder, path, plan, dev, out_file, manifest, flag_bitstre
     if manifest is not None:  # (queued now, read after the frames have been written)
         found = digest_frames(frames, dev)
     coded = frames
-    if resize is not None:  # (after the digests: they are the coded planes')
+    if sink.out_size is not None:  # (after the digests: they are the coded planes')
         from ..func_util.img_processing import resize_frames
-        frames = resize_frames(frames, resize[0], resize[1], resize[2], dev)
+        frames = resize_frames(frames, int(sink.out_size[0]), int(sink.out_size[1]), sink.resample, dev)
     if is_png_folder(out_file):
-        if colour is not None:
+        if sink.colour is not None:
             from .. import color
-            print(color.info_line(colour))
-        write_png_folder(frames, out_file, dev, shown, png_coder, colour)
+            print(color.info_line(sink.colour))
+        write_png_folder(frames, out_file, dev, shown, sink.png_coder, sink.colour)
     elif out_file:  # (after the resize: the export sees the size that is written)
         from .. import rawvideo
-        rawvideo.write_raw(frames, out_file, raw_out[0], raw_out[1], dev)
+        rawvideo.write_raw(frames, out_file, sink.out_pix_fmt, tuple(sink.fps), dev)
     dist_barrier_after_write(world)
     if manifest is not None:  # the frames returned against their rows of the manifest; a whole decode against all of it
         from .. import digests

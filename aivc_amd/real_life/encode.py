@@ -9,6 +9,7 @@ import torch
 from ..codec import FrameCodec
 from ..func_util.console_display import print_log_msg
 from ..func_util.nn_util import get_value
+from ..options import SOURCE, Source
 
 
 def read_yuv(path, first=0, last=-1, device=None, pix_fmt=None):
@@ -27,7 +28,7 @@ def read_yuv(path, first=0, last=-1, device=None, pix_fmt=None):
     return frames, first, last
 
 
-def read_png_folder(path, first=0, last=-1, device=None, reader='pillow', colour=None, chroma_down='point'):
+def read_png_folder(path, first=0, last=-1, device=None, reader=SOURCE.png_reader, colour=SOURCE.colour, chroma_down=SOURCE.chroma_down):
     """A folder of the reference's pictures (func_util.img_processing.load_frames: PNG triplets in the old or the clic
     layout, or one RGB PNG per frame; detected from the file names) -> the same list of uint8 plane dicts as read_yuv.
     Frame indices are the ones in the file names; the frame size is the first picture's.  RGB pictures are converted on
@@ -36,12 +37,12 @@ def read_png_folder(path, first=0, last=-1, device=None, reader='pillow', colour
     (aivc_amd.png.read_pictures: the same planes); rank 0 then prints one `[INFO] input:` line.
     colour: None (the default) -- RGB pictures become planes by Pillow's arithmetic (BT.601, full range); an
     aivc_amd.color.ColourSpec -- by that matrix and range, chroma_down 'point' (the default) or 'box' (aivc_amd/color.py); rank 0
-    then prints one `[INFO] colour:` line.  With a folder of PNG triplets either is a ValueError: nothing is converted there."""
+    then prints one `[INFO] colour:` line.  With a folder of PNG triplets either is a ValueError (load_frames): nothing is converted
+    there."""
     from .. import color, parallel, png
     from ..func_util import img_processing as ip
     png.check_reader(reader)
     mode, rgb, present = ip.detect_folder_layout(path)
-    color.check_convertible(colour, chroma_down, path, rgb)
     last = present[-1] if last < 0 else last
     stats = {'device': 0, 'pillow': 0}
     loaded = ip.load_frames({'sequence_path': path, 'idx_starting_frame': first, 'nb_frame_to_load': last - first + 1,
@@ -104,8 +105,7 @@ def encode(param):
     _write_outputs (manifest, debug digests, bitstream), _report (RESULT lines and the returned dictionary)."""
     default = {'model': None, 'sequence_path': '', 'GOP_struct_name': '', 'GOP_struct': None, 'idx_rate': 0.,
                'final_file': '', 'flag_bitstream_debug': False, 'idx_starting_frame': 0, 'idx_end_frame': -1,
-               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False, 'scene_cut': None,
-               'size': None, 'resample': 'bicubic', 'pix_fmt': None, 'png_reader': 'pillow', 'colour': None, 'chroma_down': 'point'}
+               'working_dir': '', 'target_bpp': 0., 'rate_step': 1 / 16, 'digests': False, 'scene_cut': None, **SOURCE._asdict()}
     model = get_value('model', param, default)
     seq = get_value('sequence_path', param, default)
     gop_name = get_value('GOP_struct_name', param, default)
@@ -121,9 +121,7 @@ def encode(param):
     if first > last and last != -1:
         print('ERROR: First frame index bigger than last frame index')
         return
-    frames, first, last = _source(seq, first, last, dev, get_value('pix_fmt', param, default), get_value('size', param, default),
-                                  get_value('resample', param, default), get_value('png_reader', param, default),
-                                  get_value('colour', param, default), get_value('chroma_down', param, default))
+    frames, first, last = _source(seq, first, last, dev, Source.from_param(param))
     print_log_msg('INFO', 'Start encoding', '', '')
     t0 = time.time()
     fc = FrameCodec(model)
@@ -192,20 +190,17 @@ def encode(param):
     return _report(final_file, len(blob), n, dt, psnr, seq_res, est_bits, payload, extra)
 
 
-def _source(seq, first, last, dev, pix_fmt, size, resample, png_reader='pillow', colour=None, chroma_down='point'):
+def _source(seq, first, last, dev, source):
     """sequence_path -> (frames, first, last): a folder of pictures or a raw video file, then the optional resize.  THE ONE PLACE
-    that looks at what sequence_path is.  colour / chroma_down: how the RGB pictures of a folder become planes (read_png_folder),
-    before the resize like pix_fmt; a ValueError with anything that holds planes already."""
-    from .. import color, png
-    png.check_reader(png_reader, seq, os.path.isdir(seq))
+    that looks at what sequence_path is; source, an aivc_amd.options.Source, is checked against it before anything is read."""
+    source.check(seq)
     if os.path.isdir(seq):
-        frames, first, last = read_png_folder(seq, first, last, dev, png_reader, colour, chroma_down)
+        frames, first, last = read_png_folder(seq, first, last, dev, source.png_reader, source.colour, source.chroma_down)
     else:
-        color.check_convertible(colour, chroma_down, seq, False)
-        frames, first, last = read_yuv(seq, first, last, dev, pix_fmt)
-    if size is not None:
+        frames, first, last = read_yuv(seq, first, last, dev, source.pix_fmt)
+    if source.size is not None:
         from ..func_util.img_processing import resize_frames
-        frames = resize_frames(frames, int(size[0]), int(size[1]), resample, dev)
+        frames = resize_frames(frames, int(source.size[0]), int(source.size[1]), source.resample, dev)
     return frames, first, last
 
 

@@ -1,5 +1,5 @@
 """Pillow's 8-bit resampling, host half: the integer coefficient tables of one axis (include/aivc_hip_resize.h states the
-arithmetic, aivc_amd.ops.resize_u8 runs it on the device) and the WxH / --resample flags of the command lines.
+arithmetic, aivc_amd.ops.resize_u8 runs it on the device) and the WxH sizes of the command lines (aivc_amd/options.py).
 
 The tables are Image.resize's on an 'L' picture (reducing_gap=None, the whole picture as box), bit for bit: doubles, math.sin /
 math.cos and the expression order of Pillow's precompute_coeffs / normalize_coeffs_8bpc.  tests/resize_cases.py restates the
@@ -133,25 +133,8 @@ def parse_size(text):
     return w, h
 
 
-def _size_arg(text):
-    import argparse
-    try:
-        return parse_size(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-
-
-def add_resize_flags(p, flags):
-    """`flags`: {'--size': help, ...} -- the size flags of this command line, and --resample (encode.py, decode.py, aivc.py)"""
-    for flag, text in flags.items():
-        p.add_argument(flag, default=None, type=_size_arg, metavar='WxH', help=text)
-    p.add_argument('--resample', default=None, choices=list(FILTERS),
-                   help="the filter of %s: Pillow's Image.resize on every 8-bit plane, bit for bit, on the device; default %s "
-                        "(Pillow's own default)" % (' / '.join(flags), DEFAULT_FILTER))
-
-
-def check_resize_flags(p, a, flags):
-    """an argparse error for --resample without any of the size flags; -> the filter name (the default where none is given)"""
-    if a.resample is not None and all(getattr(a, f.lstrip('-')) is None for f in flags):
-        p.error('--resample %s: needs %s (nothing is resized without a size)' % (a.resample, ' or '.join(flags)))
-    return DEFAULT_FILTER if a.resample is None else a.resample
+def check_resample(resample, sizes):
+    """a ValueError for a filter where nothing is resized: `sizes`, {flag: size or None}, holds no size.  In the style of
+    aivc_amd.png.check_reader / check_coder."""
+    if resample is not None and all(v is None for v in sizes.values()):
+        raise ValueError('--resample %s: needs %s (nothing is resized without a size)' % (resample, ' or '.join(sizes)))

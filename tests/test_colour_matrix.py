@@ -297,15 +297,16 @@ def test_library_defaults_and_refusals(folders):
     assert sig(ip.load_RGB_as_YUV420_dic).parameters['chroma_down'].default == 'point'
     assert sig(ip.save_tensor_as_img).parameters['colour'].default is None
     assert sig(enc.read_png_folder).parameters['colour'].default is None and sig(enc.read_png_folder).parameters['chroma_down'].default == 'point'
-    assert sig(enc._source).parameters['colour'].default is None and sig(enc._source).parameters['chroma_down'].default == 'point'
+    from aivc_amd.options import Source
+    assert Source().colour is None and Source().chroma_down == 'point'
     assert sig(dec.write_png_folder).parameters['colour'].default is None
     assert list(sig(dec.write_png_folder).parameters)[:5] == ['frames', 'directory', 'device', 'indices', 'coder']
     spec = color.ColourSpec('bt709')
     for seq in (folders['raw'], folders['planes']):
         with pytest.raises(ValueError):
-            enc._source(seq, 0, -1, None, None, None, 'bicubic', 'pillow', spec, 'point')
+            enc._source(seq, 0, -1, None, Source(colour=spec))
     with pytest.raises(ValueError):
-        enc._source(folders['rgb'], 0, -1, None, None, None, 'bicubic', 'pillow', None, 'box')
+        enc._source(folders['rgb'], 0, -1, None, Source(chroma_down='box'))
     with pytest.raises(ValueError):
         ip.save_tensor_as_img(None, 'x.png', mode='rgb', colour=spec)
     assert color.info_line(spec) == '[INFO] colour: bt709 limited' and color.info_line(spec, 'box') == '[INFO] colour: bt709 limited, box chroma'

@@ -87,7 +87,8 @@ def test_default_arguments_keep_the_pillow_path():
     from aivc_amd.func_util import img_processing
     from aivc_amd.real_life import encode
     assert inspect.signature(encode.read_png_folder).parameters['reader'].default == 'pillow'
-    assert inspect.signature(encode._source).parameters['png_reader'].default == 'pillow'
+    from aivc_amd.options import Source
+    assert Source().png_reader == 'pillow'
     assert inspect.signature(img_processing.load_RGB_as_YUV420_dic).parameters['reader'].default == 'pillow'
     assert inspect.signature(img_processing.load_YUV_as_dic_tensor).parameters['reader'].default == 'pillow'
     with pytest.raises(ValueError):
